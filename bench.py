@@ -6,8 +6,8 @@ Default workload (--config c3 = BASELINE.json configs[2], the configuration the 
 of SURVEY.md 8d. One "step" = one ranging epoch for every tag: predict + full iterated update fusing the epoch's
 accelerometer sample, and the resulting pose written out. All inputs for every step are resident in HBM before the
 timed region. The trace is replayed with kfpos_run_trace_dev: --epochs-per-launch epochs per kernel launch (the
-per-tag state stays in registers between them). The same K epochs are also replayed with ONE launch (and, with several
-ranks, one pose all-gather) per epoch -- what a live 20 Hz node pays -- and reported as `per_epoch_launch`.
+per-tag state stays in registers between them). With --full the same K epochs are also replayed with ONE launch (and,
+with several ranks, one pose all-gather) per epoch -- what a live 20 Hz node pays -- and reported as `per_epoch_launch`.
 
 --config c4 = BASELINE.json configs[3]: 1 048 576 tags x 8 anchors in total, UWB-only 6-state EKF, f64, the tag batch
 split over the ranks by dist.shard_range (strong scaling: the total is fixed), poses exchanged with one RCCL all-gather
@@ -25,8 +25,19 @@ inputs; the pose all-gather runs on a side stream, overlapped with the next laun
 communicator behind the C ABI (kfpos_allgather_poses) when every rank has a GPU of its own, through torch.distributed
 otherwise (gloo rehearsals of several ranks on one card; roskfpos_amd/dist.py).
 
-Prints ONE JSON line on rank 0 (contract in the task description), with `roofline` for the step kernel
-and `cpu_baseline` = the oracle timed on the host cores over a bounded sample of the same workload.
+Prints ONE JSON line on rank 0 (contract in the task description), with `roofline` for the step kernel. A plain run
+does only what that headline needs: set-up, warm-up (the run rehearsed on throwaway banks, REHEARSAL_EPOCHS epochs at
+least), --warmup W untimed epochs and exactly --steps K timed epochs on a fresh bank, and the line. The trace is
+generated on the device (trace_on_device), so the set-up stays seconds at any K.
+
+--full adds everything else, as measured before: the timed K epochs repeated (--repeats, default 3 there, median
+reported), `per_epoch_launch`, `secondary` (the 6-state filter and the P48 covariance on the same trace), and
+`cpu_baseline` = the oracle timed on the host cores over a bounded sample of the same workload, with the GPU's RMS
+position difference against it.
+
+--dump-outputs DIR: after the timed epochs, what the timed path handed its caller after the last one -- rank 0's pose
+of that epoch (pose.npy, [T][3]), filter state (state.npy, [T][n]) and covariance (covariance.npy, [T][n][n]), f64.
+Above 64 MB in all, a fixed seeded sample of tags (sampled_tags.npy holds their indices).
 
 --dry-run: no GPU, no filter -- the launcher, the rendezvous, the shard arithmetic, the gather plumbing (gloo, CPU
 tensors) and the JSON contract only. `value` is null and the line says so; used by the CPU test-suite.
@@ -46,12 +57,15 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from roskfpos_amd import capi  # noqa: E402  (ctypes only: nothing here touches the GPU until a bank is created)
-from roskfpos_amd.dist import GATHER_MODES, ShardedReplay, device_trace, env_world, shard_range  # noqa: E402
+from roskfpos_amd import capi, synth  # noqa: E402  (ctypes only: nothing here touches the GPU until a bank is created)
+from roskfpos_amd.dist import GATHER_MODES, ShardedReplay, env_world, shard_range  # noqa: E402
 from roskfpos_amd.synth import Workload  # noqa: E402
 
 ANCHORS = 8
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20
+REHEARSAL_EPOCHS = 3000  # ~0.1 s of the c3 kernel at 65 536 tags
+TRACE_CHUNK = 1 << 24  # draws per generator pass in trace_on_device: ~1 GB of temporaries at most
 
 # SURVEY.md 8d, algorithmic bytes per tag-step:
 #   c3: read x(9) + packed P(45) as f32, write them back, 8 int32 ranges + 8 f32 errorEstimations,
@@ -182,6 +196,93 @@ def host_cores() -> int:
     return n
 
 
+# synth.Workload's draws evaluated on the device. The host generator (dist.device_trace) costs tens of ms per epoch at
+# 65 536 tags -- about a thousand epochs of the filter -- so the set-up of a long run would dwarf its timed part. Same
+# formulas in the same operation order: on CPU tensors the trace equals the host's bit for bit
+# (tests/test_bench_launch.py); the device's log / cos / sin may differ from the host's in the last bit, which moves a
+# range across a millimetre or an f32 acceleration across a rounding step in about one draw in 1e9.
+def _as_int64(c) -> int:
+    """a uint64 constant of synth as the int64 with the same bits: int64 products and sums wrap like uint64 ones"""
+    c = int(c)
+    return c - (1 << 64) if c >= 1 << 63 else c
+
+
+_GOLD, _M1, _M2 = (_as_int64(c) for c in (synth._GOLD, synth._M1, synth._M2))
+
+
+def _srl(z, k: int):
+    """logical right shift of int64 bits"""
+    return (z >> k) & ((1 << (64 - k)) - 1)
+
+
+def _mix(z):
+    z = (z ^ _srl(z, 30)) * _M1
+    z = (z ^ _srl(z, 27)) * _M2
+    return z ^ _srl(z, 31)
+
+
+def _normal(torch, key, counter):
+    """synth._normal for int64 tensors `key` and `counter` broadcast against each other"""
+    def uniform(c):
+        return _srl(_mix(key + _GOLD * c), 11).to(torch.float64) * (1.0 / 9007199254740992.0)
+    u1 = 1.0 - uniform(counter)
+    u2 = uniform(counter + 1)
+    return torch.sqrt(-2.0 * torch.log(u1)) * torch.cos(2.0 * np.pi * u2)
+
+
+def trace_on_device(torch, w, n_steps: int, device, with_imu: bool, real):
+    """dist.device_trace(torch, w, n_steps, device, with_imu, real) with the per-epoch draws made on `device`:
+    ranges [S][A][T] int32, accel [S][3][T] and cov [9][T] of `real` (9-state only), err [A][T] `real`, dts (S,) host
+    array, traj [S][3][T] f64."""
+    T, A = w.n_tags, w.n_anchors
+    f64 = torch.float64
+    tr = {"ranges": torch.empty((n_steps, A, T), dtype=torch.int32, device=device),
+          "dts": np.array([w.dt_of(s) for s in range(n_steps)])}
+    if with_imu:
+        tr["accel"] = torch.empty((n_steps, 3, T), dtype=torch.float32 if real == np.float32 else f64, device=device)
+        tr["cov"] = torch.from_numpy(np.ascontiguousarray(w.accel_cov(real).T)).to(device)
+    key = torch.from_numpy(w._key.view(np.int64)).to(device)
+    rho, omega, phi = (torch.from_numpy(v).to(device) for v in (w.rho, w.omega, w.phi))
+    anchors = [torch.from_numpy(np.ascontiguousarray(w.anchors[:, k])).to(device)[:, None] for k in range(3)]
+    chunk = max(1, TRACE_CHUNK // (A * T))  # epochs per pass
+    for s0 in range(0, n_steps, chunk):
+        steps = torch.arange(s0, min(s0 + chunk, n_steps), dtype=torch.int64, device=device)
+        t = (synth.DT_FIRST + synth.DT * steps.to(f64))[:, None]  # Workload.time_of, one row per epoch
+        ang = omega * t + phi
+        pos = (5.0 + rho * torch.cos(ang), 5.0 + rho * torch.sin(ang), 1.0 + 0.2 * torch.sin(0.1 * t + phi))
+        d2 = None
+        for k in range(3):
+            diff = pos[k][:, None, :] - anchors[k]
+            d2 = diff * diff if d2 is None else d2 + diff * diff
+        ch = ((steps + 1) * 256)[:, None, None] + 2 * torch.arange(A, device=device)[None, :, None]
+        noise = _normal(torch, key, ch)
+        tr["ranges"][s0:s0 + len(steps)] = torch.floor((torch.sqrt(d2) + synth.RANGE_SIGMA * noise) * 1000.0)
+        if with_imu:
+            w2 = omega * omega
+            acc = torch.stack([-rho * w2 * torch.cos(ang), -rho * w2 * torch.sin(ang),
+                               -0.2 * 0.01 * torch.sin(0.1 * t + phi)], dim=1)
+            ch = ((steps + 1) * 256 + 200)[:, None, None] + 2 * torch.arange(3, device=device)[None, :, None]
+            tr["accel"][s0:s0 + len(steps)] = acc + synth.ACC_SIGMA * _normal(torch, key, ch)
+    tr["err"] = torch.from_numpy(np.ascontiguousarray(w.err_est(real).T)).to(device)
+    tr["traj"] = torch.zeros((n_steps, 3, T), dtype=f64, device=device)
+    return tr
+
+
+def dump_outputs(path, pose, x, P):
+    """pose [T][3], state x [T][n] and covariance P [T][n][n] as f64 .npy files under `path`; above DUMP_LIMIT_BYTES
+    in all, a fixed seeded sample of tags, in ascending order, with their indices in sampled_tags.npy"""
+    arrays = {"pose": pose, "state": x, "covariance": P}
+    per_tag = sum(a[0].size for a in arrays.values()) * 8
+    T = x.shape[0]
+    if per_tag * T > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(T, DUMP_LIMIT_BYTES // (per_tag + 8), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["sampled_tags"] = keep
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def cpu_baseline_and_rms(cfg, w, sample_tags, sample_steps, threads):
     """Oracle (the CPU restatement of the reference path) on a bounded sample of the same workload,
     and the GPU's RMS position difference against it on that sample."""
@@ -286,15 +387,24 @@ def main():
                     help="epochs fused into one kernel launch (state resident in registers); 1 = one launch per epoch")
     ap.add_argument("--gather", choices=GATHER_MODES, default="launch",
                     help="pose all-gather of the main measurement with several ranks (dist.ShardedReplay)")
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--full", action="store_true",
+                    help="also the repeats, the one-launch-per-epoch line, the secondary lines and the CPU baseline")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed K epochs are run this many times, each on a fresh bank after its own warm-up; the "
-                         "line reports the median run and the spread of all of them")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-per-epoch", action="store_true", help="skip the extra one-launch-per-epoch measurement")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the 6-state 65536 x 8 line of the c3 run")
+                         "line reports the median run and the spread of all of them (default 1; 3 with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-per-epoch", action="store_true", help="--full without the one-launch-per-epoch measurement")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary lines of the c3 run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed epochs, write rank 0's pose, state and covariance after the last one to "
+                         "DIR/*.npy (f64, at most 64 MB: a fixed seeded sample of tags above that)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU, no filter: launcher / rendezvous / gather plumbing / JSON contract only (value null)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs needs a real run: --dry-run computes nothing")
     cfg = CONFIGS[args.config]
 
     rank, local_rank, world = env_world()
@@ -349,7 +459,7 @@ def run(args, cfg, torch, dist, rank, local_rank, world, backend, device, n_dev,
     imu = cfg["model"] == capi.MODEL_TOA_IMU
     real = np.float64 if cfg["storage"] == capi.STORE_F64 else np.float32
     w = Workload(T, ANCHORS, tag0=lo)
-    trace = device_trace(torch, w, W + K, device, imu, real)
+    trace = trace_on_device(torch, w, W + K, device, imu, real)
     # every kfpos launch and every copy into the gather buffers goes to torch's current stream, so that the HIP
     # events of kfpos_timing_* and torch's stream semantics see the same queue
     stream = None if dry else torch.cuda.current_stream().cuda_stream
@@ -415,9 +525,9 @@ def run(args, cfg, torch, dist, rank, local_rank, world, backend, device, n_dev,
         gathers = rep.gather.count - g0 if rep.gather else 0
         return elapsed, kernel_ms, rep.launches, gathers, bank
 
-    # ---- secondary measurements first (they also bring the chip to its steady clocks under this fp64 load) ----
+    # ---- --full: secondary measurements first (they also bring the chip to its steady clocks under this fp64 load) ----
     per_epoch = None
-    if not args.no_per_epoch and E != 1:
+    if args.full and not args.no_per_epoch and E != 1:
         e1, k1, l1, g1, b1 = measure(1, "epoch")
         b1.close()
         per_epoch = {"value": None if dry else total * K / e1, "unit": "tag-steps/s", "ms_per_step": e1 * 1e3 / K,
@@ -427,7 +537,8 @@ def run(args, cfg, torch, dist, rank, local_rank, world, backend, device, n_dev,
                              " per epoch: the cost of a live 20 Hz caller of kfpos_step_*_dev"}
     secondary = None
     p48_line = None
-    if args.config == "c3" and not args.no_secondary and not dry and cfg["storage"] != capi.STORE_P48:
+    full_c3 = args.full and args.config == "c3" and not args.no_secondary and not dry
+    if full_c3 and cfg["storage"] != capi.STORE_P48:
         # configs[2] as BASELINE.json words it -- compact (6-byte) covariance storage -- on the same trace, same K epochs
         ep, kp, lp, _, bp = measure(E, "none", bank=make_bank(storage=capi.STORE_P48))
         bp.close()
@@ -436,7 +547,7 @@ def run(args, cfg, torch, dist, rank, local_rank, world, backend, device, n_dev,
                     "kernel": "k_step_imu9<p48,float,8,true>", "value": total * K / ep, "unit": "tag-steps/s",
                     "ms_per_step": ep * 1e3 / K, "kernel_us_per_launch": kp * 1e3 / lp, "launches": lp,
                     "roofline_frac": 544 * (T * K / lp) / (kp * 1e-3 / lp) / 1e9 / HBM_PEAK_GBS}
-    if args.config == "c3" and not args.no_secondary and not dry:
+    if full_c3:
         # the 6-state filter on the same ranging trace (kbench's toa6_65k): the kernel BASELINE's >= 40 % HBM target
         # is reachable for; f64 storage, so its errorEstimations are f64
         tr6 = {"ranges": trace["ranges"], "dts": trace["dts"], "traj": trace["traj"],
@@ -456,6 +567,12 @@ def run(args, cfg, torch, dist, rank, local_rank, world, backend, device, n_dev,
     # ---- the main measurement: R repeats of "W warm-up epochs, K timed epochs" on fresh banks; the line reports the
     # median repeat (by wall time) and the spread of all R ----
     R = max(1, args.repeats)
+    # Warm-up beyond the W epochs: the same run, rehearsed on throwaway banks until REHEARSAL_EPOCHS epochs have run.
+    # The first run in a process is 2-4 % slower than the next ones (measured at K = 20 and 500): the chip has not run
+    # this trace and the timing path yet. A count of epochs, not a time, so that every rank rehearses equally often.
+    if not dry:
+        for _ in range(-(-REHEARSAL_EPOCHS // (W + K))):
+            measure(E, args.gather)[4].close()
     runs = []
     for _ in range(R):
         elapsed, kernel_ms, launches, gathers, bank = measure(E, args.gather)
@@ -470,7 +587,10 @@ def run(args, cfg, torch, dist, rank, local_rank, world, backend, device, n_dev,
         truth = w.position(w.time_of(W + K - 1))
         track_rms = float(np.sqrt(((x[:, :3] - truth) ** 2).sum(1).mean()))
         finite = bool(np.isfinite(x).all() and np.isfinite(P).all())
-        traj_ok = bool(np.array_equal(trace["traj"][W + K - 1].cpu().numpy().T, x[:, :3]))
+        pose = trace["traj"][W + K - 1].cpu().numpy().T
+        traj_ok = bool(np.array_equal(pose, x[:, :3]))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, pose, x, P)
     bank.close()
     fence()
     for g in gathers_made.values():
@@ -543,7 +663,7 @@ def run(args, cfg, torch, dist, rank, local_rank, world, backend, device, n_dev,
             secondary = dict(secondary or {}, c3_p48=p48_line)
         if secondary is not None:
             out["secondary"] = secondary
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             cores = host_cores()  # all host cores, count stated
             # ~10 s of oracle time: the oracle does ~2.2e4 (9-state) / ~7e4 (6-state) tag-steps/s per core
             per_core = 2.2e4 if imu else 7e4

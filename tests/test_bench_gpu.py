@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import has_gpu
@@ -39,11 +40,11 @@ def test_plain_two_rank_command_on_one_card():
 
 
 def test_plain_single_gpu_command_reduced_size():
-    """the N = 1 line at a reduced batch (the full-size run is the driver's): every contract key, roofline and
+    """the --full N = 1 line at a reduced batch (the full-size run is the driver's): every contract key, roofline and
     cpu_baseline objects present, the GPU within 1e-6 m of the oracle on the sampled tags"""
     if not has_gpu():
         pytest.skip("no GPU")
-    d = _run(["--gpus", "1", "--steps", "10", "--warmup", "5", "--tags-per-gpu", "4096", "--repeats", "2"])
+    d = _run(["--gpus", "1", "--steps", "10", "--warmup", "5", "--tags-per-gpu", "4096", "--repeats", "2", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -60,7 +61,7 @@ def test_plain_single_gpu_command_reduced_size():
 def test_p48_as_the_headline_storage():
     if not has_gpu():
         pytest.skip("no GPU")
-    d = _run(["--gpus", "1", "--steps", "10", "--warmup", "5", "--tags-per-gpu", "4096", "--repeats", "1"],
+    d = _run(["--gpus", "1", "--steps", "10", "--warmup", "5", "--tags-per-gpu", "4096", "--repeats", "1", "--full"],
              KFPOS_BENCH_STORAGE="p48")
     assert "KFPOS_STORE_P48" in d["dtype"] and "p48" in d["roofline"]["kernel"] and d["rms_pos_err_vs_cpu_ref_m"] <= 1e-6
     assert "c3_p48" not in d.get("secondary", {})
@@ -87,3 +88,46 @@ def test_two_rank_command_with_the_c_abi_gather():
     assert cal and all(v["collective"]["ok"] and v["direct"]["ok"] for v in cal.values())
     if extra:
         assert c["rccl_version"] == FAKE_VERSION
+
+
+def test_plain_single_gpu_command_dumps_its_outputs(tmp_path):
+    """the plain line times one run of exactly K epochs; --dump-outputs writes the pose, state and covariance after
+    the last of them, the same in every run of the same command"""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    lines = [_run(["--gpus", "1", "--steps", "12", "--warmup", "3", "--tags-per-gpu", "4096", "--dump-outputs",
+                   str(tmp_path / d)]) for d in ("a", "b")]
+    d = lines[0]
+    assert d["steps"] == 12 and d["repeats"]["n"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["state_finite"] and d["trajectory_matches_state"]
+    assert not {"per_epoch_launch", "secondary", "cpu_baseline", "rms_pos_err_vs_cpu_ref_m"} & set(d)
+    out = {}
+    for name, shape in (("pose", (4096, 3)), ("state", (4096, 9)), ("covariance", (4096, 9, 9))):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.shape == shape and a.dtype == np.float64 and np.isfinite(a).all() and np.array_equal(a, b), name
+        out[name] = a
+    assert np.array_equal(out["pose"], out["state"][:, :3])
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["covariance.npy", "pose.npy", "state.npy"]
+
+
+def test_device_trace_generator_on_the_gpu():
+    """bench.trace_on_device on the GPU against the host's synth.Workload (dist.device_trace) at the headline's 65 536
+    tags: the device library's log / cos / sin may round differently from the host's in the last bit, which is
+    allowed to move a range by one millimetre or an f32 acceleration by one unit in the last place, rarely"""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    import torch
+    import bench
+    from roskfpos_amd.dist import device_trace
+    from roskfpos_amd.synth import Workload
+    w = Workload(65536, 8)
+    got = bench.trace_on_device(torch, w, 6, "cuda:0", True, np.float32)
+    want = device_trace(torch, w, 6, "cuda:0", True, np.float32)
+    dr = (got["ranges"].long() - want["ranges"].long()).abs()
+    assert int(dr.max()) <= 1 and int((dr != 0).sum()) <= 4, int((dr != 0).sum())
+    ga, wa = got["accel"].cpu().numpy(), want["accel"].cpu().numpy()
+    ulp = np.abs(ga.view(np.int32).astype(np.int64) - wa.view(np.int32).astype(np.int64))
+    assert ulp.max() <= 1 and (ulp != 0).sum() <= 4, int((ulp != 0).sum())
+    for k in ("err", "cov", "traj"):
+        assert torch.equal(got[k], want[k]), k
+    assert np.array_equal(got["dts"], want["dts"])

@@ -30,7 +30,7 @@ def _json_line(stdout: str):
 
 
 def test_plain_command_launches_its_own_ranks():
-    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "6", "--warmup", "2", "--dry-run",
+    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "6", "--warmup", "2", "--dry-run", "--full",
                           "--tags-per-gpu", "200", "--epochs-per-launch", "4"], capture_output=True, text=True,
                          env=_clean_env(), timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -91,3 +91,65 @@ def test_world_size_mismatch_is_refused():
     res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run"], capture_output=True, text=True, env=env,
                          timeout=120)
     assert res.returncode != 0 and "WORLD_SIZE=3" in res.stderr
+
+
+def test_plain_command_measures_only_the_headline():
+    """without --full: one run of exactly K timed epochs, and none of the extra measurements"""
+    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "6", "--warmup", "2", "--dry-run",
+                          "--tags-per-gpu", "200", "--epochs-per-launch", "4"], capture_output=True, text=True,
+                         env=_clean_env(), timeout=300)
+    assert res.returncode == 0, res.stderr[-2000:]
+    d = _json_line(res.stdout)
+    assert CONTRACT_KEYS <= set(d) and d["steps"] == 6 and d["repeats"]["n"] == 1
+    assert d["config"]["epochs_in_timed_launches"] == [4, 2]
+    assert not {"per_epoch_launch", "secondary", "cpu_baseline", "rms_pos_err_vs_cpu_ref_m"} & set(d)
+
+
+def test_dump_outputs_needs_a_real_run():
+    res = subprocess.run([sys.executable, BENCH, "--dry-run", "--dump-outputs", "out"], capture_output=True, text=True,
+                         env=_clean_env(), timeout=120)
+    assert res.returncode != 0 and "--dump-outputs" in res.stderr
+
+
+@pytest.mark.parametrize("imu,real", [(True, "float32"), (False, "float64")])
+def test_device_trace_generator_equals_the_host_one(monkeypatch, imu, real):
+    """bench.trace_on_device (the draws made on the trace's device) against dist.device_trace (synth.Workload on the
+    host), on CPU tensors: bit for bit, across generator passes, for a shard that does not start at tag 0"""
+    import numpy as np
+    import torch
+    import bench
+    from roskfpos_amd.dist import device_trace
+    from roskfpos_amd.synth import Workload
+    monkeypatch.setattr(bench, "TRACE_CHUNK", 3 * 8 * 500)  # three epochs per pass
+    w = Workload(500, 8, tag0=70001)
+    got = bench.trace_on_device(torch, w, 11, "cpu", imu, getattr(np, real))
+    want = device_trace(torch, w, 11, "cpu", imu, getattr(np, real))
+    assert set(got) == set(want)
+    for k, v in want.items():
+        if isinstance(v, np.ndarray):
+            assert np.array_equal(got[k], v), k
+        else:
+            assert got[k].dtype == v.dtype and torch.equal(got[k], v), k
+
+
+def test_dump_outputs_sample_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    T = 1000
+    pose, x, P = np.random.default_rng(1).random((T, 3)), np.random.default_rng(2).random((T, 9)), np.zeros((T, 9, 9))
+    bench.dump_outputs(str(tmp_path / "all"), pose, x, P)
+    assert np.array_equal(np.load(tmp_path / "all" / "state.npy"), x)
+    assert not (tmp_path / "all" / "sampled_tags.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200 * 93 * 8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), pose, x, P)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["covariance.npy", "pose.npy", "sampled_tags.npy", "state.npy"]
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= bench.DUMP_LIMIT_BYTES
+    stored = np.load(tmp_path / "a" / "sampled_tags.npy")
+    keep = stored.astype(int)
+    assert np.array_equal(stored, keep) and len(keep) > 150 and np.all(np.diff(keep) > 0) and keep[-1] < T
+    assert np.array_equal(np.load(tmp_path / "a" / "pose.npy"), pose[keep])
+    for f in files:  # a fixed sample: the same tags every time
+        a = np.load(tmp_path / "a" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "b" / f))

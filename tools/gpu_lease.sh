@@ -4,7 +4,7 @@
 #
 #   tests                      the GPU test-suite
 #   one PYTEST_ARGS...         part of it (e.g. tests/test_comm_world_gpu.py -x)
-#   final                      end-of-round validation: suite, smoke(), the driver's bench command, the default bench, the
+#   final                      end-of-round validation: suite, smoke(), the driver's bench command, the default bench --full, the
 #                              plain two-rank command (bench.py spawns its ranks; gloo when they share a card), c4
 #   kbench CONFIGS [STEPS]     tools/kbench.py step-kernel timings (CONFIGS: comma list, e.g. c2,c3,c5)
 #   ab CONFIGS SPEC...         same-box timing of several library builds, three alternating rounds.
@@ -32,10 +32,10 @@ final)
   timeout -k 10 1000 python3 -m pytest tests -m gpu -x -q > $OUT/tests.log 2>&1; echo rc=$? >> $OUT/tests.log; tail -3 $OUT/tests.log
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 | tee $OUT/smoke.log
   timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.log 2>$OUT/bench_driver.err; cut -c1-300 $OUT/bench_driver.log
-  timeout -k 10 400 python3 bench.py > $OUT/bench_default.log 2>$OUT/bench_default.err; cut -c1-200 $OUT/bench_default.log
-  timeout -k 10 300 python3 bench.py --gpus 2 --steps 20 --warmup 5 > $OUT/bench_c3_2ranks.log 2>$OUT/bench_c3_2ranks.err; cut -c1-200 $OUT/bench_c3_2ranks.log
-  timeout -k 10 300 python3 bench.py --gpus 2 --config c4 --total-tags 262144 --steps 20 --warmup 5 --gather epoch > $OUT/bench_c4_2ranks.log 2>$OUT/bench_c4_2ranks.err; cut -c1-200 $OUT/bench_c4_2ranks.log
-  timeout -k 10 300 python3 bench.py --config c4 --steps 20 --warmup 5 > $OUT/bench_c4_n1.log 2>$OUT/bench_c4_n1.err; cut -c1-200 $OUT/bench_c4_n1.log ;;
+  timeout -k 10 400 python3 bench.py --full > $OUT/bench_default.log 2>$OUT/bench_default.err; cut -c1-200 $OUT/bench_default.log
+  timeout -k 10 300 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 > $OUT/bench_c3_2ranks.log 2>$OUT/bench_c3_2ranks.err; cut -c1-200 $OUT/bench_c3_2ranks.log
+  timeout -k 10 300 python3 bench.py --full --gpus 2 --config c4 --total-tags 262144 --steps 20 --warmup 5 --gather epoch > $OUT/bench_c4_2ranks.log 2>$OUT/bench_c4_2ranks.err; cut -c1-200 $OUT/bench_c4_2ranks.log
+  timeout -k 10 300 python3 bench.py --full --config c4 --steps 20 --warmup 5 > $OUT/bench_c4_n1.log 2>$OUT/bench_c4_n1.err; cut -c1-200 $OUT/bench_c4_n1.log ;;
 kbench)
   kbench $1 $2 2>/dev/null | grep '^{' | tee $OUT/kbench.jsonl | cut -c1-170 ;;
 ab)
@@ -80,16 +80,16 @@ PY
 profile)
   cd /tmp && export TMPDIR=/tmp
   rocprofv3 --kernel-trace --stats -d $OUT/stats_driver --output-format csv -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_profiled.log 2>&1
-  rocprofv3 --kernel-trace --stats -d $OUT/stats_default --output-format csv -- python3 $R/bench.py --no-cpu-baseline > $OUT/bench_default_profiled.log 2>&1
+  rocprofv3 --kernel-trace --stats -d $OUT/stats_default --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/bench_default_profiled.log 2>&1
   for E in 25 5; do
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch_$E --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-per-epoch --repeats 1 --epochs-per-launch $E --steps 100 --warmup 25 > $OUT/fetch_$E.log 2>&1
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write_$E --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-per-epoch --repeats 1 --epochs-per-launch $E --steps 100 --warmup 25 > $OUT/write_$E.log 2>&1
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch_$E --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-per-epoch --repeats 1 --epochs-per-launch $E --steps 100 --warmup 25 > $OUT/fetch_$E.log 2>&1
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write_$E --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-per-epoch --repeats 1 --epochs-per-launch $E --steps 100 --warmup 25 > $OUT/write_$E.log 2>&1
   done
   cd $R
   KEY=$(python3 -c "import bench; print(bench.CONFIGS['c3']['kernel'])")
   # the headline kernel as rocprofv3 spells it (the same process also runs the P48 instantiation: secondary.c3_p48)
   MATCH=$(python3 -c "import bench; k=bench.CONFIGS['c3']['kernel']; print('k_step_imu9<(anonymous namespace)::p48' if 'p48' in k else k.split(',')[0] + ', ' + k.split(',')[1] + ',')")
-  python3 tools/traffic_summary.py --match "$MATCH" --key "$KEY" --tags 65536 --run 25 $OUT/fetch_25 $OUT/write_25 --run 5 $OUT/fetch_5 $OUT/write_5 --note "bench.py --no-cpu-baseline --no-per-epoch --repeats 1 --steps 100 --warmup 25 at 25 and 5 epochs per launch ($TAG)" --merge $OUT/traffic_latest.json > /dev/null
+  python3 tools/traffic_summary.py --match "$MATCH" --key "$KEY" --tags 65536 --run 25 $OUT/fetch_25 $OUT/write_25 --run 5 $OUT/fetch_5 $OUT/write_5 --note "bench.py --full --no-cpu-baseline --no-per-epoch --repeats 1 --steps 100 --warmup 25 at 25 and 5 epochs per launch ($TAG)" --merge $OUT/traffic_latest.json > /dev/null
   python3 tools/traffic_summary.py --match k_step_toa6 --key "k_step_toa6<true,double,double,8,0>" --tags 65536 --run 25 $OUT/fetch_25 $OUT/write_25 --run 5 $OUT/fetch_5 $OUT/write_5 --note "the secondary 6-state line of the same runs ($TAG)" --merge $OUT/traffic_latest.json > /dev/null
   head -40 $OUT/traffic_latest.json
   for d in stats_driver stats_default; do f=$(find $OUT/$d -name "*kernel_stats.csv" | head -1); cp $f $OUT/${d}_kernel_stats.csv; head -6 $f | cut -c1-160; done
