@@ -248,6 +248,58 @@ int kfpos_latch_dim(const kfpos_handle *h);
 int kfpos_get_latch(kfpos_handle *h, double *latch);
 int kfpos_set_latch(kfpos_handle *h, const double *latch);
 
+/* ---- per-tag lifecycle: reset, read and write CHOSEN tags, on the device ----
+ * The accessors above move the whole bank. These three work on a list: `rows` is a host array of n row indices into
+ * the bank, and what crosses the bus is that list plus the listed tags' values -- the cost follows n, not n_tags. They
+ * make a row of the bank reusable: a tag that left is reset and the row serves another (kfpos_ingest.h:
+ * releaseRows / bindRows), a tag moves to another handle by kfpos_get_tags there + kfpos_set_tags here.
+ * KFPOS_VERSION is unchanged by them: detect them by symbol (dlsym / hasattr), not by version number.
+ *
+ * Common rules:
+ *   validation  happens before any write: h == NULL, rows == NULL with n > 0, n < 0, a row outside [0, n_tags) ->
+ *               KFPOS_ERR_ARG; a row listed twice in kfpos_reset_tags / kfpos_set_tags -> KFPOS_ERR_ARG (kfpos_get_tags
+ *               may repeat rows); height != NULL on a handle that is not KFPOS_MODEL_PLANAR -> KFPOS_ERR_MODEL.
+ *               kfpos_last_error() names the first offending entry of the list, whichever of these rules it breaks.
+ *               After an error nothing has been written. This host-side check IS the bounds check: the kernels never
+ *               see an index that was not checked.
+ *   n == 0      KFPOS_OK, nothing happens.
+ *   ordering    like the other synchronous calls: first everything the streaming slots have in flight completes, and
+ *               the call returns when its own work is complete. Runs on the handle's device, leaves the caller's
+ *               current device as it was.
+ *   tags not listed are not written at all.
+ *
+ * kfpos_reset_tags: the listed tags go back to the state kfpos_create (+ kfpos_set_planar) leaves a tag in: flags 0
+ * (getPose() == false, KFPOS_ST_NOT_STARTED), covariance all-zero in the handle's storage encoding, velocity 0, latched
+ * samples cleared. From then on the tag cannot be told from the same row of a handle just created with the same
+ * configuration: every later status word, state and covariance is bit-identical.
+ *   use_init_pos = 1: position (and, KFPOS_MODEL_ML, the solver's seed) = init_xyz[i] (n x 3 doubles, row-major), or
+ *                     kfpos_config.init_pos when init_xyz is NULL.
+ *   use_init_pos = 0: position NaN, i.e. the tag's next ranging epoch is its ML initialisation; init_xyz must be NULL
+ *                     (KFPOS_ERR_STATE otherwise, as kfpos_set_init_positions answers).
+ *   KFPOS_MODEL_PLANAR: height = kfpos_planar_config.fixed_height whatever init_xyz's z says (kfpos_set_init_positions
+ *                     does the same), angle = init_angle, angular speed 0, as kfpos_set_planar wrote them.
+ * Unlike kfpos_set_tags a reset does not count as a step: a handle that has never stepped is still "fresh" after it,
+ * as its rows are, so kfpos_set_init_positions / kfpos_set_planar remain legal there -- and rewrite every tag, the
+ * reset ones included.
+ * Which kernel a planar handle runs for its ranging epochs (with or without latched samples) is a property of the
+ * handle, not of a tag: a reset does not change it. */
+int kfpos_reset_tags(kfpos_handle *h, const int32_t *rows, int32_t n, const double *init_xyz);
+
+/* kfpos_get_state + kfpos_get_latch + kfpos_get_height for the listed tags only: entry i of every output is, bit for
+ * bit, row rows[i] of what those calls return (the 9-state x carries a = 0, the planar x is [x y vx vy 0 0 theta omega],
+ * P is expanded from the packed or full layout, F32 / P48 entries are decoded). x n x dim, P n x dim x dim, flags n,
+ * latch n x kfpos_latch_dim(), height n (planar). Any output may be NULL. */
+int kfpos_get_tags(kfpos_handle *h, const int32_t *rows, int32_t n,
+                   double *x, double *P, uint32_t *flags, double *latch, double *height);
+/* The inverse: stores what kfpos_set_state / kfpos_set_latch / kfpos_set_height would store for those rows (symmetric
+ * layouts read the upper triangle j >= i of P, P48 entries are rounded and encoded as the kernels do, the 9-state latch
+ * is kept as acceleration + lower triangle of its covariance in kfpos_real). Any input may be NULL = leave that part
+ * of the listed tags as it is. Like kfpos_set_state it counts as a step (kfpos_set_init_positions / kfpos_set_planar
+ * are refused afterwards), and restored planar latch bits switch the handle's ranging epochs to the instantiation
+ * that honours them. */
+int kfpos_set_tags(kfpos_handle *h, const int32_t *rows, int32_t n,
+                   const double *x, const double *P, const uint32_t *flags, const double *latch, const double *height);
+
 /* ---- streaming host API: epochs pipelined through kfpos_slot_count() slots of pinned host memory ----
  * For a node that feeds epoch after epoch from the CPU (PosGenerator's table flushes, Posgenerator.cpp:155-198, batched
  * over many tags): the synchronous calls above copy pageable arrays, turn their layout on the device and wait; here

@@ -34,6 +34,7 @@ EXPORTS = [
     "kfpos_strerror", "kfpos_version", "kfpos_timing_begin", "kfpos_timing_end",
     "kfpos_set_planar", "kfpos_step_sensor", "kfpos_step_sensor_dev", "kfpos_get_height", "kfpos_set_height",
     "kfpos_latch_dim", "kfpos_get_latch", "kfpos_set_latch",
+    "kfpos_reset_tags", "kfpos_get_tags", "kfpos_set_tags",
     "kfpos_slot_count", "kfpos_slot_acquire", "kfpos_slot_submit", "kfpos_slot_wait",
     "kfpos_shard_range", "kfpos_comm_unique_id", "kfpos_comm_create", "kfpos_comm_create_all", "kfpos_comm_destroy",
     "kfpos_comm_world", "kfpos_comm_rank", "kfpos_comm_set_total", "kfpos_allgather_poses",
@@ -129,6 +130,9 @@ def load():
     sig("kfpos_latch_dim", [vp])
     sig("kfpos_get_latch", [vp, vp])
     sig("kfpos_set_latch", [vp, vp])
+    sig("kfpos_reset_tags", [vp, vp, i32, vp])
+    sig("kfpos_get_tags", [vp, vp, i32, vp, vp, vp, vp, vp])
+    sig("kfpos_set_tags", [vp, vp, i32, vp, vp, vp, vp, vp])
     sig("kfpos_slot_count", [vp])
     sig("kfpos_slot_acquire", [vp, i32, C.POINTER(_EpochSlot)])
     sig("kfpos_slot_submit", [vp, i32, i32, f64])
@@ -341,6 +345,56 @@ class KfposBank:
         a = np.ascontiguousarray(latch, dtype=np.float64)
         assert a.shape == (self.T, self.lib.kfpos_latch_dim(self._h))
         self._chk(self.lib.kfpos_set_latch(self._h, a.ctypes.data if a.size else None))
+
+    # ---- per-tag lifecycle: chosen rows only, on the device (cost follows len(rows), not T) ----
+    @staticmethod
+    def _rows(rows):
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        assert r.ndim == 1
+        return r
+
+    def reset_tags(self, rows, init_pos=None):
+        """The listed tags go back to what a fresh bank holds: not started, P = 0, latches cleared; position =
+        init_pos ((3,) or (len(rows), 3)), the bank's init_pos when None, NaN on a bank that starts by ML."""
+        r = self._rows(rows)
+        ip = None
+        if init_pos is not None:
+            ip = np.ascontiguousarray(np.broadcast_to(np.asarray(init_pos, dtype=np.float64), (r.size, 3)))
+        self._chk(self.lib.kfpos_reset_tags(self._h, r.ctypes.data, r.size, None if ip is None else ip.ctypes.data))
+
+    def get_tags(self, rows):
+        """Rows `rows` of get_state() / get_latch() / get_height(): (x, P, flags, latch, height or None)."""
+        r = self._rows(rows)
+        m = r.size
+        x, P = np.zeros((m, self.n)), np.zeros((m, self.n, self.n))
+        fl = np.zeros(m, dtype=np.uint32)
+        latch = np.zeros((m, self.lib.kfpos_latch_dim(self._h)))
+        z = np.zeros(m) if self.model == MODEL_PLANAR else None
+        self._chk(self.lib.kfpos_get_tags(self._h, r.ctypes.data, m, x.ctypes.data, P.ctypes.data, fl.ctypes.data,
+                                          latch.ctypes.data if latch.shape[1] else None,
+                                          None if z is None else z.ctypes.data))
+        return x, P, fl, latch, z
+
+    def set_tags(self, rows, x=None, P=None, flags=None, latch=None, height=None):
+        """The inverse of get_tags; a part left None stays as it is in the listed tags."""
+        r = self._rows(rows)
+        m = r.size
+
+        def arr(v, shape, dtype=np.float64):
+            if v is None:
+                return None
+            a = np.ascontiguousarray(v, dtype=dtype)
+            assert a.shape == shape, (a.shape, shape)
+            return a
+
+        x, P = arr(x, (m, self.n)), arr(P, (m, self.n, self.n))
+        fl = arr(flags, (m,), np.uint32)
+        L = self.lib.kfpos_latch_dim(self._h)
+        latch = arr(latch, (m, L))
+        z = arr(height, (m,))
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        self._chk(self.lib.kfpos_set_tags(self._h, r.ctypes.data, m, ptr(x), ptr(P), ptr(fl),
+                                          None if L == 0 else ptr(latch), ptr(z)))
 
     # ---- streaming host API: epochs assembled in place in pinned, component-major slots ----
     def slot_acquire(self, slot):

@@ -3,12 +3,14 @@
  * host-buffer API, streaming slots, device-buffer API) and the C ABI of include/kfpos.h. The kernels live in
  * kfpos_k_*.hip (kfpos_kernels.h says which is where); the RCCL pose gather in kfpos_comm.hip.
  */
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kfpos_kernels.h"
@@ -431,6 +433,7 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
         }
         std::memset(hp, 0, off);
         h->sm_h = (unsigned char *)hp;
+        h->sm_bytes = off;
         h->sm_d = (unsigned char *)dp;
     }
     const bool parks = cfg->model == KFPOS_MODEL_PLANAR || (cfg->model == KFPOS_MODEL_TOA && h->full);
@@ -1311,6 +1314,302 @@ int kfpos_set_latch(kfpos_handle *h, const double *latch) {
     }
     HIPCHK(hipMemcpy(h->d_imu_acc, a.data(), a.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_imu_cov, c.data(), c.size(), hipMemcpyHostToDevice));
+    return KFPOS_OK;
+}
+
+/* ---- per-tag lifecycle: kfpos_reset_tags / kfpos_get_tags / kfpos_set_tags (kernels: kfpos_k_tags.hip) ---- */
+static int latch_dim(const kfpos_handle *h) {
+    return h->cfg.model == KFPOS_MODEL_TOA_IMU ? 12 : (h->cfg.model == KFPOS_MODEL_PLANAR ? LATCH_ROWS : (h->cfg.model == KFPOS_MODEL_ML ? 3 : 0));
+}
+
+/* The bounds check of the per-tag kernels: every row inside [0, n_tags), and (unique) no row twice. Nothing has been
+ * written when this fails; the text names the first offending entry of the list, whichever rule it breaks. */
+static int tags_check(const kfpos_handle *h, const char *who, const int32_t *rows, int32_t n, bool unique) {
+    if (n < 0 || (n > 0 && !rows)) {
+        g_err = std::string(who) + (n < 0 ? ": n < 0" : ": rows == NULL");
+        return KFPOS_ERR_ARG;
+    }
+    int32_t bad = 0; /* the first entry out of range, n if none */
+    while (bad < n && rows[bad] >= 0 && rows[bad] < h->cfg.n_tags) ++bad;
+    int32_t twice = bad; /* the first entry in front of it that repeats an earlier one */
+    if (unique && bad > 1) {
+        /* one sort of (row, position) keys: inside a run of equal rows positions ascend, so the second key of a run is
+         * that row's first repeat */
+        std::vector<uint64_t> key((size_t)bad);
+        for (int32_t i = 0; i < bad; ++i) key[i] = ((uint64_t)(uint32_t)rows[i] << 32) | (uint32_t)i;
+        std::sort(key.begin(), key.end());
+        for (int32_t k = 1; k < bad; ++k) {
+            const bool repeats = (key[k] >> 32) == (key[k - 1] >> 32);
+            const bool second_of_run = repeats && (k == 1 || (key[k - 2] >> 32) != (key[k] >> 32));
+            const int32_t at = (int32_t)(uint32_t)key[k];
+            if (second_of_run && at < twice) twice = at;
+        }
+    }
+    if (twice < bad) {
+        g_err = std::string(who) + ": rows[" + std::to_string(twice) + "] = row " + std::to_string(rows[twice]) +
+                " is listed twice";
+        return KFPOS_ERR_ARG;
+    }
+    if (bad < n) {
+        g_err = std::string(who) + ": rows[" + std::to_string(bad) + "] = row " + std::to_string(rows[bad]) +
+                " is outside [0, " + std::to_string(h->cfg.n_tags) + ")";
+        return KFPOS_ERR_ARG;
+    }
+    return KFPOS_OK;
+}
+
+/* the part of the kernel arguments every per-tag call shares */
+static void tag_args(const kfpos_handle *h, kfpos_k::TagArgs &a) {
+    std::memset(&a, 0, sizeof(a));
+    a.T = h->cfg.n_tags;
+    a.psz = h->psz;
+    a.buf[kfpos_k::TB_POS] = h->d_pos;
+    a.buf[kfpos_k::TB_VEL] = h->d_vel;
+    a.buf[kfpos_k::TB_P] = h->d_P;
+    a.buf[kfpos_k::TB_IMU_ACC] = h->d_imu_acc;
+    a.buf[kfpos_k::TB_IMU_COV] = h->d_imu_cov;
+    a.buf[kfpos_k::TB_LATCH] = h->d_latch;
+    a.flags = h->d_flags;
+}
+
+/* The record of one tag as kfpos_get_state / kfpos_get_latch / kfpos_get_height lay it out -- x (n) | P (n x n) |
+ * latch | height -- component by component: where it is stored, and whether kfpos_set_state / kfpos_set_latch /
+ * kfpos_set_height store THROUGH it (the mirror half of a packed covariance is read, never written). */
+static void tag_record(const kfpos_handle *h, kfpos_k::TagArgs &a) {
+    using namespace kfpos_k;
+    const int n = h->n, L = latch_dim(h);
+    int c = 0;
+    auto put = [&](int kind, int buf, int row, int stored) {
+        a.comp[c++] = TagComp{(uint8_t)kind, (uint8_t)buf, (uint8_t)row, (uint8_t)stored};
+    };
+    a.cbase[0] = c;
+    for (int k = 0; k < n; ++k) {
+        if (n == 8) { /* [x y vx vy 0 0 theta omega]; the height row of d_pos is its own section */
+            static const int src[8] = {0, 1, 0, 1, -1, -1, 2, 3};
+            if (src[k] < 0) put(TC_NONE, 0, 0, 0);
+            else put(TC_F64, (k < 2) ? TB_POS : TB_VEL, src[k], 1);
+        } else if (k < 3) put(TC_F64, TB_POS, k, 1);
+        else if (n == 9 && k < 6) put(TC_F64, TB_VEL, k - 3, 1);
+        else put(TC_NONE, 0, 0, 0); /* 6-state: the velocity is not a stored member; 9-state: a = 0 */
+    }
+    a.cbase[1] = c;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) put(TC_COV, TB_P, pidx(h, i, j), (h->full || j >= i) ? 1 : 0);
+    a.cbase[2] = c;
+    if (L == LATCH_ROWS)
+        for (int k = 0; k < L; ++k) put(TC_F64, TB_LATCH, k, 1);
+    else if (L == 3) /* ALGORITHM_ML: _previousEstimation, the seed of every solve */
+        for (int k = 0; k < L; ++k) put(TC_F64, TB_VEL, k, 1);
+    else if (L == 12) { /* acceleration [3] + the lower triangle {00,10,11,20,21,22} of its covariance, kfpos_real */
+        static const int tri[3][3] = {{0, 1, 3}, {1, 2, 4}, {3, 4, 5}};
+        for (int k = 0; k < 3; ++k) put(TC_REAL, TB_IMU_ACC, k, 1);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) put(TC_REAL, TB_IMU_COV, tri[i][j], i >= j ? 1 : 0);
+    }
+    a.cbase[3] = c;
+    if (n == 8) put(TC_F64, TB_POS, 2, 1);
+}
+
+/* The stored rows of one tag and what kfpos_create (+ kfpos_set_planar) left in them: TagComp::aux = 0 zero, 1..3 the
+ * start position, 4 / 5 the planar height / angle. */
+static void tag_fresh(const kfpos_handle *h, kfpos_k::TagArgs &a) {
+    using namespace kfpos_k;
+    const int n = h->n;
+    int c = 0;
+    auto put = [&](int kind, int buf, int row, int what) {
+        a.comp[c++] = TagComp{(uint8_t)kind, (uint8_t)buf, (uint8_t)row, (uint8_t)what};
+    };
+    for (int k = 0; k < 3; ++k) put(TC_F64, TB_POS, k, (n == 8 && k == 2) ? 4 : 1 + k);
+    if (n == 3)
+        for (int k = 0; k < 3; ++k) put(TC_F64, TB_VEL, k, 1 + k); /* the solver's seed */
+    if (n == 8)
+        for (int k = 0; k < 4; ++k) put(TC_F64, TB_VEL, k, k == 2 ? 5 : 0); /* vx vy theta omega */
+    if (n == 9)
+        for (int k = 0; k < 3; ++k) put(TC_F64, TB_VEL, k, 0);
+    for (int k = 0; k < h->psz; ++k) put(TC_COV, TB_P, k, 0);
+    if (n == 9) {
+        for (int k = 0; k < 3; ++k) put(TC_REAL, TB_IMU_ACC, k, 0);
+        for (int k = 0; k < 6; ++k) put(TC_REAL, TB_IMU_COV, k, 0);
+    }
+    if (n == 8)
+        for (int k = 0; k < LATCH_ROWS; ++k) put(TC_F64, TB_LATCH, k, 0);
+    a.n_comp = c;
+}
+
+/* Staging of the per-tag calls: the small bank's mapped block (the kernel reads and writes host memory in place), or
+ * one region of the device staging area filled and emptied with plain copies. Sized for n records of `rec` bytes, at most
+ * TAGS_STAGE_MAX: longer lists go through it in chunks of `chunk` (>= 1) records. */
+struct TagStage {
+    unsigned char *dev = nullptr, *host = nullptr; /* host != null: mapped */
+    size_t chunk = 0; /* records it holds */
+};
+static constexpr size_t TAGS_STAGE_MAX = (size_t)16 << 20;
+static int tag_stage(kfpos_handle *h, size_t rec, size_t n, TagStage &st) {
+    size_t cap = h->sm_bytes;
+    if (h->sm_h) {
+        st.dev = h->sm_d;
+        st.host = h->sm_h;
+    } else {
+        stage_reset(h);
+        cap = rec * n < TAGS_STAGE_MAX ? rec * n : TAGS_STAGE_MAX;
+        void *p = nullptr;
+        const int rc = stage_region(h, cap, &p);
+        if (rc) return rc;
+        st.dev = (unsigned char *)p;
+    }
+    st.chunk = cap / rec;
+    if (st.chunk == 0) { /* (a loop over chunks of nothing would never end) */
+        g_err = "per-tag staging holds less than one tag";
+        return KFPOS_ERR_STATE;
+    }
+    return KFPOS_OK;
+}
+static hipError_t tag_up(const TagStage &st, size_t off, const void *src, size_t bytes) {
+    if (st.host) {
+        std::memcpy(st.host + off, src, bytes);
+        return hipSuccess;
+    }
+    return hipMemcpy(st.dev + off, src, bytes, hipMemcpyHostToDevice);
+}
+static hipError_t tag_down(const TagStage &st, void *dst, size_t off, size_t bytes) {
+    if (st.host) {
+        std::memcpy(dst, st.host + off, bytes);
+        return hipSuccess;
+    }
+    return hipMemcpy(dst, st.dev + off, bytes, hipMemcpyDeviceToHost);
+}
+
+/* get (STORE = false) / set (STORE = true) of the listed tags; the host pointers of absent parts are null, and a
+ * store only ever reads the caller's arrays */
+extern "C++" template <bool STORE>
+static int tags_transfer(kfpos_handle *h, const int32_t *rows, int32_t n,
+                         std::conditional_t<STORE, const double, double> *x,
+                         std::conditional_t<STORE, const double, double> *P,
+                         std::conditional_t<STORE, const uint32_t, uint32_t> *flags,
+                         std::conditional_t<STORE, const double, double> *latch,
+                         std::conditional_t<STORE, const double, double> *height) {
+    constexpr bool store = STORE;
+    kfpos_k::TagArgs a;
+    tag_args(h, a);
+    tag_record(h, a);
+    std::conditional_t<STORE, const double, double> *part[kfpos_k::TAG_SECTIONS] = {x, P, latch_dim(h) ? latch : nullptr, height};
+    const int width[kfpos_k::TAG_SECTIONS] = {h->n, h->n * h->n, latch_dim(h), 1};
+    size_t wsum = 0;
+    for (int s = 0; s < kfpos_k::TAG_SECTIONS; ++s) wsum += (size_t)(a.w[s] = part[s] ? width[s] : 0);
+    if (wsum == 0 && !flags) return KFPOS_OK;
+    /* per listed tag: its values (doubles), its flags word, its row index */
+    const size_t rec = wsum * sizeof(double) + sizeof(uint32_t) + sizeof(int32_t);
+    TagStage st;
+    const int rc = tag_stage(h, rec, (size_t)n, st);
+    if (rc) return rc;
+    const size_t chunk = st.chunk;
+    for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
+        const size_t m = (size_t)n - c0 < chunk ? (size_t)n - c0 : chunk;
+        const size_t off_fl = m * wsum * sizeof(double), off_rows = off_fl + m * sizeof(uint32_t);
+        HIPCHK(tag_up(st, off_rows, rows + c0, m * sizeof(int32_t)));
+        if constexpr (store) {
+            size_t off = 0;
+            for (int s = 0; s < kfpos_k::TAG_SECTIONS; ++s) {
+                if (!a.w[s]) continue;
+                HIPCHK(tag_up(st, off, part[s] + c0 * width[s], m * width[s] * sizeof(double)));
+                off += m * width[s] * sizeof(double);
+            }
+            if (flags) HIPCHK(tag_up(st, off_fl, flags + c0, m * sizeof(uint32_t)));
+        }
+        a.n = (int)m;
+        a.val = (double *)st.dev;
+        a.fl = flags ? (uint32_t *)(st.dev + off_fl) : nullptr;
+        a.rows = (const int32_t *)(st.dev + off_rows);
+        kfpos_k::launch_tags(store ? kfpos_k::TAGS_SCATTER : kfpos_k::TAGS_GATHER, h->cfg.storage, nullptr, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(nullptr)); /* the staging is free again; a mapped block's results are visible */
+        if constexpr (!store) {
+            size_t off = 0;
+            for (int s = 0; s < kfpos_k::TAG_SECTIONS; ++s) {
+                if (!a.w[s]) continue;
+                HIPCHK(tag_down(st, part[s] + c0 * width[s], off, m * width[s] * sizeof(double)));
+                off += m * width[s] * sizeof(double);
+            }
+            if (flags) HIPCHK(tag_down(st, flags + c0, off_fl, m * sizeof(uint32_t)));
+        }
+    }
+    return KFPOS_OK;
+}
+
+int kfpos_get_tags(kfpos_handle *h, const int32_t *rows, int32_t n, double *x, double *P, uint32_t *flags,
+                   double *latch, double *height) {
+    g_err.clear();
+    if (!h) return KFPOS_ERR_ARG;
+    int rc = tags_check(h, "kfpos_get_tags", rows, n, false);
+    if (rc) return rc;
+    if (height && h->cfg.model != KFPOS_MODEL_PLANAR) {
+        g_err = "kfpos_get_tags: height belongs to KFPOS_MODEL_PLANAR";
+        return KFPOS_ERR_MODEL;
+    }
+    if (n == 0) return KFPOS_OK;
+    DevScope dev_(h->cfg.device);
+    if ((rc = drain_slots(h))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    return tags_transfer<false>(h, rows, n, x, P, flags, latch, height);
+}
+
+int kfpos_set_tags(kfpos_handle *h, const int32_t *rows, int32_t n, const double *x, const double *P,
+                   const uint32_t *flags, const double *latch, const double *height) {
+    g_err.clear();
+    if (!h) return KFPOS_ERR_ARG;
+    int rc = tags_check(h, "kfpos_set_tags", rows, n, true);
+    if (rc) return rc;
+    if (height && h->cfg.model != KFPOS_MODEL_PLANAR) {
+        g_err = "kfpos_set_tags: height belongs to KFPOS_MODEL_PLANAR";
+        return KFPOS_ERR_MODEL;
+    }
+    if (n == 0) return KFPOS_OK;
+    DevScope dev_(h->cfg.device);
+    if ((rc = drain_slots(h))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if ((rc = tags_transfer<true>(h, rows, n, x, P, flags, latch, height))) return rc;
+    if (flags && h->n == 8) /* restored latch bits: ranging epochs must run the instantiation that honours them */
+        for (int32_t i = 0; i < n; ++i) h->planar_sensors = h->planar_sensors || ((flags[i] >> PLANAR_HAS_SHIFT) != 0);
+    h->stepped = true;
+    return KFPOS_OK;
+}
+
+int kfpos_reset_tags(kfpos_handle *h, const int32_t *rows, int32_t n, const double *init_xyz) {
+    g_err.clear();
+    if (!h) return KFPOS_ERR_ARG;
+    int rc = tags_check(h, "kfpos_reset_tags", rows, n, true);
+    if (rc) return rc;
+    if (init_xyz && !h->cfg.use_init_pos) {
+        g_err = "kfpos_reset_tags: init_xyz on a handle without a fixed start (use_init_pos = 0): the tag's next epoch is its ML initialisation";
+        return KFPOS_ERR_STATE;
+    }
+    if (n == 0) return KFPOS_OK;
+    DevScope dev_(h->cfg.device);
+    if ((rc = drain_slots(h))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    kfpos_k::TagArgs a;
+    tag_args(h, a);
+    tag_fresh(h, a);
+    for (int k = 0; k < 3; ++k) a.cst[k] = h->cfg.use_init_pos ? h->cfg.init_pos[k] : NAN;
+    a.cst[3] = h->planar.fixed_height; /* mUWBtagZ / mAngle as kfpos_set_planar wrote them (0 / 0 if it never ran) */
+    a.cst[4] = h->planar.init_angle;
+    /* per listed tag: its start position (if given), its row index */
+    const size_t rec = (init_xyz ? 3 * sizeof(double) : 0) + sizeof(int32_t);
+    TagStage st;
+    if ((rc = tag_stage(h, rec, (size_t)n, st))) return rc;
+    const size_t chunk = st.chunk;
+    for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
+        const size_t m = (size_t)n - c0 < chunk ? (size_t)n - c0 : chunk;
+        const size_t off_rows = init_xyz ? m * 3 * sizeof(double) : 0;
+        HIPCHK(tag_up(st, off_rows, rows + c0, m * sizeof(int32_t)));
+        if (init_xyz) HIPCHK(tag_up(st, 0, init_xyz + c0 * 3, m * 3 * sizeof(double)));
+        a.n = (int)m;
+        a.init = init_xyz ? (const double *)st.dev : nullptr;
+        a.rows = (const int32_t *)(st.dev + off_rows);
+        kfpos_k::launch_tags(kfpos_k::TAGS_RESET, h->cfg.storage, nullptr, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(nullptr));
+    }
     return KFPOS_OK;
 }
 

@@ -62,21 +62,24 @@ struct RangingMsg {
     int seq;
 };
 
-/* int -> int, open addressing, never erased from: one probe for almost every lookup */
+/* int -> int, open addressing with linear probing: one probe for almost every lookup. erase() closes the gap it leaves
+ * (backward-shift deletion: every entry of the cluster behind it moves up as far as its home slot allows), so the table
+ * holds no tombstones and lookups stay as short after any number of erase / insert as right after build(). */
 class FlatIdMap {
 public:
     void build(const std::vector<int> &ids) {
+        reserve(ids.size());
+        for (size_t i = 0; i < ids.size(); ++i) insert(ids[i], (int)i); /* a repeated id keeps its last position, like std::map::operator[] did */
+    }
+    /* an empty table for up to n ids (load factor <= 1/2) */
+    void reserve(size_t n) {
         size_t cap = 16;
-        while (cap < 2 * ids.size() + 2) cap <<= 1;
+        while (cap < 2 * n + 2) cap <<= 1;
         mask_ = cap - 1;
         key_.assign(cap, empty());
         val_.assign(cap, -1);
-        for (size_t i = 0; i < ids.size(); ++i) {
-            size_t p = hash(ids[i]);
-            while (key_[p] != empty() && key_[p] != ids[i]) p = (p + 1) & mask_;
-            key_[p] = ids[i];
-            val_[p] = (int)i; /* a repeated id keeps its last position, like std::map::operator[] did */
-        }
+        size_ = 0;
+        limit_ = n;
     }
     int find(int id) const {
         size_t p = hash(id);
@@ -86,13 +89,52 @@ public:
         }
         return -1;
     }
+    /* id -> value; an id already present gets the new value. At most the reserve()d number of ids. */
+    void insert(int id, int value) {
+        size_t p = hash(id);
+        while (key_[p] != empty() && key_[p] != id) p = (p + 1) & mask_;
+        if (key_[p] == empty()) {
+            if (size_ >= limit_) throw std::length_error("FlatIdMap::insert: more ids than reserved");
+            ++size_;
+        }
+        key_[p] = id;
+        val_[p] = value;
+    }
+    /* true if the id was present */
+    bool erase(int id) {
+        size_t hole = hash(id);
+        while (key_[hole] != empty() && key_[hole] != id) hole = (hole + 1) & mask_;
+        if (key_[hole] == empty()) return false;
+        for (size_t q = (hole + 1) & mask_; key_[q] != empty(); q = (q + 1) & mask_) {
+            /* the entry at q may move into the hole if that is not in front of its home slot (distances along the probe
+             * sequence, cyclic) */
+            const size_t home = hash((int)key_[q]);
+            if (((q - home) & mask_) >= ((q - hole) & mask_)) {
+                key_[hole] = key_[q];
+                val_[hole] = val_[q];
+                hole = q;
+            }
+        }
+        key_[hole] = empty();
+        val_[hole] = -1;
+        --size_;
+        return true;
+    }
+    size_t size() const { return size_; }
+    /* diagnostic (tests, tuning; not used by the ingest): slots looked at by find(id), 1 = found (or known absent) at
+     * its home slot */
+    int probes(int id) const {
+        int n = 1;
+        for (size_t p = hash(id); key_[p] != empty() && key_[p] != id; p = (p + 1) & mask_) ++n;
+        return n;
+    }
 
 private:
     static int64_t empty() { return INT64_MIN; }
     size_t hash(int id) const { return ((uint64_t)(uint32_t)id * 0x9E3779B97F4A7C15ull >> 32) & mask_; }
     std::vector<int64_t> key_;
     std::vector<int> val_;
-    size_t mask_ = 0;
+    size_t mask_ = 0, size_ = 0, limit_ = 0;
 };
 
 class BatchedRangingNode {
@@ -104,24 +146,71 @@ public:
     BatchedRangingNode(kfpos_handle *h, const std::vector<int> &tagIds, const std::vector<int> &anchorIds)
         : h_(h), T_((int)tagIds.size()), A_((int)anchorIds.size()) {
         row_.build(tagIds);
-        col_.build(anchorIds);
-        tags_.resize(T_);
-        real_ = kfpos_real_size(h);
-        dim_ = kfpos_state_dim(h);
-        nSlots_ = kfpos_slot_count(h) < kMaxSlots ? kfpos_slot_count(h) : kMaxSlots;
-        /* one (tag, sequence) row: count, A ranges, A errorEstimations, padded to whole cache lines */
-        rowBytes_ = ((sizeof(int32_t) * (1 + A_) + 7) & ~(size_t)7) + sizeof(double) * A_;
-        rowBytes_ = (rowBytes_ + 63) & ~(size_t)63;
-        errOff_ = (sizeof(int32_t) * (1 + A_) + 7) & ~(size_t)7;
-        table_.reset(new unsigned char[(size_t)T_ * 256 * rowBytes_ + 64]); /* untouched until a tag speaks up */
-        tableBase_ = (unsigned char *)(((uintptr_t)table_.get() + 63) & ~(uintptr_t)63);
-        taken_.assign(T_, 0);
-        for (int k = 0; k < 5; ++k) roundSlot_[k] = -1;
-        if (dim_ == 8) { /* planar filter: its other four sensors go through the synchronous kfpos_step_sensor */
-            for (int k = 1; k <= 4; ++k) sens_[k].assign((size_t)T_ * sensorWidth(k), 0.0);
-            sensDt_.assign(T_, -1.0);
+        rowId_ = tagIds;
+        bound_.assign(T_, 1);
+        init(anchorIds);
+    }
+    /* nRows free rows (handle: n_tags == nRows): tags are admitted with bindRows() as they show up */
+    BatchedRangingNode(kfpos_handle *h, int nRows, const std::vector<int> &anchorIds)
+        : h_(h), T_(nRows), A_((int)anchorIds.size()) {
+        row_.reserve(nRows);
+        rowId_.assign(T_, 0);
+        bound_.assign(T_, 0);
+        init(anchorIds);
+    }
+
+    /* ---- tags that come and go: a row of the bank is reusable ----
+     * Both calls are legal only while no call of any tag is pending, i.e. right after poll() returned and before the
+     * next message (no round being assembled, nothing waiting for a later round); std::logic_error otherwise. There is
+     * no queue for them: the caller picks the moment.
+     *
+     * releaseRows: the rows stop serving their tag ids. The ids leave the id map -- later messages for them are "not
+     * one of ours", like any id this node was never told about --, and each row's table state goes back to its default:
+     * its 256 sequence rows are initialised again on first use, the estimator clock restarts (the next tag's first call
+     * has the first-call lag of 0.1 s), the 50 ms timer is disarmed; an epoch the tag still had open is dropped with it.
+     * The filter itself is left as it is until the row is bound again. A row that is not bound: std::logic_error. */
+    void releaseRows(const int *rows, int n) {
+        requireIdle("releaseRows");
+        for (int i = 0; i < n; ++i)
+            if (rows[i] < 0 || rows[i] >= T_ || !bound_[rows[i]])
+                throw std::logic_error("releaseRows: row " + std::to_string(rows[i]) + " is not bound");
+        for (int i = 0; i < n; ++i) {
+            const int r = rows[i];
+            if (!bound_[r]) continue; /* listed twice */
+            if (row_.find(rowId_[r]) == r) row_.erase(rowId_[r]);
+            bound_[r] = 0;
+            tags_[r] = Tag();
         }
     }
+    /* bindRows: row rows[i] serves tag tagIds[i] from now on, its filter as a freshly created handle has it: ONE
+     * kfpos_reset_tags for all n -- one wait on the pipeline per batch of admissions, not per tag --, then the ids enter
+     * the map. initXyz: n x 3 start positions, or nullptr = the handle's kfpos_config.init_pos (it must be nullptr on a
+     * handle that starts by ML initialisation). Rows must be free, ids must not be bound (nor listed twice):
+     * std::logic_error, and nothing has changed. */
+    void bindRows(const int *rows, const int *tagIds, int n, const double *initXyz) {
+        requireIdle("bindRows");
+        for (int i = 0; i < n; ++i) {
+            if (rows[i] < 0 || rows[i] >= T_ || bound_[rows[i]])
+                throw std::logic_error("bindRows: row " + std::to_string(rows[i]) + " is not free");
+            if (row_.find(tagIds[i]) >= 0)
+                throw std::logic_error("bindRows: tag id " + std::to_string(tagIds[i]) + " is already bound");
+            for (int j = 0; j < i; ++j)
+                if (rows[j] == rows[i] || tagIds[j] == tagIds[i])
+                    throw std::logic_error("bindRows: row or tag id listed twice");
+        }
+        if (n <= 0) return;
+        std::vector<int32_t> r(rows, rows + n);
+        check(kfpos_reset_tags(h_, r.data(), n, initXyz), "kfpos_reset_tags");
+        for (int i = 0; i < n; ++i) {
+            row_.insert(tagIds[i], rows[i]);
+            rowId_[rows[i]] = tagIds[i];
+            bound_[rows[i]] = 1;
+            tags_[rows[i]] = Tag();
+        }
+    }
+    /* the row that serves tagId, -1 if none */
+    int rowOf(int tagId) const { return row_.find(tagId); }
+    bool bound(int row) const { return bound_[row] != 0; } /* diagnostic: does the row serve a tag at the moment */
 
     /* gtec_msgs::Ranging -> PosGenerator::newTOAMeasurement -> processRangingNow */
     void onRanging(double now, int anchorId, int tagId, double range, double errorEstimation, int seq) {
@@ -203,6 +292,30 @@ private:
         double lag;
         size_t off; /* ranging: A ints in ovInt_ and A doubles in ovDbl_; sensor: its sample in ovDbl_ */
     };
+
+    void init(const std::vector<int> &anchorIds) {
+        col_.build(anchorIds);
+        tags_.resize(T_);
+        real_ = kfpos_real_size(h_);
+        dim_ = kfpos_state_dim(h_);
+        nSlots_ = kfpos_slot_count(h_) < kMaxSlots ? kfpos_slot_count(h_) : kMaxSlots;
+        /* one (tag, sequence) row: count, A ranges, A errorEstimations, padded to whole cache lines */
+        rowBytes_ = ((sizeof(int32_t) * (1 + A_) + 7) & ~(size_t)7) + sizeof(double) * A_;
+        rowBytes_ = (rowBytes_ + 63) & ~(size_t)63;
+        errOff_ = (sizeof(int32_t) * (1 + A_) + 7) & ~(size_t)7;
+        table_.reset(new unsigned char[(size_t)T_ * 256 * rowBytes_ + 64]); /* untouched until a tag speaks up */
+        tableBase_ = (unsigned char *)(((uintptr_t)table_.get() + 63) & ~(uintptr_t)63);
+        taken_.assign(T_, 0);
+        for (int k = 0; k < 5; ++k) roundSlot_[k] = -1;
+        if (dim_ == 8) { /* planar filter: its other four sensors go through the synchronous kfpos_step_sensor */
+            for (int k = 1; k <= 4; ++k) sens_[k].assign((size_t)T_ * sensorWidth(k), 0.0);
+            sensDt_.assign(T_, -1.0);
+        }
+    }
+    void requireIdle(const char *who) const {
+        if (roundCalls_ != 0 || !overflow_.empty())
+            throw std::logic_error(std::string(who) + ": estimator calls are pending; call it right after poll()");
+    }
 
     static int sensorWidth(int kind) {
         return kind == KFPOS_SENSOR_PX4FLOW ? 5 : kind == KFPOS_SENSOR_IMU ? 24 : kind == KFPOS_SENSOR_MAG ? 3 : 1;
@@ -423,6 +536,8 @@ private:
     kfpos_handle *h_;
     int T_, A_, real_ = 8, dim_ = 6;
     FlatIdMap row_, col_;
+    std::vector<int> rowId_;           /* the tag id a bound row serves */
+    std::vector<unsigned char> bound_; /* 0 = free row */
     std::vector<Tag> tags_;
     std::unique_ptr<unsigned char[]> table_;
     unsigned char *tableBase_ = nullptr;

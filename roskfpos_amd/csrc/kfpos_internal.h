@@ -71,6 +71,7 @@ struct kfpos_handle {
      * bus, so a call is "turn the layout on the CPU, launch, synchronise" -- no hipMemcpy, no layout kernels */
     unsigned char *sm_h = nullptr, *sm_d = nullptr;
     size_t sm_ranges = 0, sm_err = 0, sm_accel = 0, sm_cov = 0, sm_dt = 0, sm_sensor = 0, sm_status = 0, sm_out = 0;
+    size_t sm_bytes = 0; /* the whole block: nothing in it outlives a call, so the per-tag accessors stage through all of it */
     /* streaming host API: KFPOS_N_SLOTS slots of pinned host + device buffers, three streams (kfpos_slot_*) */
     struct Slot {
         unsigned char *host = nullptr; /* pinned block: ranges | err | accel | cov | dt | status | pos */

@@ -25,7 +25,7 @@
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
  * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_misc (8-state planar
- * filter, standalone ML estimator, getPose, layout turns), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
+ * filter, standalone ML estimator, getPose, layout turns), kfpos_k_tags (per-tag gather / scatter / reset), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
 #define KFPOS_KERNELS_H
@@ -110,7 +110,36 @@ void launch_get_pose(int model, bool full, int st, int blocks, hipStream_t s, co
 void launch_rows_to_cols(size_t esz, hipStream_t s, const void *src, void *dst, int T, int C);    /* kfpos_k_misc.hip */
 void launch_cols_to_rows(hipStream_t s, const double *src, double *dst, int T, int C);            /* kfpos_k_misc.hip */
 
-constexpr int COOP_LANES = 8;                    /* kfpos_k_coop.hip: one tag per group of 8 lanes */
+/* ---- per-tag lifecycle (kfpos_k_tags.hip): gather / scatter / reset of a list of tags ----
+ * One entry of the table that says where a component lives: kind = element type (TC_*), buf = index into TagArgs::buf,
+ * row = row of that component-major array. aux -- gather / scatter: 1 = the entry is stored through this component
+ * (0: not stored at all, or the lower-triangle mirror of a packed entry); reset: what a fresh handle holds (0 = zero,
+ * 1..5 = TagArgs::cst[aux - 1], 1..3 taken from TagArgs::init when that is given). */
+struct TagComp {
+    uint8_t kind, buf, row, aux;
+};
+enum : int { TC_NONE = 0, TC_F64 = 1, TC_COV = 2, TC_REAL = 3 };                 /* double / stored covariance entry / kfpos_real */
+enum : int { TB_POS = 0, TB_VEL, TB_P, TB_IMU_ACC, TB_IMU_COV, TB_LATCH, TB_N }; /* TagArgs::buf */
+enum : int { TAGS_GATHER = 0, TAGS_SCATTER = 1, TAGS_RESET = 2 };
+constexpr int TAG_SECTIONS = 4;            /* x | P | latch | height */
+constexpr int TAG_COMPS = 9 + 81 + 15 + 1; /* the longest record: no model has all of them at once */
+struct TagArgs {
+    int T, n, psz;            /* tags in the bank, tags listed in this launch, stored covariance entries per tag */
+    int w[TAG_SECTIONS];      /* gather / scatter: components per tag of each section present in `val`, 0 = section absent */
+    int cbase[TAG_SECTIONS];  /* where each section starts in comp[] */
+    int n_comp;               /* reset: stored rows listed in comp[] */
+    void *buf[TB_N];          /* the bank's component-major arrays */
+    uint32_t *flags;          /* [T] */
+    const int32_t *rows;      /* [n] rows of the bank, validated by the host */
+    double *val;              /* staging: x [n][w0] | P [n][w1] | latch [n][w2] | height [n][w3] */
+    uint32_t *fl;             /* staging: [n] flags words, or null */
+    const double *init;       /* reset: [n][3] start positions, or null = cst[0..2] */
+    double cst[5];            /* reset: start position x y z (NaN: ML initialisation), planar height, planar angle */
+    TagComp comp[TAG_COMPS];
+};
+void launch_tags(int op, int st, hipStream_t s, const TagArgs &a);          /* kfpos_k_tags.hip */
+
+constexpr int COOP_LANES = 8;                   /* kfpos_k_coop.hip: one tag per group of 8 lanes */
 constexpr int COOP_TAGS_PER_WAVE = 64 / COOP_LANES;
 constexpr int PLANAR_HAS_SHIFT = 4;              /* planar flags word: bits 5..7 = latched PX4Flow / IMU / magnetometer */
 constexpr int LATCH_ROWS = 15;
