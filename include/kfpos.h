@@ -300,6 +300,34 @@ int kfpos_get_tags(kfpos_handle *h, const int32_t *rows, int32_t n,
 int kfpos_set_tags(kfpos_handle *h, const int32_t *rows, int32_t n,
                    const double *x, const double *P, const uint32_t *flags, const double *latch, const double *height);
 
+/* ---- row-list steps: an epoch for the tags that REPORTED ----
+ * Tags report asynchronously: a round usually carries a fraction of the bank. The calls above are whole-bank (a tag
+ * without an epoch is marked by dt < 0, and all n_tags x max_anchors inputs cross the bus); these take a list, like
+ * the lifecycle calls: `rows` = n row indices, inputs row-major PER LISTED TAG -- entry i belongs to tag rows[i] --, and
+ * what crosses the bus and what the GPU touches follows n.
+ *   semantics   exactly the whole-bank call of the same name with the listed tags' inputs and dt < 0 for every other
+ *               tag: every status word, state, covariance and latch comes out bit-identical (the same kernel runs, on
+ *               a compact copy of the listed tags that is gathered before and scattered after it). A tag that is not
+ *               listed is not written. A negative dt[i] still skips tag rows[i] (KFPOS_ST_SKIPPED).
+ *   dt          dt_len = 1 (shared by the listed tags) or n;  status: n words or NULL
+ *   validation  on the host before any write: h == NULL, n < 0, rows == NULL with n > 0, a row outside [0, n_tags) or
+ *               listed twice -> KFPOS_ERR_ARG, kfpos_last_error() names the first offending entry. The kernels never see
+ *               an unchecked index, which is why there is no _dev variant: a device-resident list could not be checked
+ *               without a synchronisation.
+ *   n == 0      KFPOS_OK, nothing happens.
+ *   ordering, device, model errors and no-ops (6-state IMU, non-planar sensor: KFPOS_OK, status 0) as the whole-bank
+ *               calls; the call counts as a step, and a sensor call switches a planar handle's ranging epochs to the
+ *               instantiation that honours latches, as kfpos_step_sensor does.
+ * KFPOS_VERSION is unchanged by them: detect them by symbol. */
+int kfpos_step_toa_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const int32_t *range_mm /* n x max_anchors */,
+                        const void *err_est /* n x max_anchors */, const double *dt, int32_t dt_len, uint32_t *status);
+int kfpos_step_imu_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const void *accel /* n x 3 */,
+                        const void *cov /* n x 9 */, const double *dt, int32_t dt_len, uint32_t *status);
+int kfpos_step_toa_imu_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const int32_t *range_mm, const void *err_est,
+                            const void *accel, const void *cov, const double *dt, int32_t dt_len, uint32_t *status);
+int kfpos_step_sensor_rows(kfpos_handle *h, const int32_t *rows, int32_t n, int32_t kind, const double *data /* n x C */,
+                           const double *dt, int32_t dt_len, uint32_t *status);
+
 /* ---- streaming host API: epochs pipelined through kfpos_slot_count() slots of pinned host memory ----
  * For a node that feeds epoch after epoch from the CPU (PosGenerator's table flushes, Posgenerator.cpp:155-198, batched
  * over many tags): the synchronous calls above copy pageable arrays, turn their layout on the device and wait; here
@@ -334,6 +362,32 @@ int kfpos_slot_count(const kfpos_handle *h); /* 3: one being filled, one on the 
 int kfpos_slot_acquire(kfpos_handle *h, int32_t slot, kfpos_epoch_slot *out);
 int kfpos_slot_submit(kfpos_handle *h, int32_t slot, int32_t flags, double dt_shared);
 int kfpos_slot_wait(kfpos_handle *h, int32_t slot);
+
+/* A slot can also carry a row-list round (see "row-list steps"): same three slots, streams, ordering and kfpos_slot_wait;
+ * a slot serves one kind of round at a time, and acquire waits for its previous submission, whichever kind it was.
+ * Whole-bank and row-list submissions may be interleaved freely and execute in submission order.
+ *   rows        [capacity] the row list; inputs ROW-MAJOR per listed tag, so one reporter's record is contiguous:
+ *               range_mm [n][max_anchors], err_est [n][max_anchors], accel [n][3], cov [n][9], dt [n]
+ *               (KFPOS_SLOT_DT_PER_TAG; negative = skip tag rows[i])
+ *   out         status [n], pos [3][n] (stride n; unless KFPOS_SLOT_NO_POSE)
+ *   capacity    n_tags. The arrays other than `rows` are the slot's kfpos_epoch_slot arrays seen through another layout.
+ * kfpos_slot_submit_rows(flags, n): flags as kfpos_slot_submit; the list is validated on the host, in O(n), before
+ * anything is enqueued (KFPOS_ERR_ARG as above, n > capacity included); n == 0 is KFPOS_OK and enqueues nothing. Only
+ * bytes proportional to n cross the bus, in either direction. KFPOS_SLOT_REUSE_ERR / _COV are refused (KFPOS_ERR_ARG),
+ * and a row-list round never becomes "the previous submission" a later whole-bank KFPOS_SLOT_REUSE_* refers to. */
+typedef struct kfpos_rows_slot {
+    int32_t  *rows;
+    int32_t  *range_mm;
+    void     *err_est;
+    void     *accel;
+    void     *cov;
+    double   *dt;
+    uint32_t *status;
+    double   *pos;
+    int32_t   capacity;
+} kfpos_rows_slot;
+int kfpos_slot_acquire_rows(kfpos_handle *h, int32_t slot, kfpos_rows_slot *out);
+int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t n, double dt_shared);
 
 /* ---- asynchronous device-buffer API (inputs already resident in HBM) ----
  * All pointers are device pointers; `stream` is a hipStream_t (NULL = the default stream). Calls

@@ -36,6 +36,8 @@ EXPORTS = [
     "kfpos_latch_dim", "kfpos_get_latch", "kfpos_set_latch",
     "kfpos_reset_tags", "kfpos_get_tags", "kfpos_set_tags",
     "kfpos_slot_count", "kfpos_slot_acquire", "kfpos_slot_submit", "kfpos_slot_wait",
+    "kfpos_step_toa_rows", "kfpos_step_imu_rows", "kfpos_step_toa_imu_rows", "kfpos_step_sensor_rows",
+    "kfpos_slot_acquire_rows", "kfpos_slot_submit_rows",
     "kfpos_shard_range", "kfpos_comm_unique_id", "kfpos_comm_create", "kfpos_comm_create_all", "kfpos_comm_destroy",
     "kfpos_comm_world", "kfpos_comm_rank", "kfpos_comm_set_total", "kfpos_allgather_poses",
     "kfpos_allgather_poses_multi", "kfpos_comm_wait", "kfpos_comm_sync", "kfpos_assemble_poses_dev",
@@ -73,6 +75,13 @@ class _EpochSlot(C.Structure):
     """kfpos_epoch_slot: pointers into one slot of the handle's pinned host memory."""
     _fields_ = [("range_mm", C.c_void_p), ("err_est", C.c_void_p), ("accel", C.c_void_p), ("cov", C.c_void_p),
                 ("dt", C.c_void_p), ("status", C.c_void_p), ("pos", C.c_void_p)]
+
+
+class _RowsSlot(C.Structure):
+    """kfpos_rows_slot: the same pinned block seen as a row-list round, plus the slot's row list."""
+    _fields_ = [("rows", C.c_void_p), ("range_mm", C.c_void_p), ("err_est", C.c_void_p), ("accel", C.c_void_p),
+                ("cov", C.c_void_p), ("dt", C.c_void_p), ("status", C.c_void_p), ("pos", C.c_void_p),
+                ("capacity", C.c_int32)]
 
 
 _lib = None
@@ -137,6 +146,12 @@ def load():
     sig("kfpos_slot_acquire", [vp, i32, C.POINTER(_EpochSlot)])
     sig("kfpos_slot_submit", [vp, i32, i32, f64])
     sig("kfpos_slot_wait", [vp, i32])
+    sig("kfpos_step_toa_rows", [vp, vp, i32, vp, vp, vp, i32, vp])
+    sig("kfpos_step_imu_rows", [vp, vp, i32, vp, vp, vp, i32, vp])
+    sig("kfpos_step_toa_imu_rows", [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp])
+    sig("kfpos_step_sensor_rows", [vp, vp, i32, i32, vp, vp, i32, vp])
+    sig("kfpos_slot_acquire_rows", [vp, i32, C.POINTER(_RowsSlot)])
+    sig("kfpos_slot_submit_rows", [vp, i32, i32, i32, f64])
     sig("kfpos_timing_begin", [vp, vp])
     sig("kfpos_timing_end", [vp, vp, C.POINTER(C.c_float)])
     i64 = C.c_int64
@@ -396,6 +411,56 @@ class KfposBank:
         self._chk(self.lib.kfpos_set_tags(self._h, r.ctypes.data, m, ptr(x), ptr(P), ptr(fl),
                                           None if L == 0 else ptr(latch), ptr(z)))
 
+    # ---- row-list steps: an epoch for the listed rows only; inputs are per listed tag, (len(rows), ...) ----
+    def _dt_rows(self, dt, m):
+        d = np.atleast_1d(np.ascontiguousarray(dt, dtype=np.float64))
+        assert d.size in (1, m)
+        return d
+
+    def step_toa_rows(self, rows, range_mm, err_est, dt):
+        """step_toa for the tags in `rows` (everyone else: untouched, as with dt < 0); returns their status words."""
+        q = self._rows(rows)
+        r = np.ascontiguousarray(range_mm, dtype=np.int32)
+        e = np.ascontiguousarray(err_est, dtype=self.real)
+        assert r.shape == (q.size, self.A) and e.shape == (q.size, self.A)
+        d, st = self._dt_rows(dt, q.size), np.zeros(q.size, dtype=np.uint32)
+        self._chk(self.lib.kfpos_step_toa_rows(self._h, q.ctypes.data, q.size, r.ctypes.data, e.ctypes.data,
+                                               d.ctypes.data, d.size, st.ctypes.data))
+        return st
+
+    def step_imu_rows(self, rows, accel, cov, dt):
+        q = self._rows(rows)
+        a = np.ascontiguousarray(accel, dtype=self.real)
+        c = np.ascontiguousarray(cov, dtype=self.real)
+        assert a.shape == (q.size, 3) and c.shape == (q.size, 9)
+        d, st = self._dt_rows(dt, q.size), np.zeros(q.size, dtype=np.uint32)
+        self._chk(self.lib.kfpos_step_imu_rows(self._h, q.ctypes.data, q.size, a.ctypes.data, c.ctypes.data,
+                                               d.ctypes.data, d.size, st.ctypes.data))
+        return st
+
+    def step_toa_imu_rows(self, rows, range_mm, err_est, accel, cov, dt):
+        q = self._rows(rows)
+        r = np.ascontiguousarray(range_mm, dtype=np.int32)
+        e = np.ascontiguousarray(err_est, dtype=self.real)
+        a = np.ascontiguousarray(accel, dtype=self.real)
+        c = np.ascontiguousarray(cov, dtype=self.real)
+        assert r.shape == (q.size, self.A) and e.shape == (q.size, self.A)
+        assert a.shape == (q.size, 3) and c.shape == (q.size, 9)
+        d, st = self._dt_rows(dt, q.size), np.zeros(q.size, dtype=np.uint32)
+        self._chk(self.lib.kfpos_step_toa_imu_rows(self._h, q.ctypes.data, q.size, r.ctypes.data, e.ctypes.data,
+                                                   a.ctypes.data, c.ctypes.data, d.ctypes.data, d.size,
+                                                   st.ctypes.data))
+        return st
+
+    def step_sensor_rows(self, rows, kind, data, dt):
+        q = self._rows(rows)
+        x = np.ascontiguousarray(data, dtype=np.float64).reshape(q.size, -1)
+        assert x.shape[1] == _SENSOR_WIDTH[kind]
+        d, st = self._dt_rows(dt, q.size), np.zeros(q.size, dtype=np.uint32)
+        self._chk(self.lib.kfpos_step_sensor_rows(self._h, q.ctypes.data, q.size, kind, x.ctypes.data,
+                                                  d.ctypes.data, d.size, st.ctypes.data))
+        return st
+
     # ---- streaming host API: epochs assembled in place in pinned, component-major slots ----
     def slot_acquire(self, slot):
         """Wait for the slot's previous submission; returns numpy views over the slot's pinned memory:
@@ -419,6 +484,28 @@ class KfposBank:
 
     def slot_wait(self, slot):
         self._chk(self.lib.kfpos_slot_wait(self._h, slot))
+
+    def slot_acquire_rows(self, slot):
+        """The slot as a row-list round: numpy views at full capacity (T listed tags), row-major per listed tag:
+        dict(rows [T], range_mm [T][A], err_est [T][A], accel [T][3], cov [T][9], dt [T], status [T], pos (flat 3 T:
+        after a round of n tags its first 3 n doubles are [3][n])). Fill the first n entries, then slot_submit_rows."""
+        sl = _RowsSlot()
+        self._chk(self.lib.kfpos_slot_acquire_rows(self._h, slot, C.byref(sl)))
+        T, A = self.T, self.A
+
+        def view(ptr, shape, dtype):
+            n = int(np.prod(shape))
+            buf = (C.c_char * (n * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dtype, count=n).reshape(shape)
+
+        return {"rows": view(sl.rows, (T,), np.int32),
+                "range_mm": view(sl.range_mm, (T, A), np.int32), "err_est": view(sl.err_est, (T, A), self.real),
+                "accel": view(sl.accel, (T, 3), self.real), "cov": view(sl.cov, (T, 9), self.real),
+                "dt": view(sl.dt, (T,), np.float64), "status": view(sl.status, (T,), np.uint32),
+                "pos": view(sl.pos, (3 * T,), np.float64)}
+
+    def slot_submit_rows(self, slot, flags, n, dt_shared=0.0):
+        self._chk(self.lib.kfpos_slot_submit_rows(self._h, slot, int(flags), int(n), float(dt_shared)))
 
     # ---- device-buffer API (pointers: ints or torch tensors; layouts in include/kfpos.h) ----
     def step_toa_dev(self, range_mm, err_est, dt, status=None, stream=None, dt_dev=None):

@@ -129,15 +129,17 @@ step_kernel_t step_kernel(const kfpos_handle *h, bool sensor_call = false, bool 
     return kfpos_k::imu9_kernel(st, as, !imu_only);
 }
 
+/* a.T tags: the whole bank, or the n tags of a work bank (row-list steps). WHICH kernel runs is a property of the handle,
+ * never of a.T: a row-list step computes bit for bit what the whole-bank call does */
 int launch_step(kfpos_handle *h, const KArgs &a, hipStream_t s) {
     if (h->coop) {
-        const int groups = (h->cfg.n_tags + COOP_TAGS_PER_WAVE - 1) / COOP_TAGS_PER_WAVE;
+        const int groups = (a.T + COOP_TAGS_PER_WAVE - 1) / COOP_TAGS_PER_WAVE;
         hipLaunchKernelGGL(step_kernel(h), dim3(groups), dim3(WAVE), 0, s, a);
         HIPCHK(hipGetLastError());
         h->stepped = true;
         return KFPOS_OK;
     }
-    const int blocks = (h->cfg.n_tags + WAVE - 1) / WAVE;
+    const int blocks = (a.T + WAVE - 1) / WAVE;
     /* does the selected kernel stage the epoch in LDS? */
     const bool generic = h->force_generic || static_anchors(h) <= 0 || (h->cfg.model == KFPOS_MODEL_TOA && h->full) ||
                          (h->cfg.model == KFPOS_MODEL_PLANAR && h->planar_sensors) || toa6_two_waves(h);
@@ -240,10 +242,11 @@ void rows_to_cols_host(void *dst, const void *src, size_t T, int C) {
         for (int c = 0; c < C; ++c) d[(size_t)c * T + t] = s[t * C + c];
 }
 /* host row-major [T][C] -> component-major [C][T] inside the mapped block */
-void small_in(kfpos_handle *h, size_t off, const void *src, int C, size_t esz) {
-    if (esz == 4) rows_to_cols_host<uint32_t>(h->sm_h + off, src, h->cfg.n_tags, C);
-    else rows_to_cols_host<uint64_t>(h->sm_h + off, src, h->cfg.n_tags, C);
+void small_in_n(kfpos_handle *h, size_t off, const void *src, size_t T, int C, size_t esz) {
+    if (esz == 4) rows_to_cols_host<uint32_t>(h->sm_h + off, src, T, C);
+    else rows_to_cols_host<uint64_t>(h->sm_h + off, src, T, C);
 }
+void small_in(kfpos_handle *h, size_t off, const void *src, int C, size_t esz) { small_in_n(h, off, src, h->cfg.n_tags, C, esz); }
 /* component-major [C][T] doubles in the mapped block -> host row-major [T][C] */
 void small_out(const kfpos_handle *h, double *dst, size_t off_doubles, int C) {
     const size_t T = h->cfg.n_tags;
@@ -485,7 +488,7 @@ int kfpos_destroy(kfpos_handle *h) {
     if (!h) return KFPOS_ERR_ARG;
     void *ptrs[] = {h->d_pos, h->d_vel, h->d_P, h->d_imu_acc, h->d_imu_cov, h->d_flags, h->d_ranges,
                     h->d_err, h->d_accel, h->d_cov, h->d_dt, h->d_out, h->d_status, h->d_latch, h->d_sensor,
-                    h->d_stage};
+                    h->d_stage, h->d_work};
     DevScope dev_(h->cfg.device);
     (void)hipDeviceSynchronize(); /* nothing of this handle may still be in flight (streaming slots) */
     for (void *p : ptrs)
@@ -493,6 +496,7 @@ int kfpos_destroy(kfpos_handle *h) {
     if (h->sm_h) (void)hipHostFree(h->sm_h);
     for (auto &sl : h->slot) {
         if (sl.host) (void)hipHostFree(sl.host);
+        if (sl.rows) (void)hipHostFree(sl.rows);
         if (sl.dev) (void)hipFree(sl.dev);
         if (sl.copied) (void)hipEventDestroy(sl.copied);
         if (sl.copied2) (void)hipEventDestroy(sl.copied2);
@@ -1610,6 +1614,324 @@ int kfpos_reset_tags(kfpos_handle *h, const int32_t *rows, int32_t n, const doub
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(nullptr));
     }
+    return KFPOS_OK;
+}
+
+/* ---- row-list steps: kfpos_step_*_rows, kfpos_slot_acquire_rows / kfpos_slot_submit_rows ----
+ * The step kernels are not touched and see no row index: the listed tags' stored bits are gathered into a compact work
+ * bank (kfpos_k_tags.hip: k_rows_work), the kernel this handle runs anyway steps that bank with KArgs::T = n, and the
+ * result is scattered back. Launches per round: gather + one layout turn per input array (2 for a ranging round, 4 for a
+ * fused one, 1 for a sensor sample; none on a small bank's mapped block) + step + scatter. */
+struct RowsLayout {
+    size_t in_bytes; /* one input area (for work_cap tags) and the places inside it */
+    size_t i_rows, i_ranges, i_err, i_accel, i_cov, i_sensor, i_dt, i_status, i_pos;
+    size_t w[kfpos_k::TB_N], w_flags, w_ranges, w_err, w_accel, w_cov, w_sensor; /* the work bank at stride n */
+    size_t total;
+};
+static RowsLayout rows_layout(const kfpos_handle *h, size_t cap, size_t n) {
+    using namespace kfpos_k;
+    RowsLayout L{};
+    const size_t A = h->cfg.max_anchors, m = h->msz, imu = h->n == 9 ? 1 : 0, pl = h->n == 8 ? 1 : 0;
+    size_t off = 0;
+    auto region = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    L.i_rows = region(cap * sizeof(int32_t));
+    L.i_ranges = region(cap * A * sizeof(int32_t));
+    L.i_err = region(cap * A * m);
+    L.i_accel = region(imu * cap * 3 * m);
+    L.i_cov = region(imu * cap * 9 * m);
+    L.i_sensor = region(pl * cap * 24 * sizeof(double));
+    L.i_dt = region(cap * sizeof(double));
+    L.i_status = region(cap * sizeof(uint32_t));
+    L.i_pos = region(cap * 3 * sizeof(double));
+    L.in_bytes = off;
+    off = KFPOS_N_SLOTS * L.in_bytes;
+    L.w[TB_POS] = region(3 * n * sizeof(double));
+    L.w[TB_VEL] = region((h->n == 8 ? 4 : (h->n == 6 ? 0 : 3)) * n * sizeof(double));
+    L.w[TB_P] = region((size_t)h->psz * n * h->rsz);
+    L.w[TB_IMU_ACC] = region(imu * 3 * n * m);
+    L.w[TB_IMU_COV] = region(imu * 6 * n * m);
+    L.w[TB_LATCH] = region(pl * LATCH_ROWS * n * sizeof(double));
+    L.w_flags = region(n * sizeof(uint32_t));
+    L.w_ranges = region(n * A * sizeof(int32_t));
+    L.w_err = region(n * A * m);
+    L.w_accel = region(imu * n * 3 * m);
+    L.w_cov = region(imu * n * 9 * m);
+    L.w_sensor = region(pl * n * 24 * sizeof(double));
+    L.total = off;
+    return L;
+}
+/* room for n listed tags; growing frees the old block, so everything in flight completes first */
+static int rows_reserve(kfpos_handle *h, size_t n) {
+    if (n <= h->work_cap) return KFPOS_OK;
+    size_t cap = n > 2 * h->work_cap ? n : 2 * h->work_cap;
+    if (cap > (size_t)h->cfg.n_tags) cap = h->cfg.n_tags;
+    HIPCHK(hipDeviceSynchronize());
+    if (h->d_work) (void)hipFree(h->d_work);
+    h->d_work = nullptr;
+    h->work_cap = 0;
+    HIPCHK(hipMalloc((void **)&h->d_work, rows_layout(h, cap, cap).total));
+    h->work_cap = cap;
+    return KFPOS_OK;
+}
+/* tags_check(unique) in O(n) -- a round of the streaming path validates its list on every submission: each row carries
+ * the number of the call that last listed it. Same answers, same texts: the first offending entry of the list. */
+static int rows_check(kfpos_handle *h, const char *who, const int32_t *rows, int32_t n) {
+    if (n < 0 || (n > 0 && !rows)) return tags_check(h, who, rows, n, true);
+    if (h->row_stamp.empty()) h->row_stamp.assign((size_t)h->cfg.n_tags, 0u);
+    if (++h->stamp == 0) { /* wrapped: forget every earlier call */
+        std::fill(h->row_stamp.begin(), h->row_stamp.end(), 0u);
+        h->stamp = 1;
+    }
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t r = rows[i];
+        if (r < 0 || r >= h->cfg.n_tags || h->row_stamp[r] == h->stamp) return tags_check(h, who, rows, i + 1, true);
+        h->row_stamp[r] = h->stamp;
+    }
+    return KFPOS_OK;
+}
+/* gather -> step -> scatter on stream s. a: fill_args + the inputs of the call at [.][n], status [n], traj [3][n] */
+static int rows_step(kfpos_handle *h, hipStream_t s, const RowsLayout &L, const int32_t *d_rows, int n, KArgs &a) {
+    using namespace kfpos_k;
+    TagArgs g;
+    tag_args(h, g);
+    tag_fresh(h, g); /* the stored rows of a tag: the list a reset writes */
+    g.n = n;
+    g.rows = d_rows;
+    for (int b = 0; b < TB_N; ++b) g.wbuf[b] = g.buf[b] ? h->d_work + L.w[b] : nullptr;
+    g.wflags = (uint32_t *)(h->d_work + L.w_flags);
+    launch_tags(TAGS_WORK_IN, h->cfg.storage, s, g);
+    HIPCHK(hipGetLastError());
+    a.T = n;
+    a.pos = (double *)g.wbuf[TB_POS];
+    a.vel = (double *)g.wbuf[TB_VEL];
+    a.P = g.wbuf[TB_P];
+    a.flags = g.wflags;
+    a.imu_acc = g.wbuf[TB_IMU_ACC];
+    a.imu_cov = g.wbuf[TB_IMU_COV];
+    a.platch = (double *)g.wbuf[TB_LATCH];
+    const int rc = launch_step(h, a, s);
+    if (rc) return rc;
+    launch_tags(TAGS_WORK_OUT, h->cfg.storage, s, g);
+    HIPCHK(hipGetLastError());
+    return KFPOS_OK;
+}
+
+enum { ROWS_TOA = 0, ROWS_IMU = 1, ROWS_TOA_IMU = 2, ROWS_SENSOR = 3 };
+/* the synchronous row-list calls: what the whole-bank call of the same name does, for the listed tags only */
+static int step_rows_host(kfpos_handle *h, const char *who, int call, const int32_t *rows, int32_t n,
+                          const int32_t *range_mm, const void *err_est, const void *accel, const void *cov,
+                          int32_t sensor_kind, const double *data, const double *dt, int32_t dt_len, uint32_t *status) {
+    g_err.clear();
+    if (!h) return KFPOS_ERR_ARG;
+    const bool rng = call == ROWS_TOA || call == ROWS_TOA_IMU, imu = call == ROWS_IMU || call == ROWS_TOA_IMU;
+    const int C = call == ROWS_SENSOR ? sensor_width(sensor_kind) : 0;
+    if (call == ROWS_SENSOR && C == 0) return KFPOS_ERR_ARG;
+    int rc = rows_check(h, who, rows, n);
+    if (rc) return rc;
+    if (n == 0) return KFPOS_OK;
+    if ((rng && (!range_mm || !err_est)) || (imu && (!accel || !cov)) || (call == ROWS_SENSOR && !data)) return KFPOS_ERR_ARG;
+    if (call == ROWS_TOA_IMU && h->cfg.model != KFPOS_MODEL_TOA_IMU) return KFPOS_ERR_MODEL;
+    if ((call == ROWS_IMU && h->cfg.model != KFPOS_MODEL_TOA_IMU) || (call == ROWS_SENSOR && h->cfg.model != KFPOS_MODEL_PLANAR)) {
+        if (status) std::memset(status, 0, sizeof(uint32_t) * n); /* the reference's empty virtuals */
+        return KFPOS_OK;
+    }
+    if (rng && !h->have_anchors) {
+        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
+        return KFPOS_ERR_STATE;
+    }
+    if (!dt || (dt_len != 1 && dt_len != n)) return KFPOS_ERR_ARG;
+    DevScope dev_(h->cfg.device);
+    if ((rc = drain_slots(h))) return rc;
+    if ((rc = rows_reserve(h, (size_t)n))) return rc;
+    const RowsLayout L = rows_layout(h, h->work_cap, (size_t)n);
+    const bool small = h->sm_h != nullptr; /* inputs and status through the mapped block, turned on the CPU */
+    unsigned char *in = h->d_work;         /* input area 0: the slots have been drained */
+    const size_t A = h->cfg.max_anchors, m = h->msz;
+    /* host row-major [n][C] -> device component-major [C][n]; the first HIP error is kept in `he` */
+    hipError_t he = hipSuccess;
+    auto stage = [&](const void *src, int Cc, size_t esz, size_t sm_off, size_t i_off, size_t w_off) -> const void * {
+        if (small) {
+            small_in_n(h, sm_off, src, (size_t)n, Cc, esz);
+            return h->sm_d + sm_off;
+        }
+        if (he == hipSuccess) he = hipMemcpy(in + i_off, src, (size_t)n * Cc * esz, hipMemcpyHostToDevice);
+        kfpos_k::launch_rows_to_cols(esz, nullptr, in + i_off, h->d_work + w_off, n, Cc);
+        if (he == hipSuccess) he = hipGetLastError();
+        return h->d_work + w_off;
+    };
+    KArgs a;
+    fill_args(h, a);
+    const int32_t *d_rows;
+    if (small) {
+        std::memcpy(h->sm_h + h->sm_out, rows, sizeof(int32_t) * n); /* the pose-output region: free during a step */
+        d_rows = (const int32_t *)(h->sm_d + h->sm_out);
+    } else {
+        HIPCHK(hipMemcpy(in + L.i_rows, rows, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+        d_rows = (const int32_t *)(in + L.i_rows);
+    }
+    if (rng) {
+        a.ranges = (const int32_t *)stage(range_mm, (int)A, sizeof(int32_t), h->sm_ranges, L.i_ranges, L.w_ranges);
+        a.err = stage(err_est, (int)A, m, h->sm_err, L.i_err, L.w_err);
+    }
+    if (imu) {
+        a.accel = stage(accel, 3, m, h->sm_accel, L.i_accel, L.w_accel);
+        a.cov = stage(cov, 9, m, h->sm_cov, L.i_cov, L.w_cov);
+    }
+    if (call == ROWS_SENSOR) a.sensor = (const double *)stage(data, C, sizeof(double), h->sm_sensor, L.i_sensor, L.w_sensor);
+    HIPCHK(he);
+    a.dt_shared = dt[0];
+    if (dt_len != 1 || n == 1) {
+        if (small) {
+            std::memcpy(h->sm_h + h->sm_dt, dt, sizeof(double) * n);
+            a.dt = (const double *)(h->sm_d + h->sm_dt);
+        } else {
+            HIPCHK(hipMemcpy(in + L.i_dt, dt, sizeof(double) * n, hipMemcpyHostToDevice));
+            a.dt = (const double *)(in + L.i_dt);
+        }
+    }
+    a.status = small ? (uint32_t *)(h->sm_d + h->sm_status) : (uint32_t *)(in + L.i_status);
+    a.mode = call == ROWS_SENSOR ? sensor_kind : (call == ROWS_TOA ? MODE_TOA : (call == ROWS_IMU ? MODE_IMU_ONLY : MODE_FUSED));
+    a.latch = 1;
+    rc = rows_step(h, nullptr, L, d_rows, n, a);
+    if (call == ROWS_SENSOR) h->planar_sensors = true; /* ranging epochs now carry the latched samples */
+    if (rc) return rc;
+    if (small) {
+        HIPCHK(hipStreamSynchronize(nullptr));
+        if (status) std::memcpy(status, h->sm_h + h->sm_status, sizeof(uint32_t) * n);
+        return KFPOS_OK;
+    }
+    HIPCHK(hipDeviceSynchronize());
+    if (status) HIPCHK(hipMemcpy(status, in + L.i_status, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    return KFPOS_OK;
+}
+
+int kfpos_step_toa_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const int32_t *range_mm, const void *err_est,
+                        const double *dt, int32_t dt_len, uint32_t *status) {
+    return step_rows_host(h, "kfpos_step_toa_rows", ROWS_TOA, rows, n, range_mm, err_est, nullptr, nullptr, 0, nullptr, dt, dt_len, status);
+}
+int kfpos_step_imu_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const void *accel, const void *cov,
+                        const double *dt, int32_t dt_len, uint32_t *status) {
+    return step_rows_host(h, "kfpos_step_imu_rows", ROWS_IMU, rows, n, nullptr, nullptr, accel, cov, 0, nullptr, dt, dt_len, status);
+}
+int kfpos_step_toa_imu_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const int32_t *range_mm, const void *err_est,
+                            const void *accel, const void *cov, const double *dt, int32_t dt_len, uint32_t *status) {
+    return step_rows_host(h, "kfpos_step_toa_imu_rows", ROWS_TOA_IMU, rows, n, range_mm, err_est, accel, cov, 0, nullptr, dt, dt_len, status);
+}
+int kfpos_step_sensor_rows(kfpos_handle *h, const int32_t *rows, int32_t n, int32_t kind, const double *data,
+                           const double *dt, int32_t dt_len, uint32_t *status) {
+    return step_rows_host(h, "kfpos_step_sensor_rows", ROWS_SENSOR, rows, n, nullptr, nullptr, nullptr, nullptr, kind, data, dt, dt_len, status);
+}
+
+int kfpos_slot_acquire_rows(kfpos_handle *h, int32_t slot, kfpos_rows_slot *out) {
+    g_err.clear();
+    if (!h || !out || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
+    DevScope dev_(h->cfg.device);
+    const int rc = slots_init(h);
+    if (rc) return rc;
+    auto &sl = h->slot[slot];
+    if (!sl.rows) HIPCHK(hipHostMalloc((void **)&sl.rows, sizeof(int32_t) * h->cfg.n_tags, hipHostMallocDefault));
+    if (sl.busy) {
+        HIPCHK(hipEventSynchronize(sl.done));
+        sl.busy = false;
+    }
+    out->rows = sl.rows;
+    out->range_mm = (int32_t *)(sl.host + h->so_ranges);
+    out->err_est = sl.host + h->so_err;
+    out->accel = sl.host + h->so_accel;
+    out->cov = sl.host + h->so_cov;
+    out->dt = (double *)(sl.host + h->so_dt);
+    out->status = (uint32_t *)(sl.host + h->so_status);
+    out->pos = (double *)(sl.host + h->so_pos);
+    out->capacity = h->cfg.n_tags;
+    return KFPOS_OK;
+}
+
+int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t n, double dt_shared) {
+    g_err.clear();
+    if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
+    DevScope dev_(h->cfg.device);
+    auto &sl = h->slot[slot];
+    if (!h->s_copy || sl.busy || !sl.rows) {
+        g_err = "kfpos_slot_submit_rows: acquire the slot first (kfpos_slot_acquire_rows)";
+        return KFPOS_ERR_STATE;
+    }
+    const int kind = flags & 0xff;
+    if (kind != KFPOS_SLOT_TOA && kind != KFPOS_SLOT_IMU && kind != KFPOS_SLOT_TOA_IMU) return KFPOS_ERR_ARG;
+    if (flags & (KFPOS_SLOT_REUSE_ERR | KFPOS_SLOT_REUSE_COV)) {
+        g_err = "kfpos_slot_submit_rows: KFPOS_SLOT_REUSE_* belongs to whole-bank rounds (a row-list round brings the listed tags' own values)";
+        return KFPOS_ERR_ARG;
+    }
+    if (n > h->cfg.n_tags) {
+        g_err = "kfpos_slot_submit_rows: n exceeds the slot's capacity (n_tags)";
+        return KFPOS_ERR_ARG;
+    }
+    int rc = rows_check(h, "kfpos_slot_submit_rows", sl.rows, n);
+    if (rc) return rc;
+    if (n == 0) return KFPOS_OK;
+    if (h->cfg.model == KFPOS_MODEL_PLANAR && kind != KFPOS_SLOT_TOA) return KFPOS_ERR_MODEL; /* its sensors: kfpos_step_sensor_rows */
+    const bool imu9 = h->cfg.model == KFPOS_MODEL_TOA_IMU;
+    if (kind == KFPOS_SLOT_TOA_IMU && !imu9) return KFPOS_ERR_MODEL;
+    const bool has_rng = kind != KFPOS_SLOT_IMU, has_imu = imu9 && kind != KFPOS_SLOT_TOA;
+    if (kind == KFPOS_SLOT_IMU && !imu9) { /* KalmanFilterTOA::newIMUMeasurement is empty */
+        std::memset(sl.host + h->so_status, 0, sizeof(uint32_t) * n);
+        return KFPOS_OK;
+    }
+    if (has_rng && !h->have_anchors) {
+        g_err = "kfpos_set_anchors has not been called";
+        return KFPOS_ERR_STATE;
+    }
+    if ((rc = rows_reserve(h, (size_t)n))) return rc;
+    const RowsLayout L = rows_layout(h, h->work_cap, (size_t)n);
+    unsigned char *in = h->d_work + (size_t)slot * L.in_bytes; /* this slot's input area: its last round has completed */
+    const size_t N = (size_t)n, A = h->cfg.max_anchors, m = h->msz;
+    /* 1. the listed tags' records, pinned host -> device on the copy stream: bytes proportional to n. The slot's device
+     * block is not touched: it may hold the errorEstimations / covariance a later whole-bank round reuses */
+    auto up = [&](size_t i_off, const void *src, size_t bytes) {
+        return hipMemcpyAsync(in + i_off, src, bytes, hipMemcpyHostToDevice, h->s_copy);
+    };
+    HIPCHK(up(L.i_rows, sl.rows, N * sizeof(int32_t)));
+    if (has_rng) {
+        HIPCHK(up(L.i_ranges, sl.host + h->so_ranges, N * A * sizeof(int32_t)));
+        HIPCHK(up(L.i_err, sl.host + h->so_err, N * A * m));
+    }
+    if (has_imu) {
+        HIPCHK(up(L.i_accel, sl.host + h->so_accel, N * 3 * m));
+        HIPCHK(up(L.i_cov, sl.host + h->so_cov, N * 9 * m));
+    }
+    if (flags & KFPOS_SLOT_DT_PER_TAG) HIPCHK(up(L.i_dt, sl.host + h->so_dt, N * sizeof(double)));
+    HIPCHK(hipEventRecord(sl.copied, h->s_copy));
+    /* 2. turn, gather, step, scatter on the compute stream, in submission order with the whole-bank rounds */
+    HIPCHK(hipStreamWaitEvent(h->s_comp, sl.copied, 0));
+    KArgs a;
+    fill_args(h, a);
+    auto turn = [&](size_t i_off, size_t w_off, int Cc, size_t esz) -> const void * {
+        kfpos_k::launch_rows_to_cols(esz, h->s_comp, in + i_off, h->d_work + w_off, n, Cc);
+        return h->d_work + w_off;
+    };
+    if (has_rng) {
+        a.ranges = (const int32_t *)turn(L.i_ranges, L.w_ranges, (int)A, sizeof(int32_t));
+        a.err = turn(L.i_err, L.w_err, (int)A, m);
+    }
+    if (has_imu) {
+        a.accel = turn(L.i_accel, L.w_accel, 3, m);
+        a.cov = turn(L.i_cov, L.w_cov, 9, m);
+    }
+    HIPCHK(hipGetLastError());
+    a.mode = kind == KFPOS_SLOT_TOA ? MODE_TOA : (kind == KFPOS_SLOT_IMU ? MODE_IMU_ONLY : MODE_FUSED);
+    a.latch = 1;
+    a.dt = (flags & KFPOS_SLOT_DT_PER_TAG) ? (const double *)(in + L.i_dt) : nullptr;
+    a.dt_shared = dt_shared;
+    a.status = (uint32_t *)(in + L.i_status);
+    const bool want_pose = !(flags & KFPOS_SLOT_NO_POSE);
+    a.traj = want_pose ? (double *)(in + L.i_pos) : nullptr;
+    if ((rc = rows_step(h, h->s_comp, L, (const int32_t *)(in + L.i_rows), n, a))) return rc;
+    HIPCHK(hipEventRecord(sl.computed, h->s_comp));
+    /* 3. status [n] and pos [3][n] back */
+    HIPCHK(hipStreamWaitEvent(h->s_back, sl.computed, 0));
+    HIPCHK(hipMemcpyAsync(sl.host + h->so_status, in + L.i_status, N * sizeof(uint32_t), hipMemcpyDeviceToHost, h->s_back));
+    if (want_pose) HIPCHK(hipMemcpyAsync(sl.host + h->so_pos, in + L.i_pos, N * 3 * sizeof(double), hipMemcpyDeviceToHost, h->s_back));
+    HIPCHK(hipEventRecord(sl.done, h->s_back));
+    sl.busy = true;
     return KFPOS_OK;
 }
 

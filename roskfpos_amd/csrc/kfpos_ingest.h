@@ -37,6 +37,11 @@
  * onPX4Flow, onCompass, onMag): they queue behind that tag's pending ranging epochs, so each filter sees its
  * calls in arrival order, and a round hands every kind to the GPU in one call (the IMU slot kind for the 9-state
  * filter, kfpos_step_sensor for the planar one; the 6-state filter ignores them like the reference does).
+ *
+ * setSparseRounds(true): a round is assembled as a ROW LIST instead (kfpos_slot_submit_rows, kfpos_step_sensor_rows):
+ * each call appends its row and one contiguous record, only the reporters' bytes cross the bus, and the GPU steps a
+ * compact copy of them. Same filters, bit for bit; which mode is cheaper depends on the fraction of the bank that
+ * reports per round.
  */
 #ifndef KFPOS_INGEST_H
 #define KFPOS_INGEST_H
@@ -44,6 +49,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -208,6 +214,25 @@ public:
             tags_[rows[i]] = Tag();
         }
     }
+    /* Sparse rounds (off by default): rounds go to the GPU as row lists -- see the head of this file. May be switched
+     * whenever no call is pending (right after poll()); std::logic_error otherwise. */
+    void setSparseRounds(bool on) {
+        requireIdle("setSparseRounds");
+        sparse_ = on;
+    }
+    bool sparseRounds() const { return sparse_; }
+    /* Status words, if anybody wants them: sink(row, kind, status) for every estimator call made (kind 0 = ranging
+     * epoch, KFPOS_SENSOR_* otherwise), in the order the calls were placed. A round's words are delivered when its slot
+     * is taken again, or by deliverStatuses(), which waits for everything in flight. */
+    using StatusSink = std::function<void(int row, int kind, uint32_t status)>;
+    void setStatusSink(StatusSink sink) { sink_ = std::move(sink); }
+    void deliverStatuses() {
+        for (int s = 0; s < nSlots_; ++s) {
+            if (flightKind_[s] < 0) continue;
+            check(kfpos_slot_wait(h_, s), "kfpos_slot_wait");
+            deliver(s);
+        }
+    }
     /* the row that serves tagId, -1 if none */
     int rowOf(int tagId) const { return row_.find(tagId); }
     bool bound(int row) const { return bound_[row] != 0; } /* diagnostic: does the row serve a tag at the moment */
@@ -307,6 +332,7 @@ private:
         tableBase_ = (unsigned char *)(((uintptr_t)table_.get() + 63) & ~(uintptr_t)63);
         taken_.assign(T_, 0);
         for (int k = 0; k < 5; ++k) roundSlot_[k] = -1;
+        for (int s = 0; s < kMaxSlots; ++s) flightKind_[s] = -1;
         if (dim_ == 8) { /* planar filter: its other four sensors go through the synchronous kfpos_step_sensor */
             for (int k = 1; k <= 4; ++k) sens_[k].assign((size_t)T_ * sensorWidth(k), 0.0);
             sensDt_.assign(T_, -1.0);
@@ -418,21 +444,41 @@ private:
         }
     }
 
-    /* the slot (pinned, component-major) that collects this round's calls of `kind` */
-    kfpos_epoch_slot &slotFor(int kind) {
+    /* the slot (pinned; component-major, or in sparse mode row-major per listed tag) that collects this round's calls
+     * of `kind` */
+    int slotFor(int kind) {
         if (roundSlot_[kind] < 0) {
             const int s = nextSlot_++ % nSlots_;
-            check(kfpos_slot_acquire(h_, s, &slot_[s]), "kfpos_slot_acquire"); /* waits for its previous round */
-            if (!slotInit_[s]) {
-                for (int t = 0; t < T_; ++t) slot_[s].dt[t] = -1.0;
-                slotInit_[s] = true;
+            if (sparse_) { /* no dt = -1 fill, nothing to undo: the list says who is in the round */
+                check(kfpos_slot_acquire_rows(h_, s, &rslot_[s]), "kfpos_slot_acquire_rows"); /* waits for its previous round */
+                deliver(s);
+                rowsN_[s] = 0;
+                slotInit_[s] = false; /* its dt array no longer holds -1 everywhere */
             } else {
-                for (int t : written_[s]) slot_[s].dt[t] = -1.0;
+                check(kfpos_slot_acquire(h_, s, &slot_[s]), "kfpos_slot_acquire"); /* waits for its previous round */
+                deliver(s);
+                if (!slotInit_[s]) {
+                    for (int t = 0; t < T_; ++t) slot_[s].dt[t] = -1.0;
+                    slotInit_[s] = true;
+                } else {
+                    for (int t : written_[s]) slot_[s].dt[t] = -1.0;
+                }
             }
             written_[s].clear();
             roundSlot_[kind] = s;
         }
-        return slot_[roundSlot_[kind]];
+        return roundSlot_[kind];
+    }
+    /* the status words of the round slot s carried last (it has completed) */
+    void deliver(int s) {
+        if (flightKind_[s] < 0) return;
+        if (sink_) {
+            if (flightSparse_[s])
+                for (int i = 0; i < rowsN_[s]; ++i) sink_(rslot_[s].rows[i], flightKind_[s], rslot_[s].status[i]);
+            else
+                for (int t : written_[s]) sink_(t, flightKind_[s], slot_[s].status[t]);
+        }
+        flightKind_[s] = -1;
     }
 
     /* one call of one tag into the round being assembled */
@@ -441,8 +487,31 @@ private:
         touched_.push_back(row);
         ++roundCalls_;
         const size_t T = (size_t)T_;
-        if (kind == 0) {
-            kfpos_epoch_slot &sl = slotFor(0);
+        if (sparse_ && (kind == 0 || dim_ == 9)) { /* append the row and ONE contiguous record */
+            const int s = slotFor(kind == 0 ? 0 : KFPOS_SENSOR_IMU);
+            kfpos_rows_slot &sl = rslot_[s];
+            const size_t i = (size_t)rowsN_[s]++;
+            sl.rows[i] = row;
+            sl.dt[i] = lag;
+            if (kind == 0) {
+                int32_t *r = sl.range_mm + i * A_;
+                for (int a = 0; a < A_; ++a) r[a] = mm[a] > 0 ? mm[a] : 0; /* only entries > 0 (:483) */
+                if (real_ == 4) {
+                    float *e = (float *)sl.err_est + i * A_;
+                    for (int a = 0; a < A_; ++a) e[a] = (float)err[a];
+                } else {
+                    std::memcpy((double *)sl.err_est + i * A_, err, sizeof(double) * A_);
+                }
+            } else if (real_ == 4) {
+                float *ac = (float *)sl.accel + i * 3, *cv = (float *)sl.cov + i * 9;
+                for (int k = 0; k < 3; ++k) ac[k] = (float)sample[12 + k];
+                for (int k = 0; k < 9; ++k) cv[k] = (float)sample[15 + k];
+            } else {
+                std::memcpy((double *)sl.accel + i * 3, sample + 12, sizeof(double) * 3);
+                std::memcpy((double *)sl.cov + i * 9, sample + 15, sizeof(double) * 9);
+            }
+        } else if (kind == 0) {
+            kfpos_epoch_slot &sl = slot_[slotFor(0)];
             for (int a = 0; a < A_; ++a) sl.range_mm[(size_t)a * T + row] = mm[a] > 0 ? mm[a] : 0; /* only entries > 0 (:483) */
             if (real_ == 4) {
                 float *e = (float *)sl.err_est;
@@ -454,7 +523,7 @@ private:
             sl.dt[row] = lag;
             written_[roundSlot_[0]].push_back(row);
         } else if (dim_ == 9) { /* KalmanFilterTOAIMU::newIMUMeasurement: acceleration + its covariance */
-            kfpos_epoch_slot &sl = slotFor(KFPOS_SENSOR_IMU);
+            kfpos_epoch_slot &sl = slot_[slotFor(KFPOS_SENSOR_IMU)];
             if (real_ == 4) {
                 float *ac = (float *)sl.accel, *cv = (float *)sl.cov;
                 for (int k = 0; k < 3; ++k) ac[(size_t)k * T + row] = (float)sample[12 + k];
@@ -466,9 +535,10 @@ private:
             }
             sl.dt[row] = lag;
             written_[roundSlot_[KFPOS_SENSOR_IMU]].push_back(row);
-        } else { /* planar filter: the sample as the reference callback passes it */
+        } else { /* planar filter: the sample as the reference callback passes it; sparse: one record per listed tag */
             const int C = sensorWidth(kind);
-            std::memcpy(&sens_[kind][(size_t)row * C], sample, sizeof(double) * C);
+            const size_t at = sparse_ ? sensRows_[kind].size() : (size_t)row;
+            std::memcpy(&sens_[kind][at * C], sample, sizeof(double) * C);
             if (sensRows_[kind].empty()) sensKinds_.push_back(kind);
             sensRows_[kind].push_back(row);
             sensLag_[kind].push_back(lag);
@@ -477,20 +547,35 @@ private:
 
     /* hand the assembled round to the GPU: one submission per kind present */
     void submitRound() {
-        if (roundSlot_[0] >= 0) {
-            check(kfpos_slot_submit(h_, roundSlot_[0], KFPOS_SLOT_TOA | KFPOS_SLOT_DT_PER_TAG | KFPOS_SLOT_NO_POSE, 0.0),
-                  "kfpos_slot_submit");
-            roundSlot_[0] = -1;
-        }
-        if (roundSlot_[KFPOS_SENSOR_IMU] >= 0) {
-            check(kfpos_slot_submit(h_, roundSlot_[KFPOS_SENSOR_IMU], KFPOS_SLOT_IMU | KFPOS_SLOT_DT_PER_TAG | KFPOS_SLOT_NO_POSE, 0.0),
-                  "kfpos_slot_submit");
-            roundSlot_[KFPOS_SENSOR_IMU] = -1;
+        static const int kSlotKind[2][2] = {{0, KFPOS_SLOT_TOA}, {KFPOS_SENSOR_IMU, KFPOS_SLOT_IMU}};
+        for (const auto &k : kSlotKind) {
+            const int s = roundSlot_[k[0]];
+            if (s < 0) continue;
+            const int flags = k[1] | KFPOS_SLOT_DT_PER_TAG | KFPOS_SLOT_NO_POSE;
+            if (sparse_) check(kfpos_slot_submit_rows(h_, s, flags, rowsN_[s], 0.0), "kfpos_slot_submit_rows");
+            else check(kfpos_slot_submit(h_, s, flags, 0.0), "kfpos_slot_submit");
+            flightKind_[s] = k[0];
+            flightSparse_[s] = sparse_;
+            roundSlot_[k[0]] = -1;
         }
         for (int kind : sensKinds_) { /* planar sensors: synchronous (the call waits for the slots first) */
-            for (size_t i = 0; i < sensRows_[kind].size(); ++i) sensDt_[sensRows_[kind][i]] = sensLag_[kind][i];
-            check(kfpos_step_sensor(h_, kind, sens_[kind].data(), sensDt_.data(), T_, nullptr), "kfpos_step_sensor");
-            for (int r : sensRows_[kind]) sensDt_[r] = -1.0;
+            const std::vector<int> &rows = sensRows_[kind];
+            const int n = (int)rows.size();
+            uint32_t *st = nullptr;
+            if (sink_) {
+                sensSt_.resize((size_t)T_);
+                st = sensSt_.data();
+            }
+            if (sparse_) { /* no [T x C] staging: the samples lie one record per listed tag */
+                check(kfpos_step_sensor_rows(h_, rows.data(), n, kind, sens_[kind].data(), sensLag_[kind].data(), n, st),
+                      "kfpos_step_sensor_rows");
+            } else {
+                for (int i = 0; i < n; ++i) sensDt_[rows[i]] = sensLag_[kind][i];
+                check(kfpos_step_sensor(h_, kind, sens_[kind].data(), sensDt_.data(), T_, st), "kfpos_step_sensor");
+                for (int r : rows) sensDt_[r] = -1.0;
+            }
+            if (sink_)
+                for (int i = 0; i < n; ++i) sink_(rows[i], kind, st[sparse_ ? i : rows[i]]);
             sensRows_[kind].clear();
             sensLag_[kind].clear();
         }
@@ -549,6 +634,16 @@ private:
     static constexpr int kMaxSlots = 8;
     int nSlots_ = 2;
     kfpos_epoch_slot slot_[kMaxSlots];
+    /* sparse rounds: the same slots as row lists, and how many rows the round in each holds */
+    static_assert(sizeof(int) == sizeof(int32_t), "row lists are int32_t");
+    bool sparse_ = false;
+    kfpos_rows_slot rslot_[kMaxSlots];
+    int rowsN_[kMaxSlots] = {0};
+    /* what each slot has in flight (kind, -1 = nothing to deliver; assembled as a row list?) and who listens */
+    int flightKind_[kMaxSlots];
+    bool flightSparse_[kMaxSlots] = {false};
+    StatusSink sink_;
+    std::vector<uint32_t> sensSt_;
     bool slotInit_[kMaxSlots] = {false};
     std::vector<int> written_[kMaxSlots];
     int roundSlot_[5];

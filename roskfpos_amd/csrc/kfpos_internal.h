@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/kfpos.h"
 
@@ -81,11 +82,20 @@ struct kfpos_handle {
          * sensor covariance: an upload into those regions waits for it, whichever slot holds the current ones by then */
         hipEvent_t err_reader = nullptr, cov_reader = nullptr;
         bool busy = false;
+        int32_t *rows = nullptr; /* pinned [n_tags]: the row list of a row-list round (kfpos_slot_acquire_rows) */
     } slot[KFPOS_N_SLOTS];
     size_t so_ranges = 0, so_err = 0, so_accel = 0, so_cov = 0, so_dt = 0, so_status = 0, so_pos = 0, so_bytes = 0;
     hipStream_t s_copy = nullptr, s_copy2 = nullptr, s_comp = nullptr, s_back = nullptr;
     size_t split_bytes = 0;                            /* H2D copies from this size on travel as two halves on two streams */
     int err_slot = -1, cov_slot = -1;                  /* which slot's device block holds the current err / cov */
+    /* row-list steps (kfpos_step_*_rows, kfpos_slot_submit_rows): one device block, allocated on first use, grown to the
+     * largest n seen (never beyond n_tags): KFPOS_N_SLOTS input areas -- what a round uploads (rows, row-major inputs,
+     * dt) and returns (status, pos); fixed places, since the copy stream runs ahead of the compute stream -- followed by
+     * the work bank: the listed tags' state and the turned inputs at stride n, used on one stream in submission order */
+    unsigned char *d_work = nullptr;
+    size_t work_cap = 0;                               /* listed tags it holds */
+    std::vector<uint32_t> row_stamp;                   /* [n_tags] host: the call that last listed a row (duplicate check in O(n)) */
+    uint32_t stamp = 0;
 };
 
 #endif /* KFPOS_INTERNAL_H */

@@ -1,6 +1,8 @@
 /*
  * kfpos_k_tags.hip -- per-tag lifecycle kernels (kfpos_get_tags / kfpos_set_tags / kfpos_reset_tags): read, write or
- * re-initialise the filters of a LIST of tags, at a cost that follows the length of the list and not the size of the bank.
+ * re-initialise the filters of a LIST of tags, at a cost that follows the length of the list and not the size of the bank;
+ * and the gather / scatter between the bank and the compact work bank on which a row-list step (kfpos_step_*_rows,
+ * kfpos_slot_submit_rows) runs the unchanged step kernels (k_rows_work, below).
  *
  * Work item = one (listed tag, component). The staging side is row-major per listed tag, section after section
  * (x | P | latch | height, the formats of kfpos_get_state / kfpos_get_latch / kfpos_get_height), and work item g reads
@@ -89,8 +91,51 @@ __global__ __launch_bounds__(256) void k_tags_reset(const TagArgs a) {
     else if (d.kind == kfpos_k::TC_REAL) strow<MREAL>(a.buf[d.buf], d.row, T, t, v);
 }
 
+/* ---- the work bank of a row-list step: stored bits of the listed tags, bank <-> work, no decode ----
+ * Grid: x = 256 listed tags (tag index fastest: the work side, stride n, is fully coalesced), y = stored row of
+ * comp[] (block-uniform), the last y = the flags word. The bank side is one scattered 2-8 byte access per item. */
+template <typename E, bool TO_BANK>
+__device__ inline void raw_move(void *bank, void *work, size_t row, size_t T, size_t n, uint32_t t, uint32_t i) {
+    E *b = ((E *)bank) + row * T, *w = ((E *)work) + row * n;
+    if (TO_BANK) b[t] = w[i];
+    else w[i] = b[t];
+}
+template <typename REAL, typename MREAL, bool TO_BANK>
+__global__ __launch_bounds__(256) void k_rows_work(const TagArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (uint32_t)a.n) return;
+    const uint32_t t = (uint32_t)a.rows[i];
+    const size_t T = a.T, n = a.n;
+    const int c = blockIdx.y;
+    if (c == a.n_comp) {
+        raw_move<uint32_t, TO_BANK>(a.flags, a.wflags, 0, T, n, t, i);
+        return;
+    }
+    const TagComp d = a.comp[c];
+    void *bank = a.buf[d.buf], *work = a.wbuf[d.buf];
+    using RAWM = std::conditional_t<sizeof(MREAL) == 4, uint32_t, uint64_t>;
+    if (d.kind == kfpos_k::TC_F64) raw_move<uint64_t, TO_BANK>(bank, work, d.row, T, n, t, i);
+    else if (d.kind == kfpos_k::TC_REAL) raw_move<RAWM, TO_BANK>(bank, work, d.row, T, n, t, i);
+    else if (d.kind == kfpos_k::TC_COV) {
+        if constexpr (std::is_same<REAL, p48>::value) { /* both planes: [psz][.] uint32, then [psz][.] uint16 */
+            raw_move<uint32_t, TO_BANK>(bank, work, d.row, T, n, t, i);
+            raw_move<uint16_t, TO_BANK>(((uint32_t *)bank) + (size_t)a.psz * T, ((uint32_t *)work) + (size_t)a.psz * n,
+                                        d.row, T, n, t, i);
+        } else {
+            using RAWC = std::conditional_t<sizeof(REAL) == 4, uint32_t, uint64_t>;
+            raw_move<RAWC, TO_BANK>(bank, work, d.row, T, n, t, i);
+        }
+    }
+}
+
 template <typename REAL, typename MREAL>
 void launch_tags_as(int op, int blocks, hipStream_t s, const TagArgs &a) {
+    if (op == kfpos_k::TAGS_WORK_IN || op == kfpos_k::TAGS_WORK_OUT) {
+        const dim3 grid((a.n + 255) / 256, a.n_comp + 1);
+        if (op == kfpos_k::TAGS_WORK_IN) hipLaunchKernelGGL((k_rows_work<REAL, MREAL, false>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_rows_work<REAL, MREAL, true>), grid, dim3(256), 0, s, a);
+        return;
+    }
     if (op == kfpos_k::TAGS_GATHER) hipLaunchKernelGGL((k_tags_gather<REAL, MREAL>), dim3(blocks), dim3(256), 0, s, a);
     else if (op == kfpos_k::TAGS_SCATTER) hipLaunchKernelGGL((k_tags_scatter<REAL, MREAL>), dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_tags_reset<REAL, MREAL>), dim3(blocks), dim3(256), 0, s, a);
@@ -100,7 +145,7 @@ void launch_tags_as(int op, int blocks, hipStream_t s, const TagArgs &a) {
 
 void kfpos_k::launch_tags(int op, int st, hipStream_t s, const TagArgs &a) {
     size_t items = a.n;
-    if (op == TAGS_RESET) {
+    if (op == TAGS_RESET || op == TAGS_WORK_IN || op == TAGS_WORK_OUT) {
         if ((size_t)a.n * a.n_comp > items) items = (size_t)a.n * a.n_comp;
     } else {
         size_t w = 0;

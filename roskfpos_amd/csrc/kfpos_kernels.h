@@ -25,7 +25,7 @@
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
  * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_misc (8-state planar
- * filter, standalone ML estimator, getPose, layout turns), kfpos_k_tags (per-tag gather / scatter / reset), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
+ * filter, standalone ML estimator, getPose, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
 #define KFPOS_KERNELS_H
@@ -120,7 +120,7 @@ struct TagComp {
 };
 enum : int { TC_NONE = 0, TC_F64 = 1, TC_COV = 2, TC_REAL = 3 };                 /* double / stored covariance entry / kfpos_real */
 enum : int { TB_POS = 0, TB_VEL, TB_P, TB_IMU_ACC, TB_IMU_COV, TB_LATCH, TB_N }; /* TagArgs::buf */
-enum : int { TAGS_GATHER = 0, TAGS_SCATTER = 1, TAGS_RESET = 2 };
+enum : int { TAGS_GATHER = 0, TAGS_SCATTER = 1, TAGS_RESET = 2, TAGS_WORK_IN = 3, TAGS_WORK_OUT = 4 };
 constexpr int TAG_SECTIONS = 4;            /* x | P | latch | height */
 constexpr int TAG_COMPS = 9 + 81 + 15 + 1; /* the longest record: no model has all of them at once */
 struct TagArgs {
@@ -135,9 +135,14 @@ struct TagArgs {
     uint32_t *fl;             /* staging: [n] flags words, or null */
     const double *init;       /* reset: [n][3] start positions, or null = cst[0..2] */
     double cst[5];            /* reset: start position x y z (NaN: ML initialisation), planar height, planar angle */
+    void *wbuf[TB_N];         /* TAGS_WORK_IN / _OUT: the work bank, the same arrays as buf[] at stride n (row-list steps) */
+    uint32_t *wflags;         /* [n] */
     TagComp comp[TAG_COMPS];
 };
 void launch_tags(int op, int st, hipStream_t s, const TagArgs &a);          /* kfpos_k_tags.hip */
+/* TAGS_WORK_IN: work[c][i] = bank[c][rows[i]] for every stored row c listed in comp[] (n_comp of them, the list reset
+ * uses) and the flags word, raw stored bits; TAGS_WORK_OUT: the inverse. The step kernels then run on the work bank
+ * with KArgs::T = n: they never see a row index. */
 
 constexpr int COOP_LANES = 8;                   /* kfpos_k_coop.hip: one tag per group of 8 lanes */
 constexpr int COOP_TAGS_PER_WAVE = 64 / COOP_LANES;

@@ -11,7 +11,12 @@
             memcpy: the producer, not the library, is the bound here)
   reuse     `slots` with KFPOS_SLOT_REUSE_ERR | KFPOS_SLOT_REUSE_COV (constant errorEstimation / sensor covariance)
 
-    python tools/hostbench.py [--tags 65536] [--steps 60]
+  --sparse F  adds the row-list entry points for a round in which a fraction F of the tags reports (rows spread over
+            the bank): `rows_sync` = kfpos_step_*_rows from pageable arrays, `rows_slots` = kfpos_slot_submit_rows
+            pipelined over the slots, the listed records already in the slot. Off by default: the output is then
+            what it always was
+
+    python tools/hostbench.py [--tags 65536] [--steps 60] [--sparse 0.05]
 """
 import argparse
 import json
@@ -30,6 +35,7 @@ ap.add_argument("--tags", type=int, default=65536)
 ap.add_argument("--steps", type=int, default=60)
 ap.add_argument("--model", type=int, default=1)
 ap.add_argument("--modes", default="sync,slots,reuse,nopose,fill,fillreuse")
+ap.add_argument("--sparse", type=float, default=None, metavar="F")
 a = ap.parse_args()
 MODES = set(a.modes.split(","))
 T, A, S = a.tags, 8, a.steps
@@ -124,5 +130,44 @@ if "fill" in MODES:
     out["slots_with_cpu_fill"] = stream(fill=True, reuse=False)
 if "fillreuse" in MODES:
     out["slots_with_cpu_fill_reuse"] = stream(fill=True, reuse=True)
+if a.sparse is not None:
+    n = max(1, min(T, int(round(a.sparse * T))))
+    rows = np.sort(np.random.default_rng(1).choice(T, size=n, replace=False)).astype(np.int32)  # spread over the bank
+    part = [(r[rows], ac[rows]) for r, ac, _ in inputs]
+    err_n, cov_n = err[rows], cov[rows]
+    bank = new_bank()
+    bank.step_toa_imu(*inputs[0][:1], err, inputs[0][1], cov, 0.1) if imu else bank.step_toa(inputs[0][0], err, 0.1)
+
+    def rows_call(s):
+        r, ac = part[s % NPRE]
+        bank.step_toa_imu_rows(rows, r, err_n, ac, cov_n, 0.05) if imu else bank.step_toa_rows(rows, r, err_n, 0.05)
+
+    for s in range(3):
+        rows_call(s)
+    t0 = time.perf_counter()
+    for s in range(S):
+        rows_call(s)
+    el = time.perf_counter() - t0
+    out["rows_sync"] = {"fraction": a.sparse, "rows": n, "ms_per_step_call": el / S * 1e3, "tag_steps_per_s": n * S / el}
+    NS = bank.lib.kfpos_slot_count(bank._h)
+    kind = capi.SLOT_TOA_IMU if imu else capi.SLOT_TOA
+    for k in range(NS):             # every slot holds a complete row-list round
+        v = bank.slot_acquire_rows(k)
+        v["rows"][:n] = rows
+        v["range_mm"][:n], v["accel"][:n] = part[k]
+        v["err_est"][:n], v["cov"][:n] = err_n, cov_n
+    for s in range(2 * NS):
+        bank.slot_acquire_rows(s % NS)
+        bank.slot_submit_rows(s % NS, kind, n, 0.05)
+    t0 = time.perf_counter()
+    for s in range(S):
+        bank.slot_acquire_rows(s % NS)
+        bank.slot_submit_rows(s % NS, kind, n, 0.05)
+    for k in range(NS):
+        bank.slot_wait(k)
+    el = time.perf_counter() - t0
+    assert np.isfinite(bank.get_state()[0]).all()
+    bank.close()
+    out["rows_slots"] = {"fraction": a.sparse, "rows": n, "ms_per_epoch": el / S * 1e3, "tag_steps_per_s": n * S / el}
 out["env"] = {k: os.environ[k] for k in ("HSA_ENABLE_SDMA", "GPU_FORCE_BLIT_COPY_SIZE", "HIP_FORCE_DEV_KERNARG") if k in os.environ}
 print(json.dumps(out))

@@ -6,7 +6,10 @@
  * triggers, written straight into the pinned slot) and poll (timers + submitting the round); the GPU works on round r
  * while the CPU ingests epoch r + 1. Prints one JSON line.
  *   g++ -O2 -std=c++17 -I include -I roskfpos_amd/csrc -o ingestbench tools/ingestbench.cpp -L roskfpos_amd/csrc -lkfpos_hip
- *   ./ingestbench [tags] [epochs] [model 0|1] [batch]
+ *   ./ingestbench [tags] [epochs] [model 0|1] [batch] [--sparse] [--reporters PCT]
+ * --sparse: rounds are assembled as row lists (BatchedRangingNode::setSparseRounds); --reporters PCT: only PCT percent of
+ * the tags (spread over the bank) speak, the same ones in every epoch. Either option adds its fields to the JSON line;
+ * without them the run and the line are what they always were.
  */
 #include <algorithm>
 #include <chrono>
@@ -25,6 +28,19 @@ static double now_s() {
 }
 
 int main(int argc, char **argv) {
+    bool sparse = false;
+    int reporters = 100;
+    {
+        int keep = 1; /* options out, positional arguments stay where they were */
+        for (int i = 1; i < argc; ++i) {
+            if (!std::strcmp(argv[i], "--sparse")) sparse = true;
+            else if (!std::strcmp(argv[i], "--reporters") && i + 1 < argc) reporters = std::atoi(argv[++i]);
+            else argv[keep++] = argv[i];
+        }
+        argc = keep;
+        if (reporters < 1 || reporters > 100) { std::fprintf(stderr, "--reporters: 1..100\n"); return 1; }
+    }
+    const bool extra = sparse || reporters != 100;
     const int T = argc > 1 ? std::atoi(argv[1]) : 65536, K = argc > 2 ? std::atoi(argv[2]) : 12;
     const int model = argc > 3 ? std::atoi(argv[3]) : 0;
     const size_t batch = argc > 4 ? (size_t)std::atol(argv[4]) : 4096;
@@ -46,14 +62,17 @@ int main(int argc, char **argv) {
     kfpos_set_anchors(h, xyz, anchorIds.data(), A);
     for (int t = 0; t < T; ++t) tagIds.push_back(0x1000 + 3 * t); /* sparse ids */
     BatchedRangingNode node(h, tagIds, anchorIds);
+    if (sparse) node.setSparseRounds(true);
     /* one epoch of messages, re-stamped per epoch: tag k sits at (5 + cos k, 5 + sin k, 1) */
-    std::vector<RangingMsg> msgs((size_t)T * A);
+    std::vector<RangingMsg> msgs;
+    msgs.reserve((size_t)T * A);
     for (int a = 0; a < A; ++a)
         for (int t = 0; t < T; ++t) {
+            if (t % 100 >= reporters) continue;
             const double px = 5 + std::cos(0.001 * t), py = 5 + std::sin(0.001 * t), pz = 1.0;
             const double d = std::sqrt((px - xyz[3 * a]) * (px - xyz[3 * a]) + (py - xyz[3 * a + 1]) * (py - xyz[3 * a + 1]) +
                                        (pz - xyz[3 * a + 2]) * (pz - xyz[3 * a + 2]));
-            msgs[(size_t)a * T + t] = RangingMsg{0.0, 100 + a, 0x1000 + 3 * t, d * 1000.0 + (t % 7), 0.0025, 0};
+            msgs.push_back(RangingMsg{0.0, 100 + a, 0x1000 + 3 * t, d * 1000.0 + (t % 7), 0.0025, 0});
         }
     double t_ingest = 0, t_poll = 0;
     int calls = 0;
@@ -79,10 +98,12 @@ int main(int argc, char **argv) {
     std::printf("{\"tags\": %d, \"anchors\": %d, \"model\": %d, \"epochs\": %d, \"messages\": %.0f, \"batch\": %zu, "
                 "\"ingest_Mmsg_per_s\": %.2f, \"ingest_ms_per_epoch\": %.3f, \"poll_ms_per_epoch\": %.3f, "
                 "\"end_to_end_Mmsg_per_s\": %.2f, \"end_to_end_ms_per_epoch\": %.3f, \"estimator_calls\": %d, "
-                "\"overflow_calls\": %llu, \"pose0\": [%.4f, %.4f, %.4f], \"realtime_factor_at_20Hz\": %.2f}\n",
+                "\"overflow_calls\": %llu, \"pose0\": [%.4f, %.4f, %.4f], \"realtime_factor_at_20Hz\": %.2f",
                 T, A, model, K, n, batch, n / t_ingest / 1e6, t_ingest / K * 1e3, t_poll / K * 1e3, n / wall / 1e6,
                 wall / K * 1e3, calls, (unsigned long long)node.overflowCalls(), pos[0], pos[1], pos[2],
                 0.05 / (wall / K));
+    if (extra) std::printf(", \"sparse\": %s, \"reporters_pct\": %d", sparse ? "true" : "false", reporters);
+    std::printf("}\n");
     kfpos_destroy(h);
     return 0;
 }
