@@ -830,21 +830,34 @@ struct CovPark9 {
     int stride;
 };
 
+/* The step in two parts, so that a caller can act between them (the kernel stores the pose there: it is final, and the
+ * covariance update -- 630 instructions without a memory access -- covers the store):
+ *   step_imu9_state  everything up to the updated position and velocity. false: the step is over, `status` is its
+ *                    status word (ML initialisation, too few ranges, update skipped); true: step_imu9_cov is still due.
+ *   step_imu9_cov    the covariance update; returns the status word.
+ * diag: the accelerometer covariance is diagonal -- Sigma^-1 of this tag has exact zeros off its diagonal -- so the gain
+ * iteration takes the DIAG form of its pass: same operations on the same numbers in the same order, minus the terms that
+ * are exact zeros, i.e. the same bits (the kernel decides once per launch and per wavefront; false is always right). */
 template <bool RANGING, class SC>
-KFPOS_FN uint32_t step_imu9(Tag9 &tg, SC &sc, const Params &pr, double dt, const Imu &imu, const CovPark9 &park) {
+KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, const Imu &imu, const CovPark9 &park,
+                              bool diag, Iekf9Out &o, uint32_t &status) {
     constexpr bool has_ranging = RANGING;
     const int n_valid = has_ranging ? count_used(sc, pr, 0) : 0;
     if (!pr.use_init_pos && (isnan(tg.pos[0]) || isnan(tg.pos[1]))) { /* :121-122, z is not tested */
-        if (!has_ranging) return 0;
-        if (n_valid < 4) return ST_FEW_RANGES;
+        status = 0;
+        if (!has_ranging) return false;
+        status = ST_FEW_RANGES;
+        if (n_valid < 4) return false;
         double p[3] = {1.0, 1.0, 4.0}, sse, c[6];
         set_weights_ml(sc, pr, 0ull);
         const int it = ml_estimate(p, sc, pr, 0, n_valid, sse);
-        if (ml_covariance_throws(sc, pr, 0, n_valid, sse)) return ST_UPDATE_SKIPPED; /* reference: abort */
-        if (!ml_covariance(p, sc, pr, sse, c)) return ST_UPDATE_SKIPPED;
+        status = ST_UPDATE_SKIPPED;
+        if (ml_covariance_throws(sc, pr, 0, n_valid, sse)) return false; /* reference: abort */
+        if (!ml_covariance(p, sc, pr, sse, c)) return false;
         tg.pos[0] = p[0]; tg.pos[1] = p[1]; tg.pos[2] = p[2];
         tg.P(0, 0) = c[0]; tg.P(0, 1) = c[1]; tg.P(1, 1) = c[3]; /* xy block only, :134-137 */
-        return pack_status(ST_ML_INIT, 0, it, -1);
+        status = pack_status(ST_ML_INIT, 0, it, -1);
+        return false;
     }
     const double c = dt * dt / 2;
     double xhat[9];
@@ -871,25 +884,27 @@ KFPOS_FN uint32_t step_imu9(Tag9 &tg, SC &sc, const Params &pr, double dt, const
     /* B safely invertible on every lane: the information-form iteration (the usual case); otherwise -- right after a
      * fixed start, B is singular -- the (I + M B) form */
     const bool invertible = sym6_inverse(B, binv, park.stride, INFO_FORM_MIN_PIVOT);
-    Iekf9Out o;
     iekf9_weights(xhat, sc, pr, has_ranging, n_valid, o); /* position + epoch only */
     /* The 9-state filter has no try/catch: the reference node aborts here. This core keeps the predicted
      * covariance and reports the tag instead. */
     if (o.flags & ST_UPDATE_SKIPPED) {
         KFPOS_UNROLL
         for (int k = 0; k < 45; ++k) tg.P.a[k] = park.a[k * park.stride];
-        return ST_UPDATE_SKIPPED;
+        status = ST_UPDATE_SKIPPED;
+        return false;
     }
     /* per lane, not per wavefront: a tag's arithmetic must not depend on its wave-mates (a wavefront whose lanes
      * disagree runs both forms one after the other, each under its lanes' mask) */
     if (invertible) {
-        iekf9_info<false, RANGING, true>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
+        if (diag) iekf9_info<true, RANGING, true>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
+        else iekf9_info<false, RANGING, true>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
         KFPOS_UNROLL
         for (int k = 0; k < 45; ++k) tg.P.a[k] = park.a[k * park.stride];
     } else {
         KFPOS_UNROLL
         for (int k = 0; k < 45; ++k) tg.P.a[k] = park.a[k * park.stride];
-        iekf9<false, RANGING>(xhat, tg.P, sc, pr, imu, 20, 1e-4, o);
+        if (diag) iekf9<true, RANGING>(xhat, tg.P, sc, pr, imu, 20, 1e-4, o);
+        else iekf9<false, RANGING>(xhat, tg.P, sc, pr, imu, 20, 1e-4, o);
     }
     KFPOS_UNROLL
     for (int i = 0; i < 6; ++i) { /* x = xhat + P E' w: position and velocity are what the filter keeps (:189-194) */
@@ -899,8 +914,19 @@ KFPOS_FN uint32_t step_imu9(Tag9 &tg, SC &sc, const Params &pr, double dt, const
         if (i < 3) tg.pos[i] = xhat[i] + v;
         else tg.vel[i - 3] = xhat[i] + v;
     }
+    status = 0;
+    return true;
+}
+KFPOS_FN uint32_t step_imu9_cov(Tag9 &tg, const Iekf9Out &o, const Imu &imu) {
     cov_update9(tg.P, o.mrlast, o.dlast, imu);
     return pack_status(o.flags, o.gain_iters, o.ml_iters, -1);
+}
+template <bool RANGING, class SC>
+KFPOS_FN uint32_t step_imu9(Tag9 &tg, SC &sc, const Params &pr, double dt, const Imu &imu, const CovPark9 &park) {
+    Iekf9Out o;
+    uint32_t status;
+    if (!step_imu9_state<RANGING>(tg, sc, pr, dt, imu, park, false, o, status)) return status;
+    return step_imu9_cov(tg, o, imu);
 }
 
 /* getPose (KalmanFilterTOAIMU.cpp:476-510): predicted position / velocity and the position block */

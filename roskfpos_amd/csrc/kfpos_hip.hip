@@ -54,6 +54,7 @@ void fill_args(const kfpos_handle *h, KArgs &a) {
     a.top_n = h->cfg.top_n;
     a.ml_variant = h->cfg.model == KFPOS_MODEL_ML ? h->cfg.ml_variant : 0;
     a.pair9 = h->pair9 ? 1 : 0;
+    a.imu9_diag = h->imu9_diag ? 1 : 0;
     a.use_init_pos = h->cfg.use_init_pos;
     a.use_fixed_height = h->planar.use_fixed_height;
     a.imu_fixed_cov_acc = h->planar.imu_use_fixed_cov_acc;
@@ -368,6 +369,8 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
         }
         const char *np = getenv("KFPOS_PAIR9");
         h->pair9 = np && np[0] == '1';
+        const char *nd = getenv("KFPOS_IMU9_DIAG");
+        h->imu9_diag = !(nd && nd[0] == '0');
         const char *nc = getenv("KFPOS_NO_COOP");
         /* up to 8 192 tags (1024 groups-of-8 wavefronts = one per SIMD) 8 lanes per tag pay off: 4.4-5.0 us per epoch
          * against 7.5 us; at 16 384 the one-tag-per-lane grid wins again (7.7 vs 8.3 us, measured) */

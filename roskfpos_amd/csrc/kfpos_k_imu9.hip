@@ -53,9 +53,13 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
     constexpr bool AHEAD = sizeof(MREAL) == 4 && !std::is_same<REAL, float>::value;
     const bool fresh_imu = a.mode != MODE_TOA;
     constexpr int NA = AS > 0 ? AS : 1;
-    if (a.n_steps == 1 && a.dt && a.dt[t32] < 0.0) { /* no epoch / sample for this tag in this call */
-        skipped_lane(a, t, true);
-        return;
+    double dt_tag = a.dt_shared; /* the dt of a single-epoch call */
+    if (a.n_steps == 1 && a.dt) {
+        dt_tag = a.dt[t32];
+        if (dt_tag < 0.0) { /* no epoch / sample for this tag in this call */
+            skipped_lane(a, t, true);
+            return;
+        }
     }
 
     /* load order = order of first use (see k_step_toa6): flags, epoch, position, velocity, IMU sample, then the
@@ -114,30 +118,68 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
         if (a.latch) latch_imu_cov<MREAL>(a, T, t32, cv);
     }
     if (imu.has) imu_whitener(cv, imu.ci, imu.ci_stride);
+    /* Diagonal accelerometer covariance (what IMU drivers publish): the gain iteration then runs the diagonal form of its
+     * pass, which leaves out terms that are exact zeros -- the same bits for every tag. Decided once per launch (the
+     * whitener is per launch) and per wavefront: every lane's COMPUTED Sigma^-1 has zeros off its diagonal (a lane
+     * without a sample never looks at it). KFPOS_IMU9_DIAG=0 forces the full form (tests, A/B runs). */
+    bool diag = false;
+    if (a.imu9_diag) {
+        const bool mine = !imu.has || (imu.Wi(1) == 0.0 && imu.Wi(2) == 0.0 && imu.Wi(4) == 0.0);
+        diag = __builtin_amdgcn_ballot_w64(mine) == __builtin_amdgcn_ballot_w64(true);
+    }
 
+    /* dt: in a multi-epoch launch it is wave-uniform and sits in the kernel arguments -- read one epoch ahead with a
+     * scalar load, so that the epoch loop holds no vector load (and no vmcnt wait) for it; the per-tag dt of a
+     * single-epoch call was read at the top */
+    const bool multi = a.n_steps > 1; /* wave-uniform */
+    double dt_next = multi ? a.dt_steps[0] : dt_tag;
+    /* the accelerometer sample of the next epoch travels with its ranges where the two are fetched together (below) */
+    constexpr bool IMU_WITH_EPOCH = AHEAD && AS > 0 && RANGING;
 
+    /* Everything loaded so far has arrived before the loop is entered (the first thing a step does is predict the
+     * covariance, so nothing is lost): a wait for these loads INSIDE the loop would be repeated in every epoch, where it
+     * waits for the epoch that was only just prefetched. 0x0F70 = vmcnt(0), the other counters untouched. */
+    __builtin_amdgcn_s_waitcnt(0x0F70);
     uint32_t s = 0;
     for (int e = 0; e < a.n_steps; ++e) { /* the state stays in registers from epoch to epoch */
-        const double dt = epoch_dt(a, t, e);
+        const double dt = dt_next;
+        if (multi && e + 1 < a.n_steps) dt_next = a.dt_steps[opaque_uniform(e + 1)];
         if (fresh_imu) { /* fresh sample: newIMUMeasurement latches it (KalmanFilterTOAIMU.cpp:78-89) */
 #pragma unroll
             for (int k = 0; k < 3; ++k) imu.acc[k] = (double)rawi.acc[k];
-            if (e + 1 < a.n_steps) {
-                if constexpr (AHEAD) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
+            if constexpr (AHEAD && !IMU_WITH_EPOCH) {
+                if (e + 1 < a.n_steps) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
             }
         }
+        /* The step in two parts with the pose store between them: the pose a per-epoch caller would have read back
+         * (getPose at timeLag 0) is final before the covariance update, and vmcnt counts stores too -- the wait at the
+         * loop's back-edge (for the prefetched epoch) would otherwise sit right behind this store and wait for its
+         * acknowledgement in every epoch. One store for every lane, whichever way it left the first part. */
+        Iekf9Out o;
+        auto finish = [&](bool update) {
+            if (a.traj) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) (a.traj + ((size_t)opaque_uniform(e) * 3 + k) * T)[t32] = tg.pos[k];
+            }
+            if (update) s = step_imu9_cov(tg, o, imu);
+        };
         if constexpr (AS > 0) {
             RegScratch<AS> sc;
             if (has_ranging) {
                 unpack_epoch<MREAL, AS>(raw, sc);
                 if (e + 1 < a.n_steps) {
-                    if constexpr (AHEAD) fetch_epoch<MREAL, AS>(a, opaque_lane(t), opaque_uniform(e + 1), raw);
+                    if constexpr (AHEAD) {
+                        fetch_epoch<MREAL, AS>(a, opaque_lane(t), opaque_uniform(e + 1), raw);
+                        if constexpr (IMU_WITH_EPOCH) {
+                            if (fresh_imu) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
+                        }
+                    }
                 }
             } else {
 #pragma unroll
                 for (int k = 0; k < AS; ++k) sc.r[k] = sc.e[k] = sc.w[k] = 0.0;
             }
-            s = step_imu9<RANGING>(tg, sc, pr, dt, imu, park);
+            finish(step_imu9_state<RANGING>(tg, sc, pr, dt, imu, park, diag, o, s));
             if constexpr (!AHEAD) { /* 8-byte measurements: the next epoch is fetched when this one is over */
                 if (e + 1 < a.n_steps) {
                     if (fresh_imu) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
@@ -147,14 +189,10 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
         } else {
             Scratch sc{nullptr, nullptr, nullptr, WAVE};
             if (has_ranging) sc = stage_epoch_lds<MREAL>(a, lds, lane, t, opaque_uniform(e));
-            s = step_imu9<RANGING>(tg, sc, pr, dt, imu, park);
+            finish(step_imu9_state<RANGING>(tg, sc, pr, dt, imu, park, diag, o, s));
             if constexpr (!AHEAD) { /* the ranges are staged per epoch above; the next accelerometer sample is not */
                 if (e + 1 < a.n_steps && fresh_imu) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
             }
-        }
-        if (a.traj) { /* the pose a per-epoch caller would have read back (getPose at timeLag 0) */
-#pragma unroll
-            for (int k = 0; k < 3; ++k) (a.traj + ((size_t)opaque_uniform(e) * 3 + k) * T)[t32] = tg.pos[k];
         }
         if constexpr (cov_is_rounded<REAL>()) { /* what n single-epoch launches would have kept in HBM */
             if (e + 1 < a.n_steps) {

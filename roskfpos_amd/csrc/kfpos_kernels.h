@@ -50,6 +50,7 @@ struct KArgs {
     double accel_noise, jolt, cost_threshold;
     int ignore_worst, top_n, use_init_pos, ml_variant;
     int pair9;        /* 9-state kernel: two lanes per tag for the tail of the gain iteration (KFPOS_PAIR9=1; off by default: DESIGN 6a) */
+    int imu9_diag;    /* 9-state kernel: a wavefront whose accelerometer covariances are all diagonal runs the diagonal form of the gain iteration's pass (same bits; KFPOS_IMU9_DIAG=0: never) */
     /* planar filter configuration (kfpos_planar_config) */
     int use_fixed_height, imu_fixed_cov_acc, imu_fixed_cov_w;
     double px4_height, px4_arm_p1, px4_arm_p2, px4_cov_vel, px4_cov_gyro_z;
