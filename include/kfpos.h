@@ -430,6 +430,39 @@ int kfpos_run_trace_dev(kfpos_handle *h, int32_t n_steps,
                         const void *cov, int64_t stride_cov,
                         const double *dt_steps, double *trajectory, uint32_t *status, void *stream);
 
+/* Replay an IMU-rate event schedule of the 9-state filter (KFPOS_MODEL_TOA_IMU) resident in HBM, in the node's own
+ * call sequence: newIMUMeasurement arrives at the IMU's rate, several samples per ranging epoch, each a complete
+ * predict + IMU-only update at its own timeLag, and newTOAMeasurement re-fuses the latched sample
+ * (KalmanFilterTOAIMU.cpp:49-92). Equivalent, bit for bit, to the same events as single calls in order -- a
+ * KFPOS_EVENT_IMU event is kfpos_step_imu_dev(accel_i, cov, NULL, dt_e, ...), a KFPOS_EVENT_TOA event is
+ * kfpos_step_toa_dev(range_j, err_j, NULL, dt_e, ...): state, covariance as the handle stores it (compact storage is
+ * rounded after every event), flags, the latched sample and its covariance, every status word and trajectory row --
+ * but up to 128 events run inside ONE launch with every tag's state resident in registers
+ * (KFPOS_TRACE_CHUNK_STEPS applies, as in kfpos_run_trace_dev). A TOA event that precedes the first IMU event of
+ * the call fuses what the handle held latched before the call: that sample with ITS covariance, or nothing.
+ * The call ends with its last sample and `cov` latched, as the single calls would leave them.
+ *   kinds, dt_events  HOST arrays of n_events entries: what each event is, and its timeLag, shared by all tags
+ *   range_mm, err_est the j-th TOA event reads base + j * stride elements (stride_err may be 0: one array)
+ *   accel             the i-th IMU event reads base + i * stride_accel elements
+ *   cov               [9][n_tags], ONE array for the whole call: a sensor covariance per sample is not supported
+ *                     here -- callers that have one use the single calls
+ *   trajectory        [n_events][3][n_tags] double or NULL: the position after every event
+ *   status_events     [n_events][n_tags] status word of every event, or NULL
+ *   status            [n_tags] status words of the LAST event, or NULL
+ * Decided on the host before anything is enqueued: NULL handle, n_events < 0, a kind other than 0 or 1, or a missing
+ * array for a kind that occurs (kinds / dt_events included) -> KFPOS_ERR_ARG; a handle of another model ->
+ * KFPOS_ERR_MODEL; anchors unset with at least one TOA event -> KFPOS_ERR_STATE. n_events == 0 is KFPOS_OK and
+ * changes nothing. KFPOS_VERSION is unchanged: detect the call by symbol. */
+#define KFPOS_EVENT_IMU 0 /* newIMUMeasurement: latch the sample, predict + IMU-only update */
+#define KFPOS_EVENT_TOA 1 /* newTOAMeasurement: ranging epoch, re-fusing whatever sample is latched */
+int kfpos_run_events_dev(kfpos_handle *h, int32_t n_events,
+                         const uint8_t *kinds, const double *dt_events,
+                         const int32_t *range_mm, int64_t stride_ranges,
+                         const void *err_est, int64_t stride_err,
+                         const void *accel, int64_t stride_accel,
+                         const void *cov,
+                         double *trajectory, uint32_t *status_events, uint32_t *status, void *stream);
+
 /* ---- multi-GPU: contiguous tag shards + ONE collective, the RCCL all-gather of poses ----
  * The reference runs one filter in one process (node_pos.cpp:176-181) and has no counterpart. Here a node that serves
  * more tags than one GPU holds cuts the batch into contiguous ranges, one handle per GPU; the filters never talk to each

@@ -30,7 +30,8 @@ EXPORTS = [
     "kfpos_real_size", "kfpos_step_toa", "kfpos_step_imu", "kfpos_step_toa_imu", "kfpos_get_pose",
     "kfpos_get_pose_each", "kfpos_get_predicted",
     "kfpos_state_dim", "kfpos_get_state", "kfpos_set_state", "kfpos_step_toa_dev", "kfpos_step_imu_dev",
-    "kfpos_step_toa_imu_dev", "kfpos_get_pose_dev", "kfpos_run_trace_dev", "kfpos_last_error",
+    "kfpos_step_toa_imu_dev", "kfpos_get_pose_dev", "kfpos_run_trace_dev", "kfpos_run_events_dev",
+    "kfpos_last_error",
     "kfpos_strerror", "kfpos_version", "kfpos_timing_begin", "kfpos_timing_end",
     "kfpos_set_planar", "kfpos_step_sensor", "kfpos_step_sensor_dev", "kfpos_get_height", "kfpos_set_height",
     "kfpos_latch_dim", "kfpos_get_latch", "kfpos_set_latch",
@@ -46,6 +47,7 @@ EXPORTS = [
 GATHER_COLLECTIVE, GATHER_DIRECT = 0, 1
 COMM_ID_BYTES = 128
 SLOT_TOA, SLOT_IMU, SLOT_TOA_IMU = 0, 1, 2
+EVENT_IMU, EVENT_TOA = 0, 1  # kfpos_run_events_dev: newIMUMeasurement / newTOAMeasurement
 SLOT_DT_PER_TAG, SLOT_REUSE_ERR, SLOT_REUSE_COV, SLOT_NO_POSE = 0x100, 0x200, 0x400, 0x800
 
 
@@ -131,6 +133,7 @@ def load():
     sig("kfpos_get_pose_dev", [vp, f64, vp, vp, vp, vp, vp])
     L.kfpos_run_trace_dev.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64,
                                       vp, vp, vp, vp]
+    sig("kfpos_run_events_dev", [vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp])
     sig("kfpos_set_planar", [vp, C.POINTER(PlanarConfig)])
     sig("kfpos_step_sensor", [vp, i32, vp, vp, i32, vp])
     sig("kfpos_step_sensor_dev", [vp, i32, vp, vp, f64, vp, vp])
@@ -537,6 +540,20 @@ class KfposBank:
         self._chk(self.lib.kfpos_run_trace_dev(self._h, n_steps, _ptr(range_mm), stride_ranges, _ptr(err_est),
                                                stride_err, _ptr(accel), stride_accel, _ptr(cov), stride_cov,
                                                d.ctypes.data, _ptr(trajectory), _ptr(status), _ptr(stream)))
+
+    def run_events_dev(self, kinds, dt_events, range_mm=None, stride_ranges=0, err_est=None, stride_err=0,
+                       accel=None, stride_accel=0, cov=None, trajectory=None, status_events=None, status=None,
+                       stream=None):
+        """kfpos_run_events_dev: kinds (EVENT_IMU / EVENT_TOA) and dt_events are host arrays of one entry per event;
+        the j-th TOA event reads range_mm / err_est + j * stride, the i-th IMU event accel + i * stride_accel; cov is
+        one [9][T] array for the call. Bit for bit the same events as single step_imu_dev / step_toa_dev calls."""
+        k = np.ascontiguousarray(kinds, dtype=np.uint8)
+        d = np.ascontiguousarray(dt_events, dtype=np.float64)
+        assert k.ndim == 1 and d.shape == k.shape
+        self._chk(self.lib.kfpos_run_events_dev(self._h, k.size, k.ctypes.data, d.ctypes.data, _ptr(range_mm),
+                                                stride_ranges, _ptr(err_est), stride_err, _ptr(accel), stride_accel,
+                                                _ptr(cov), _ptr(trajectory), _ptr(status_events), _ptr(status),
+                                                _ptr(stream)))
 
     def timing_begin(self, stream=None):
         self._chk(self.lib.kfpos_timing_begin(self._h, _ptr(stream)))

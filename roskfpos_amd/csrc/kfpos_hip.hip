@@ -704,6 +704,104 @@ int kfpos_run_trace_dev(kfpos_handle *h, int32_t n_steps, const int32_t *range_m
     return KFPOS_OK;
 }
 
+int kfpos_run_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds, const double *dt_events,
+                         const int32_t *range_mm, int64_t stride_ranges, const void *err_est, int64_t stride_err,
+                         const void *accel, int64_t stride_accel, const void *cov, double *trajectory,
+                         uint32_t *status_events, uint32_t *status, void *stream) {
+    g_err.clear();
+    if (!h || n_events < 0) return KFPOS_ERR_ARG;
+    if (n_events == 0) return KFPOS_OK;
+    if (!kinds || !dt_events) return KFPOS_ERR_ARG;
+    int n_toa = 0, n_imu = 0, lead = -1; /* lead: ranging events ahead of the call's first sample */
+    for (int e = 0; e < n_events; ++e) {
+        if (kinds[e] == KFPOS_EVENT_TOA) ++n_toa;
+        else if (kinds[e] == KFPOS_EVENT_IMU) {
+            if (lead < 0) lead = e;
+            ++n_imu;
+        } else {
+            g_err = "kfpos_run_events_dev: kinds[" + std::to_string(e) + "] = " + std::to_string((int)kinds[e]) + " is no event kind";
+            return KFPOS_ERR_ARG;
+        }
+    }
+    if (lead < 0) lead = n_events;
+    if ((n_toa && (!range_mm || !err_est)) || (n_imu && (!accel || !cov))) return KFPOS_ERR_ARG;
+    if (h->cfg.model != KFPOS_MODEL_TOA_IMU) return KFPOS_ERR_MODEL;
+    if (n_toa && !h->have_anchors) {
+        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
+        return KFPOS_ERR_STATE;
+    }
+    DevScope dev_(h->cfg.device);
+    const size_t T = h->cfg.n_tags, r = h->msz;
+    const hipStream_t s = (hipStream_t)stream;
+    /* Ranging events ahead of the first sample re-fuse what the handle held latched, with THAT sample's covariance:
+     * the multi-epoch ranging path of kfpos_run_trace_dev, which reads the latch. It reports the last status word of
+     * a launch only, so with status_events every one of these events is a launch of its own. */
+    if (lead > 0) {
+        KArgs a;
+        fill_args(h, a);
+        a.mode = MODE_TOA;
+        a.stride_ranges = stride_ranges;
+        a.stride_err = stride_err;
+        const int chunk = status_events ? 1 : h->trace_chunk;
+        for (int s0 = 0; s0 < lead; s0 += chunk) {
+            const int n = lead - s0 < chunk ? lead - s0 : chunk;
+            a.n_steps = n;
+            a.ranges = range_mm + (size_t)s0 * stride_ranges;
+            a.err = (const char *)err_est + (size_t)s0 * stride_err * r;
+            for (int k = 0; k < n; ++k) a.dt_steps[k] = dt_events[s0 + k];
+            a.dt_shared = dt_events[s0];
+            a.traj = trajectory ? trajectory + (size_t)s0 * 3 * T : nullptr;
+            a.status = status_events ? status_events + (size_t)s0 * T : (s0 + n == n_events ? status : nullptr);
+            const int rc = launch_step(h, a, s);
+            if (rc != KFPOS_OK) return rc;
+        }
+        if (lead == n_events && status_events && status)
+            HIPCHK(hipMemcpyAsync(status, status_events + (size_t)(n_events - 1) * T, sizeof(uint32_t) * T,
+                                  hipMemcpyDeviceToDevice, s));
+    }
+    if (lead == n_events) return KFPOS_OK;
+    /* From the first sample on: k_events_imu9, up to trace_chunk events per launch. Every launch leaves its last
+     * sample and `cov` latched, so the next one (and whoever calls next) finds them where single calls leave them. */
+    const int as = (!h->force_generic && static_anchors(h) == 8) ? 8 : 0;
+    const kfpos_k::events_kernel_t kern = kfpos_k::imu9_events_kernel(h->cfg.storage, as);
+    const size_t lds = park9_bytes() + (as == 0 ? lds_bytes(h) : 0);
+    if (lds > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kfpos_k::EvArgs ev;
+    fill_args(h, ev.k);
+    ev.k.stride_ranges = stride_ranges;
+    ev.k.stride_err = stride_err;
+    ev.k.stride_accel = stride_accel;
+    ev.k.cov = cov;
+    const int blocks = (int)((T + WAVE - 1) / WAVE);
+    size_t j = (size_t)lead, i = 0; /* ranging epochs / samples consumed so far */
+    for (int e0 = lead; e0 < n_events; e0 += h->trace_chunk) {
+        const int n = n_events - e0 < h->trace_chunk ? n_events - e0 : h->trace_chunk;
+        ev.k.n_steps = n;
+        ev.k.ranges = range_mm ? range_mm + j * stride_ranges : nullptr;
+        ev.k.err = err_est ? (const char *)err_est + j * stride_err * r : nullptr;
+        ev.k.accel = (const char *)accel + i * stride_accel * r;
+        ev.kinds[0] = ev.kinds[1] = 0;
+        for (int k = 0; k < n; ++k) {
+            ev.k.dt_steps[k] = dt_events[e0 + k];
+            if (kinds[e0 + k] == KFPOS_EVENT_TOA) {
+                ev.kinds[k >> 6] |= 1ull << (k & 63);
+                ++j;
+            } else {
+                ++i;
+            }
+        }
+        ev.k.dt_shared = dt_events[e0];
+        ev.k.traj = trajectory ? trajectory + (size_t)e0 * 3 * T : nullptr;
+        ev.status_events = status_events ? status_events + (size_t)e0 * T : nullptr;
+        ev.k.status = e0 + n == n_events ? status : nullptr;
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), lds, s, ev);
+        HIPCHK(hipGetLastError());
+        h->stepped = true;
+    }
+    return KFPOS_OK;
+}
+
 static int launch_pose(kfpos_handle *h, double dt_ahead, const double *dt_each, double *pos, double *cov3x3,
                        double *vel, uint32_t *status, void *stream, double *full_x = nullptr,
                        double *full_P = nullptr) {

@@ -6,35 +6,6 @@
 namespace {
 
 /* ------------------------------------------------------------------ 9-state step kernel */
-/* The acceleration sample is fetched one epoch ahead like the ranges. Its covariance is loaded and whitened ONCE per
- * launch: a multi-epoch launch always has one covariance array for all its epochs (stride_cov = 0: a sensor with a
- * fixed covariance); a trace with a covariance per epoch is replayed one epoch per launch (kfpos_run_trace_dev). */
-template <typename MREAL>
-struct RawImu {
-    MREAL acc[3];
-};
-template <typename MREAL>
-__device__ inline void fetch_imu(const KArgs &a, size_t t, int s, RawImu<MREAL> &raw) {
-    const MREAL *ap = (const MREAL *)a.accel + (size_t)s * a.stride_accel;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) raw.acc[k] = (ap + (size_t)k * a.T)[(uint32_t)t];
-}
-template <typename MREAL>
-__device__ inline void fetch_imu_cov(const KArgs &a, size_t t, int s, MREAL raw[9]) {
-    const MREAL *cp = (const MREAL *)a.cov + (size_t)s * a.stride_cov;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) raw[k] = (cp + (size_t)k * a.T)[(uint32_t)t];
-}
-template <typename MREAL>
-__device__ inline void latch_imu_cov(const KArgs &a, size_t T, uint32_t t32, const double cv[9]) {
-    strow<MREAL>(a.imu_cov, 0, T, t32, cv[0]);
-    strow<MREAL>(a.imu_cov, 1, T, t32, cv[3]);
-    strow<MREAL>(a.imu_cov, 2, T, t32, cv[4]);
-    strow<MREAL>(a.imu_cov, 3, T, t32, cv[6]);
-    strow<MREAL>(a.imu_cov, 4, T, t32, cv[7]);
-    strow<MREAL>(a.imu_cov, 5, T, t32, cv[8]);
-}
-
 /* RANGING = false: the IMU-only call (MODE_IMU_ONLY), a kernel of its own */
 template <typename REAL, typename MREAL, int AS, bool RANGING = true>
 __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {

@@ -24,7 +24,7 @@
  *    shuffle and no barrier (the exception: the 8-lanes-per-tag kernel of small banks, kfpos_k_coop.hip).
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
- * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_misc (8-state planar
+ * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_misc (8-state planar
  * filter, standalone ML estimator, getPose, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
@@ -98,6 +98,20 @@ struct PoseArgs {
 
 typedef void (*step_kernel_t)(const KArgs);
 
+/* kfpos_run_events_dev (kfpos_k_imu9ev.hip): an argument block of its own around KArgs, whose layout every other kernel
+ * sees unchanged. k.n_steps events; k.dt_steps[e] is the timeLag of event e; bit e of `kinds` says what it is (0 =
+ * KFPOS_EVENT_IMU, 1 = KFPOS_EVENT_TOA); the j-th ranging event of the launch reads k.ranges / k.err + j * stride,
+ * the i-th IMU event k.accel + i * stride; k.cov is the one covariance of the call; k.traj / status_events start at
+ * the launch's first event; k.status: the last event's words, or null. */
+struct EvArgs {
+    KArgs k;
+    unsigned long long kinds[KFPOS_TRACE_CHUNK / 64];
+    uint32_t *status_events; /* [n_steps][T] or null */
+};
+static_assert(KFPOS_TRACE_CHUNK == 128, "EvArgs::kinds is indexed as two 64-bit words");
+static_assert(sizeof(EvArgs) <= 4096, "kernel arguments are limited to 4 KB");
+typedef void (*events_kernel_t)(const EvArgs);
+
 /* ---- selectors: each is defined in the translation unit that instantiates the kernels it hands out ----
  * st = KFPOS_STORE_*; as = anchor-count specialisation (8: epoch in registers; -8 / -16: compile-time loops over an
  * LDS-resident epoch; 0: run-time loop); heur: 0 = no outlier heuristic, 1 = top-N only, 2 = leave-one-out */
@@ -105,6 +119,7 @@ step_kernel_t toa6_sym_kernel(int st, int as, int heur, bool two_waves);   /* kf
 step_kernel_t toa6_full_kernel(int st, int as, int heur);                  /* kfpos_k_toa6f.hip */
 step_kernel_t toa6_coop_kernel(int st);                                    /* kfpos_k_coop.hip */
 step_kernel_t imu9_kernel(int st, int as, bool ranging);                   /* kfpos_k_imu9.hip */
+events_kernel_t imu9_events_kernel(int st, int as);                        /* kfpos_k_imu9ev.hip: as = 8 or 0 */
 step_kernel_t ml_kernel(int st, int as);                                   /* kfpos_k_misc.hip */
 step_kernel_t planar_kernel(int st, bool sensors, int as);                 /* kfpos_k_misc.hip */
 void launch_get_pose(int model, bool full, int st, int blocks, hipStream_t s, const PoseArgs &a); /* kfpos_k_misc.hip */
@@ -312,6 +327,36 @@ __device__ inline StaticScratch<N> stage_epoch_lds_n(const KArgs &a, double *lds
     }
     return sc;
 }
+/* ---- 9-state kernels (kfpos_k_imu9.hip, kfpos_k_imu9ev.hip): the accelerometer sample and its covariance ---- */
+/* The acceleration sample is fetched one epoch ahead like the ranges. Its covariance is loaded and whitened ONCE per
+ * launch: a multi-epoch launch always has one covariance array for all its epochs (stride_cov = 0: a sensor with a
+ * fixed covariance); a trace with a covariance per epoch is replayed one epoch per launch (kfpos_run_trace_dev). */
+template <typename MREAL>
+struct RawImu {
+    MREAL acc[3];
+};
+template <typename MREAL>
+__device__ inline void fetch_imu(const KArgs &a, size_t t, int s, RawImu<MREAL> &raw) {
+    const MREAL *ap = (const MREAL *)a.accel + (size_t)s * a.stride_accel;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) raw.acc[k] = (ap + (size_t)k * a.T)[(uint32_t)t];
+}
+template <typename MREAL>
+__device__ inline void fetch_imu_cov(const KArgs &a, size_t t, int s, MREAL raw[9]) {
+    const MREAL *cp = (const MREAL *)a.cov + (size_t)s * a.stride_cov;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) raw[k] = (cp + (size_t)k * a.T)[(uint32_t)t];
+}
+template <typename MREAL>
+__device__ inline void latch_imu_cov(const KArgs &a, size_t T, uint32_t t32, const double cv[9]) {
+    strow<MREAL>(a.imu_cov, 0, T, t32, cv[0]);
+    strow<MREAL>(a.imu_cov, 1, T, t32, cv[3]);
+    strow<MREAL>(a.imu_cov, 2, T, t32, cv[4]);
+    strow<MREAL>(a.imu_cov, 3, T, t32, cv[6]);
+    strow<MREAL>(a.imu_cov, 4, T, t32, cv[7]);
+    strow<MREAL>(a.imu_cov, 5, T, t32, cv[8]);
+}
+
 /* A wave-uniform epoch index the optimiser cannot see through: addresses derived from it are formed anew in every
  * epoch (a few scalar instructions) instead of living as two dozen running row pointers across the whole epoch loop,
  * where they exhaust the scalar registers and end up as spilled 64-bit per-lane addresses. */

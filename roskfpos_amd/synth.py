@@ -23,6 +23,8 @@ ERR_EST = 0.0025
 ACC_SIGMA = 0.1
 ACC_COV = 0.01
 _CH_PER_STEP = np.uint64(256)
+_SUB_BASE = np.uint64(1 << 40)  # counters of the samples between two ranging epochs (accel_between): beyond any step's channels
+_SUB_PER_STEP = 64
 _GOLD = np.uint64(0x9E3779B97F4A7C15)
 _M1 = np.uint64(0xBF58476D1CE4E5B9)
 _M2 = np.uint64(0x94D049BB133111EB)
@@ -124,6 +126,19 @@ class Workload:
         base = np.uint64(step + 1) * _CH_PER_STEP + np.uint64(200)
         ch = base + np.uint64(2) * np.arange(3, dtype=np.uint64)
         return (a + ACC_SIGMA * _normal(self._key[:, None], ch[None, :])).astype(dtype)
+
+    def accel_between(self, step: int, sub: int, n_sub: int, dtype=np.float64) -> np.ndarray:
+        """(T, 3) accelerometer sample `sub` (0 .. n_sub - 1) of the n_sub that an IMU running faster than the ranging
+        delivers between ranging epochs step - 1 and step, evenly spaced: sample sub is taken dt_of(step) * (sub + 1) /
+        (n_sub + 1) after epoch step - 1 (each of the n_sub + 1 events of the period then has that fraction of dt_of(step)
+        as its timeLag). Noise counters of its own, above every per-step channel: accel(), ranges_mm() and the planar
+        sensors draw exactly what they drew before."""
+        if not (0 <= sub < n_sub <= _SUB_PER_STEP):
+            raise ValueError("0 <= sub < n_sub <= %d" % _SUB_PER_STEP)
+        t = self.time_of(step) - self.dt_of(step) * (n_sub - sub) / (n_sub + 1)
+        base = _SUB_BASE + (np.uint64(step + 1) * np.uint64(_SUB_PER_STEP) + np.uint64(sub)) * np.uint64(8)
+        ch = base + np.uint64(2) * np.arange(3, dtype=np.uint64)
+        return (self.acceleration(t) + ACC_SIGMA * _normal(self._key[:, None], ch[None, :])).astype(dtype)
 
     def accel_cov(self, dtype=np.float64) -> np.ndarray:
         """(T, 9) row-major 3x3 accelerometer covariance."""

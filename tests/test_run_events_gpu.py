@@ -1,0 +1,349 @@
+"""kfpos_run_events_dev: an IMU-rate event schedule of the 9-state filter in one launch computes, bit for bit, what the same
+events give as single kfpos_step_imu_dev / kfpos_step_toa_dev calls -- state, covariance as stored, flags, latch, the
+status word and the position of every event -- and stays with the oracle after every event.
+
+One schedule serves every test: a leading ranging event on a handle with nothing latched, runs of 0, 1 and 4 IMU samples
+between rangings, two rangings back to back, one event with dt = 0, the dropout rows of cases.Case.epoch; it ends on a
+ranging event, or -- three more samples appended -- on an IMU event. With KFPOS_TRACE_CHUNK_STEPS=7 a launch boundary
+falls inside a run of IMU samples and another directly before a ranging event (asserted below)."""
+import contextlib
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+from cases import Case, rms_and_max
+from conftest import has_gpu
+from roskfpos_amd.synth import Workload
+
+pytestmark = pytest.mark.gpu
+
+IMU, TOA = 0, 1
+RUNS = (0, 1, 4, 0, 4, 4, 1, 0, 4, 1, 4, 1)   # IMU samples ahead of each ranging event
+TAIL = 3                                      # IMU samples behind the last ranging event ("ends on an IMU event")
+DT_ZERO = 10                                  # the event with dt = 0 (an IMU sample inside a run of four)
+ERR_ARG, ERR_MODEL, ERR_STATE = 1, 4, 5
+
+
+@contextlib.contextmanager
+def _env(**kv):
+    """environment variables the library reads in kfpos_create"""
+    old = {k: os.environ.get(k) for k in kv}
+    try:
+        for k, v in kv.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _kinds(end_on_imu):
+    kinds = []
+    for k in RUNS:
+        kinds += [IMU] * k + [TOA]
+    if end_on_imu:
+        kinds += [IMU] * TAIL
+    return np.array(kinds, dtype=np.uint8)
+
+
+def test_the_schedule_holds_what_it_is_meant_to_hold():
+    for end_on_imu in (False, True):
+        k = _kinds(end_on_imu)
+        assert 36 <= k.size <= 40 and k[0] == TOA and k[-1] == (IMU if end_on_imu else TOA)
+        assert {0, 1, 4} <= set(RUNS) and k[DT_ZERO] == IMU
+        assert any(k[e] == TOA and k[e + 1] == TOA for e in range(k.size - 1))
+        # launches of 7 events behind the leading ranging event (which goes down the ranging path of its own)
+        starts = list(range(1 + 7, k.size, 7))
+        assert any(k[s - 1] == IMU and k[s] == IMU for s in starts), "no boundary inside an IMU run"
+        assert any(k[s] == TOA for s in starts), "no boundary directly before a ranging event"
+    eps = range(len(RUNS))
+    assert any(s % 7 == 3 for s in eps) and any(s % 11 == 5 for s in eps) and any(s % 23 == 9 for s in eps)
+
+
+class Inputs:
+    """the schedule's inputs in HBM (component-major), and on the host in the (T, ...) form the oracle takes"""
+
+    def __init__(self, T, A, storage, fixed, cov_full, end_on_imu, dev="cuda:0"):
+        import torch
+        from roskfpos_amd import capi
+        self.T, self.A, self.storage, self.fixed = T, A, storage, fixed
+        real = self.real = np.float64 if storage == capi.STORE_F64 else np.float32
+        case = Case("events", 1, A, fixed=fixed, T=T, cov_full=cov_full)
+        w = self.w = Workload(T, A)
+        self.kinds = _kinds(end_on_imu)
+        self.dts = np.round(np.random.default_rng(20261017).uniform(0.004, 0.03, self.kinds.size), 4)
+        self.dts[DT_ZERO] = 0.0
+        self.ranges = np.stack([case.epoch(w, s) for s in range(len(RUNS))])              # (J, T, A)
+        acc = [w.accel_between(s, i, k, real) for s, k in enumerate(RUNS) for i in range(k)]
+        acc += [w.accel_between(len(RUNS), i, TAIL, real) for i in range(TAIL if end_on_imu else 0)]
+        self.accel = np.stack(acc)                                                        # (I, T, 3)
+        self.err = w.err_est(real)
+        self.cov = case.accel_cov(w).astype(real)
+        self.cov_other = Case("other", 1, A, T=T, cov_full=not cov_full).accel_cov(w).astype(real)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        self.d_r, self.d_e = up(self.ranges.transpose(0, 2, 1)), up(self.err.T)
+        self.d_a, self.d_c, self.d_c_other = up(self.accel.transpose(0, 2, 1)), up(self.cov.T), up(self.cov_other.T)
+
+    def bank(self, chunk=None):
+        from roskfpos_amd import capi
+        with _env(KFPOS_TRACE_CHUNK_STEPS=chunk):
+            return capi.KfposBank(capi.MODEL_TOA_IMU, self.T, self.w.anchors, storage=self.storage,
+                                  init_pos=self.w.init_positions() if self.fixed else None)
+
+
+def _final(b):
+    x, P, fl = b.get_state()
+    return x, P, fl, b.get_latch()
+
+
+def _single_calls(b, inp, kinds, dts):
+    """the events as single _dev calls -> (position after every event, status of every event, x, P, flags, latch)"""
+    import torch
+    n, T = kinds.size, inp.T
+    st = torch.zeros(n, T, dtype=torch.int32, device=inp.d_r.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    traj = np.zeros((n, 3, T))
+    j = i = 0
+    for e in range(n):
+        if kinds[e] == TOA:
+            b.step_toa_dev(inp.d_r[j], inp.d_e, dts[e], status=st[e], stream=stream)
+            j += 1
+        else:
+            b.step_imu_dev(inp.d_a[i], inp.d_c, dts[e], status=st[e], stream=stream)
+            i += 1
+        torch.cuda.synchronize()
+        traj[e] = b.get_state()[0][:, :3].T
+    return (traj, st.cpu().numpy()) + _final(b)
+
+
+def _one_call(b, inp, kinds, dts, outputs=True):
+    import torch
+    n, T, A = kinds.size, inp.T, inp.A
+    dev = inp.d_r.device
+    traj = torch.full((n, 3, T), 7.0, dtype=torch.float64, device=dev) if outputs else None
+    ste = torch.full((n, T), -1, dtype=torch.int32, device=dev) if outputs else None
+    st = torch.full((T,), -1, dtype=torch.int32, device=dev)
+    b.run_events_dev(kinds, dts, range_mm=inp.d_r, stride_ranges=A * T, err_est=inp.d_e, stride_err=0, accel=inp.d_a,
+                     stride_accel=3 * T, cov=inp.d_c, trajectory=traj, status_events=ste, status=st,
+                     stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    last = st.cpu().numpy()
+    if not outputs:
+        return (None, last) + _final(b)
+    assert np.array_equal(last, ste[-1].cpu().numpy()), "status is not the last event's"
+    return (traj.cpu().numpy(), ste.cpu().numpy()) + _final(b)
+
+
+NAMES = ("position after every event", "status of every event", "x", "P", "flags", "latch")
+
+
+def _same_bytes(got, ref, what, first=0):
+    for g, r, name in list(zip(got, ref, NAMES))[first:]:
+        assert g.shape == r.shape and g.dtype == r.dtype, (what, name)
+        assert g.tobytes() == r.tobytes(), (what, name)
+
+
+def _bit_identity(T, A, storage, combos):
+    for fixed, cov_full, end_on_imu in combos:
+        inp = Inputs(T, A, storage, fixed, cov_full, end_on_imu)
+        b = inp.bank()
+        ref = _single_calls(b, inp, inp.kinds, inp.dts)
+        b.close()
+        low = ref[1] & 0xFF
+        assert (low == 0).mean() > 0.5 and (low != 0).any()      # most steps are plain, the dropout paths ran
+        if not fixed:
+            assert (ref[1] & 0x08).any()                         # ML initialisations happened
+        what = f"fixed={fixed} cov_full={cov_full} end_on_imu={end_on_imu}"
+        for chunk in (None, 7):
+            b = inp.bank(chunk)
+            got = _one_call(b, inp, inp.kinds, inp.dts)
+            b.close()
+            _same_bytes(got, ref, f"{what} chunk={chunk}")
+        b = inp.bank(7)
+        bare = _one_call(b, inp, inp.kinds, inp.dts, outputs=False)   # trajectory = status_events = NULL
+        b.close()
+        assert bare[1].tobytes() == ref[1][-1].tobytes(), (what, "last status")
+        _same_bytes(bare, ref, f"{what} without per-event outputs", first=2)
+
+
+EVERY = [(f, c, e) for f in (True, False) for c in (False, True) for e in (False, True)]
+
+
+@pytest.mark.parametrize("A", [8, 5])               # epoch in registers; run-time anchor loop
+@pytest.mark.parametrize("storage", [0, 1, 2, 3])   # f64, f32, mixed, p48
+def test_one_call_equals_the_single_calls_bit_for_bit(storage, A):
+    if not has_gpu():
+        pytest.skip("no GPU")
+    _bit_identity(130, A, storage, EVERY)           # two full wavefronts and one of two lanes
+
+
+@pytest.mark.parametrize("A", [8, 5])
+@pytest.mark.parametrize("storage", [0, 1, 2, 3])
+def test_one_call_equals_the_single_calls_for_a_single_tag(storage, A):
+    if not has_gpu():
+        pytest.skip("no GPU")
+    _bit_identity(1, A, storage, [(True, False, True), (False, True, False)])
+
+
+@pytest.mark.parametrize("storage,A", [(0, 8), (1, 5), (2, 8), (3, 5), (2, 5)])
+def test_leading_ranging_events_fuse_the_previously_latched_sample_with_its_covariance(storage, A):
+    if not has_gpu():
+        pytest.skip("no GPU")
+    import torch
+    kinds = np.array([TOA, TOA, IMU, TOA, IMU, IMU, TOA, TOA], dtype=np.uint8)
+    for cov_full in (False, True):
+        inp = Inputs(130, A, storage, True, cov_full, False)
+        dts = inp.dts[:kinds.size].copy()
+        out = []
+        for one_call in (False, True):
+            for chunk in ((None, 3) if one_call else (None,)):
+                b = inp.bank(chunk)
+                # an earlier sample, latched with ANOTHER covariance than the call's
+                b.step_imu_dev(inp.d_a[-1], inp.d_c_other, 0.02, stream=torch.cuda.current_stream().cuda_stream)
+                torch.cuda.synchronize()
+                out.append((_one_call if one_call else _single_calls)(b, inp, kinds, dts))
+                b.close()
+        _same_bytes(out[1], out[0], f"cov_full={cov_full}")
+        _same_bytes(out[2], out[0], f"cov_full={cov_full} chunk=3")
+        # the comparison has teeth: had the two leading events fused the latched sample with the CALL's covariance
+        # (here: the latch rewritten to carry it, then the single calls), the covariance would have come out differently
+        def lead(swap):
+            stream = torch.cuda.current_stream().cuda_stream
+            b = inp.bank()
+            b.step_imu_dev(inp.d_a[-1], inp.d_c_other, 0.02, stream=stream)
+            torch.cuda.synchronize()
+            if swap:
+                b2 = inp.bank()
+                b2.step_imu_dev(inp.d_a[-1], inp.d_c, 0.02, stream=stream)
+                torch.cuda.synchronize()
+                b.set_latch(b2.get_latch())
+                b2.close()
+            res = _single_calls(b, inp, kinds[:2], dts[:2])
+            b.close()
+            return res
+
+        assert lead(False)[3].tobytes() != lead(True)[3].tobytes()
+
+
+@pytest.mark.parametrize("A", [8, 5])
+@pytest.mark.parametrize("fixed", [True, False])
+@pytest.mark.parametrize("cov_full", [False, True])
+def test_f64_storage_matches_the_oracle_after_every_event(cov_full, fixed, A):
+    """position RMS <= 1e-9 m and max <= 1e-8 m after every event (the bounds of test_gpu_parity.py for the 9-state
+    cases), every status word equal to the oracle's, no tag left out"""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    import oracle_py
+    T = 130
+    inp = Inputs(T, A, 0, fixed, cov_full, True)
+    b = inp.bank()
+    got = _one_call(b, inp, inp.kinds, inp.dts)
+    b.close()
+    o = oracle_py.OracleBank(1, T, inp.w.anchors, init_pos=inp.w.init_positions() if fixed else None, n_threads=8)
+    j = i = 0
+    worst = [0.0, 0.0]
+    for e, kind in enumerate(inp.kinds):
+        if kind == TOA:
+            so = o.step_toa(inp.ranges[j], inp.err, inp.dts[e])
+            j += 1
+        else:
+            so = o.step_imu(inp.accel[i], inp.cov, inp.dts[e])
+            i += 1
+        po = o.get_state()[0][:, :3]
+        pg = got[0][e].T
+        assert pg.shape == po.shape == (T, 3)
+        rms, mx, same_nan = rms_and_max(pg, po)
+        worst = [max(worst[0], rms), max(worst[1], mx)]
+        assert same_nan, e
+        assert rms <= 1e-9 and mx <= 1e-8, (e, rms, mx)
+        assert np.array_equal(so, got[1][e].astype(np.uint32)), (e, "status words")
+    print(f"A={A} fixed={fixed} cov_full={cov_full}: worst RMS {worst[0]:.3e} m, worst max {worst[1]:.3e} m "
+          f"against the oracle over {inp.kinds.size} events")
+    assert np.isfinite(got[0][-1]).all()   # every tag has started by the end, none was left out of the comparison
+
+
+def _raw_call(b, n, kinds, dts, r, e, a, c, A, T):
+    p = lambda x: None if x is None else (x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr())  # noqa: E731
+    return b.lib.kfpos_run_events_dev(b._h, n, p(kinds), p(dts), p(r), A * T, p(e), 0, p(a), 3 * T, p(c),
+                                      None, None, None, None)
+
+
+def _snapshot(b):
+    x, P, fl = b.get_state()
+    parts = [x, P, fl]
+    if b.model == 1:
+        parts.append(b.get_latch())
+    return b"".join(np.ascontiguousarray(p).tobytes() for p in parts)
+
+
+def test_argument_errors_are_decided_before_anything_runs():
+    if not has_gpu():
+        pytest.skip("no GPU")
+    from roskfpos_amd import capi
+    T, A = 130, 8
+    inp = Inputs(T, A, capi.STORE_MIXED, True, False, False)
+    b = inp.bank()
+    _one_call(b, inp, inp.kinds[:9], inp.dts[:9])            # a bank with something in it
+    before = _snapshot(b)
+    k, d = inp.kinds[:9].copy(), inp.dts[:9].copy()
+    only_imu, only_toa = np.zeros(3, dtype=np.uint8), np.ones(3, dtype=np.uint8)
+    bad = k.copy()
+    bad[4] = 2
+    r, e, a, c = inp.d_r, inp.d_e, inp.d_a, inp.d_c
+    refused = {
+        "n_events < 0": (-1, k, d, r, e, a, c),
+        "a kind other than 0 or 1": (9, bad, d, r, e, a, c),
+        "kinds missing": (9, None, d, r, e, a, c),
+        "dt_events missing": (9, k, None, r, e, a, c),
+        "range_mm missing, TOA events": (9, k, d, None, e, a, c),
+        "err_est missing, TOA events": (3, only_toa, d, r, None, a, c),
+        "accel missing, IMU events": (9, k, d, r, e, None, c),
+        "cov missing, IMU events": (3, only_imu, d, r, e, a, None),
+    }
+    for what, args in refused.items():
+        assert _raw_call(b, *args, A, T) == ERR_ARG, what
+        assert _snapshot(b) == before, what
+    # arrays of a kind that does not occur may be missing; n_events == 0 changes nothing
+    assert _raw_call(b, 0, None, None, None, None, None, None, A, T) == 0
+    assert _raw_call(b, 0, k, d, r, e, a, c, A, T) == 0
+    assert _snapshot(b) == before, "n_events == 0"
+    assert _raw_call(b, 3, only_toa, d, r, e, None, None, A, T) == 0
+    assert _raw_call(b, 3, only_imu, d, None, None, a, c, A, T) == 0
+    assert _snapshot(b) != before
+    b.close()
+
+    # another model
+    b6 = capi.KfposBank(capi.MODEL_TOA, T, inp.w.anchors, storage=capi.STORE_MIXED, init_pos=inp.w.init_positions())
+    b6.step_toa_dev(r[0], e, 0.1)
+    before = _snapshot(b6)
+    assert _raw_call(b6, 9, k, d, r, e, a, c, A, T) == ERR_MODEL
+    assert _raw_call(b6, 3, only_toa, d, r, e, None, None, A, T) == ERR_MODEL
+    assert _snapshot(b6) == before
+    b6.close()
+
+    # a 9-state handle whose anchors are not set: ranging events are refused, IMU events run
+    lib = capi.load()
+    cfg = capi._Config()
+    cfg.model, cfg.n_tags, cfg.max_anchors, cfg.storage = capi.MODEL_TOA_IMU, T, A, capi.STORE_MIXED
+    cfg.accel_noise, cfg.jolt, cfg.cost_threshold, cfg.use_init_pos = 0.5, 0.5, 0.5, 1
+    cfg.init_pos = (ctypes.c_double * 3)(5.0, 5.0, 1.0)
+    h = ctypes.c_void_p()
+    assert lib.kfpos_create(ctypes.byref(cfg), ctypes.byref(h)) == 0
+    bare = capi.KfposBank.__new__(capi.KfposBank)
+    bare.lib, bare._h, bare.T, bare.A, bare.model, bare.storage = lib, h, T, A, capi.MODEL_TOA_IMU, capi.STORE_MIXED
+    bare.n = lib.kfpos_state_dim(h)
+    assert lib.kfpos_init(h) == 0
+    before = _snapshot(bare)
+    assert _raw_call(bare, 9, k, d, r, e, a, c, A, T) == ERR_STATE
+    assert _snapshot(bare) == before
+    assert _raw_call(bare, 3, only_imu, d, None, None, a, c, A, T) == 0
+    assert _snapshot(bare) != before
+    bare.close()
