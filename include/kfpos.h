@@ -463,6 +463,42 @@ int kfpos_run_events_dev(kfpos_handle *h, int32_t n_events,
                          const void *cov,
                          double *trajectory, uint32_t *status_events, uint32_t *status, void *stream);
 
+/* Replay a multi-sensor event schedule of the 8-state planar filter (KFPOS_MODEL_PLANAR) resident in HBM, in the
+ * node's own call sequence: ranging epochs plus PX4Flow, IMU, magnetometer and compass samples, each at its own rate
+ * and its own timeLag (KalmanFilter.cpp:84-229). Equivalent, bit for bit, to the same events as single calls in order
+ * -- a KFPOS_PLANAR_EVENT_TOA event is kfpos_step_toa_dev(range_j, err_j, NULL, dt_e, ...), an event of kind
+ * KFPOS_SENSOR_* is kfpos_step_sensor_dev(kind, sample_i, NULL, dt_e, ...): state, height, covariance as the handle
+ * stores it (compact storage is rounded after every event), flags, all 15 latch rows, every status word and
+ * trajectory row -- but up to 128 events run inside ONE launch with every tag's state and latched samples resident in
+ * registers (KFPOS_TRACE_CHUNK_STEPS applies, as in kfpos_run_trace_dev). A PX4Flow sample of quality 0 is dropped
+ * per tag, as the single call drops it: that tag sits the event out (status KFPOS_ST_SKIPPED, trajectory row = the
+ * untouched position). Ranging events ahead of the call's first sensor event on a handle that never had a sensor
+ * sample run the ranging-only kernel, as single calls would.
+ *   kinds, dt_events  HOST arrays of n_events entries: what each event is (0..4), and its timeLag, shared by all tags
+ *   in                device pointers, component-major; the n-th event of a kind reads base + n * stride elements.
+ *                     Arrays of kinds that do not occur may be NULL. Zero-initialise the struct.
+ *   trajectory        [n_events][3][n_tags] double or NULL: x, y, height after every event
+ *   status_events     [n_events][n_tags] status word of every event, or NULL
+ *   status            [n_tags] status words of the LAST event, or NULL
+ * Decided on the host before anything is enqueued: NULL handle, n_events < 0, a kind outside 0..4, missing kinds /
+ * dt_events / in, or a missing array for a kind that occurs -> KFPOS_ERR_ARG (kfpos_last_error() names the first
+ * offending event); a handle of another model -> KFPOS_ERR_MODEL; anchors unset with at least one ranging event ->
+ * KFPOS_ERR_STATE. n_events == 0 is KFPOS_OK and changes nothing. KFPOS_VERSION is unchanged: detect the call by
+ * symbol. */
+#define KFPOS_PLANAR_EVENT_TOA 0 /* newTOAMeasurement; the other kinds are KFPOS_SENSOR_PX4FLOW .. _COMPASS (1..4) */
+typedef struct kfpos_planar_inputs {
+    const int32_t *range_mm; int64_t stride_ranges;  /* j-th ranging event: [max_anchors][n_tags] */
+    const void    *err_est;  int64_t stride_err;     /* kfpos_real; stride may be 0: one array */
+    const double  *px4flow;  int64_t stride_px4flow; /* i-th PX4Flow event: [5][n_tags] */
+    const double  *imu;      int64_t stride_imu;     /* [24][n_tags] */
+    const double  *mag;      int64_t stride_mag;     /* [3][n_tags] */
+    const double  *compass;  int64_t stride_compass; /* [1][n_tags] */
+} kfpos_planar_inputs;
+int kfpos_run_planar_events_dev(kfpos_handle *h, int32_t n_events,
+                                const uint8_t *kinds, const double *dt_events,
+                                const kfpos_planar_inputs *in,
+                                double *trajectory, uint32_t *status_events, uint32_t *status, void *stream);
+
 /* ---- multi-GPU: contiguous tag shards + ONE collective, the RCCL all-gather of poses ----
  * The reference runs one filter in one process (node_pos.cpp:176-181) and has no counterpart. Here a node that serves
  * more tags than one GPU holds cuts the batch into contiguous ranges, one handle per GPU; the filters never talk to each

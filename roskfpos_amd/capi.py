@@ -31,6 +31,7 @@ EXPORTS = [
     "kfpos_get_pose_each", "kfpos_get_predicted",
     "kfpos_state_dim", "kfpos_get_state", "kfpos_set_state", "kfpos_step_toa_dev", "kfpos_step_imu_dev",
     "kfpos_step_toa_imu_dev", "kfpos_get_pose_dev", "kfpos_run_trace_dev", "kfpos_run_events_dev",
+    "kfpos_run_planar_events_dev",
     "kfpos_last_error",
     "kfpos_strerror", "kfpos_version", "kfpos_timing_begin", "kfpos_timing_end",
     "kfpos_set_planar", "kfpos_step_sensor", "kfpos_step_sensor_dev", "kfpos_get_height", "kfpos_set_height",
@@ -48,6 +49,7 @@ GATHER_COLLECTIVE, GATHER_DIRECT = 0, 1
 COMM_ID_BYTES = 128
 SLOT_TOA, SLOT_IMU, SLOT_TOA_IMU = 0, 1, 2
 EVENT_IMU, EVENT_TOA = 0, 1  # kfpos_run_events_dev: newIMUMeasurement / newTOAMeasurement
+PLANAR_EVENT_TOA = 0  # kfpos_run_planar_events_dev: newTOAMeasurement; the other kinds are SENSOR_PX4FLOW .. SENSOR_COMPASS
 SLOT_DT_PER_TAG, SLOT_REUSE_ERR, SLOT_REUSE_COV, SLOT_NO_POSE = 0x100, 0x200, 0x400, 0x800
 
 
@@ -84,6 +86,13 @@ class _RowsSlot(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("range_mm", C.c_void_p), ("err_est", C.c_void_p), ("accel", C.c_void_p),
                 ("cov", C.c_void_p), ("dt", C.c_void_p), ("status", C.c_void_p), ("pos", C.c_void_p),
                 ("capacity", C.c_int32)]
+
+
+class PlanarInputs(C.Structure):
+    """kfpos_planar_inputs: device pointers and strides (elements) of a planar event schedule's inputs."""
+    _fields_ = [("range_mm", C.c_void_p), ("stride_ranges", C.c_int64), ("err_est", C.c_void_p), ("stride_err", C.c_int64),
+                ("px4flow", C.c_void_p), ("stride_px4flow", C.c_int64), ("imu", C.c_void_p), ("stride_imu", C.c_int64),
+                ("mag", C.c_void_p), ("stride_mag", C.c_int64), ("compass", C.c_void_p), ("stride_compass", C.c_int64)]
 
 
 _lib = None
@@ -134,6 +143,7 @@ def load():
     L.kfpos_run_trace_dev.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64,
                                       vp, vp, vp, vp]
     sig("kfpos_run_events_dev", [vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp])
+    sig("kfpos_run_planar_events_dev", [vp, i32, vp, vp, C.POINTER(PlanarInputs), vp, vp, vp, vp])
     sig("kfpos_set_planar", [vp, C.POINTER(PlanarConfig)])
     sig("kfpos_step_sensor", [vp, i32, vp, vp, i32, vp])
     sig("kfpos_step_sensor_dev", [vp, i32, vp, vp, f64, vp, vp])
@@ -554,6 +564,23 @@ class KfposBank:
                                                 stride_ranges, _ptr(err_est), stride_err, _ptr(accel), stride_accel,
                                                 _ptr(cov), _ptr(trajectory), _ptr(status_events), _ptr(status),
                                                 _ptr(stream)))
+
+    def run_planar_events_dev(self, kinds, dt_events, range_mm=None, stride_ranges=0, err_est=None, stride_err=0,
+                              px4flow=None, stride_px4flow=0, imu=None, stride_imu=0, mag=None, stride_mag=0,
+                              compass=None, stride_compass=0, trajectory=None, status_events=None, status=None,
+                              stream=None):
+        """kfpos_run_planar_events_dev (MODEL_PLANAR): kinds (PLANAR_EVENT_TOA, SENSOR_PX4FLOW .. SENSOR_COMPASS) and
+        dt_events are host arrays of one entry per event; the n-th event of a kind reads that kind's array + n * stride
+        elements ([A][T] ranges and errorEstimations, [5][T], [24][T], [3][T], [1][T] samples). Bit for bit the same
+        events as single step_toa_dev / step_sensor_dev calls."""
+        k = np.ascontiguousarray(kinds, dtype=np.uint8)
+        d = np.ascontiguousarray(dt_events, dtype=np.float64)
+        assert k.ndim == 1 and d.shape == k.shape
+        inp = PlanarInputs(_ptr(range_mm), stride_ranges, _ptr(err_est), stride_err, _ptr(px4flow), stride_px4flow,
+                           _ptr(imu), stride_imu, _ptr(mag), stride_mag, _ptr(compass), stride_compass)
+        self._chk(self.lib.kfpos_run_planar_events_dev(self._h, k.size, k.ctypes.data, d.ctypes.data, C.byref(inp),
+                                                       _ptr(trajectory), _ptr(status_events), _ptr(status),
+                                                       _ptr(stream)))
 
     def timing_begin(self, stream=None):
         self._chk(self.lib.kfpos_timing_begin(self._h, _ptr(stream)))

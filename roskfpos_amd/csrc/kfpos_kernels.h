@@ -24,7 +24,7 @@
  *    shuffle and no barrier (the exception: the 8-lanes-per-tag kernel of small banks, kfpos_k_coop.hip).
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
- * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_misc (8-state planar
+ * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_misc (8-state planar
  * filter, standalone ML estimator, getPose, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
@@ -112,6 +112,21 @@ static_assert(KFPOS_TRACE_CHUNK == 128, "EvArgs::kinds is indexed as two 64-bit 
 static_assert(sizeof(EvArgs) <= 4096, "kernel arguments are limited to 4 KB");
 typedef void (*events_kernel_t)(const EvArgs);
 
+/* kfpos_run_planar_events_dev (kfpos_k_planarev.hip): the planar filter's argument block around KArgs, unchanged as
+ * well. k.n_steps events; k.dt_steps[e] is the timeLag of event e; its kind (0 = ranging, KFPOS_SENSOR_* otherwise)
+ * is nibble e of `kinds`; the j-th ranging event of the launch reads k.ranges / k.err + j * stride, the i-th event of
+ * sensor kind c sens[c - 1] + i * stride_sens[c - 1]; k.traj / status_events start at the launch's first event;
+ * k.status: the last event's words, or null. */
+struct PevArgs {
+    KArgs k;
+    uint32_t kinds[KFPOS_TRACE_CHUNK / 8];
+    const double *sens[4];     /* PX4Flow [5][T], IMU [24][T], magnetometer [3][T], compass [1][T] */
+    long long stride_sens[4];
+    uint32_t *status_events;   /* [n_steps][T] or null */
+};
+static_assert(sizeof(PevArgs) <= 4096, "kernel arguments are limited to 4 KB");
+typedef void (*planar_events_kernel_t)(const PevArgs);
+
 /* ---- selectors: each is defined in the translation unit that instantiates the kernels it hands out ----
  * st = KFPOS_STORE_*; as = anchor-count specialisation (8: epoch in registers; -8 / -16: compile-time loops over an
  * LDS-resident epoch; 0: run-time loop); heur: 0 = no outlier heuristic, 1 = top-N only, 2 = leave-one-out */
@@ -120,6 +135,7 @@ step_kernel_t toa6_full_kernel(int st, int as, int heur);                  /* kf
 step_kernel_t toa6_coop_kernel(int st);                                    /* kfpos_k_coop.hip */
 step_kernel_t imu9_kernel(int st, int as, bool ranging);                   /* kfpos_k_imu9.hip */
 events_kernel_t imu9_events_kernel(int st, int as);                        /* kfpos_k_imu9ev.hip: as = 8 or 0 */
+planar_events_kernel_t planar_events_kernel(int st, int as);               /* kfpos_k_planarev.hip: as = -8 or 0 */
 step_kernel_t ml_kernel(int st, int as);                                   /* kfpos_k_misc.hip */
 step_kernel_t planar_kernel(int st, bool sensors, int as);                 /* kfpos_k_misc.hip */
 void launch_get_pose(int model, bool full, int st, int blocks, hipStream_t s, const PoseArgs &a); /* kfpos_k_misc.hip */
