@@ -463,6 +463,47 @@ int kfpos_run_events_dev(kfpos_handle *h, int32_t n_events,
                          const void *cov,
                          double *trajectory, uint32_t *status_events, uint32_t *status, void *stream);
 
+/* kfpos_run_events_dev for a bank whose tags each have a timeline of their own (the name follows kfpos_get_pose_each):
+ * every tag carries its IMU on its own clock, ranging rounds reach tags at different moments, and in any round some
+ * tags are absent. The caller merges the tags' timelines into event SLOTS. A slot's kind is shared by the bank; who
+ * takes part in it, and at which timeLag, is per tag: dt_events_dev[e * n_tags + t] < 0.0 means tag t sits slot e out
+ * (exactly this predicate, as in every single call with a dt array: a NaN dt runs the event). Tags that have nothing
+ * in a slot get a negative dt.
+ * Equivalent, bit for bit, to the slots as single calls in order -- kfpos_step_imu_dev(accel_i, cov,
+ * dt_events_dev + e * n_tags, 0, ...) for a KFPOS_EVENT_IMU slot, kfpos_step_toa_dev(range_j, err_j,
+ * dt_events_dev + e * n_tags, 0, ...) for a KFPOS_EVENT_TOA slot: state, covariance as the handle stores it (compact
+ * storage is rounded after every event a tag ran), flags, the latched sample and its six latched covariance entries,
+ * every status word and trajectory row -- but up to 128 slots run inside ONE launch (KFPOS_TRACE_CHUNK_STEPS applies).
+ * A tag that sits a slot out: its status_events word is KFPOS_ST_SKIPPED, its trajectory row is its untouched position,
+ * nothing of it changes, and the slot's input entries for it are never used (they may be NaN). A tag that runs no event
+ * of the call keeps every stored byte: the flags word (a fresh tag stays not started), the latch, compact covariance
+ * planes.
+ * The latched sample: a tag's TOA events ahead of ITS OWN first IMU event in the call re-fuse what that tag had latched
+ * before the call, with that sample's covariance, or nothing; from its first IMU event on the tag uses `cov`. At the end
+ * only tags that sampled in the call have their last sample and `cov` latched.
+ *   kinds             HOST array of n_events entries: KFPOS_EVENT_IMU / KFPOS_EVENT_TOA
+ *   dt_events_dev     DEVICE, [n_events][n_tags] double: each tag's timeLag in each slot, < 0 = absent
+ *   range_mm, err_est the j-th TOA slot reads base + j * stride elements (stride_err may be 0: one array); j counts
+ *                     slots, not a tag's own events
+ *   accel             the i-th IMU slot reads base + i * stride_accel elements
+ *   cov               [9][n_tags], ONE array for the whole call (a covariance per sample: use the single calls)
+ *   trajectory        [n_events][3][n_tags] double or NULL: the position after every slot
+ *   status_events     [n_events][n_tags] status word of every slot, or NULL
+ *   status            [n_tags] status words of the LAST slot (KFPOS_ST_SKIPPED for tags absent from it), or NULL
+ * Decided on the host before anything is enqueued: NULL handle, n_events < 0, NULL kinds or dt_events_dev with
+ * n_events > 0, a kind other than 0 or 1 (kfpos_last_error() names the event), or a missing array for a kind that
+ * occurs -> KFPOS_ERR_ARG; a handle of another model -> KFPOS_ERR_MODEL; anchors unset with at least one TOA slot ->
+ * KFPOS_ERR_STATE. n_events == 0 is KFPOS_OK and touches nothing; accel / cov may be NULL when no IMU slot occurs,
+ * range_mm / err_est when no TOA slot does. KFPOS_VERSION is unchanged: detect the call by symbol. */
+int kfpos_run_events_each_dev(kfpos_handle *h, int32_t n_events,
+                              const uint8_t *kinds,          /* HOST, n_events: KFPOS_EVENT_IMU / KFPOS_EVENT_TOA */
+                              const double *dt_events_dev,   /* DEVICE, [n_events][n_tags] */
+                              const int32_t *range_mm, int64_t stride_ranges,
+                              const void *err_est, int64_t stride_err,
+                              const void *accel, int64_t stride_accel,
+                              const void *cov,
+                              double *trajectory, uint32_t *status_events, uint32_t *status, void *stream);
+
 /* Replay a multi-sensor event schedule of the 8-state planar filter (KFPOS_MODEL_PLANAR) resident in HBM, in the
  * node's own call sequence: ranging epochs plus PX4Flow, IMU, magnetometer and compass samples, each at its own rate
  * and its own timeLag (KalmanFilter.cpp:84-229). Equivalent, bit for bit, to the same events as single calls in order

@@ -31,7 +31,7 @@ EXPORTS = [
     "kfpos_get_pose_each", "kfpos_get_predicted",
     "kfpos_state_dim", "kfpos_get_state", "kfpos_set_state", "kfpos_step_toa_dev", "kfpos_step_imu_dev",
     "kfpos_step_toa_imu_dev", "kfpos_get_pose_dev", "kfpos_run_trace_dev", "kfpos_run_events_dev",
-    "kfpos_run_planar_events_dev",
+    "kfpos_run_events_each_dev", "kfpos_run_planar_events_dev",
     "kfpos_last_error",
     "kfpos_strerror", "kfpos_version", "kfpos_timing_begin", "kfpos_timing_end",
     "kfpos_set_planar", "kfpos_step_sensor", "kfpos_step_sensor_dev", "kfpos_get_height", "kfpos_set_height",
@@ -143,6 +143,7 @@ def load():
     L.kfpos_run_trace_dev.argtypes = [vp, i32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64,
                                       vp, vp, vp, vp]
     sig("kfpos_run_events_dev", [vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp])
+    sig("kfpos_run_events_each_dev", [vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp])
     sig("kfpos_run_planar_events_dev", [vp, i32, vp, vp, C.POINTER(PlanarInputs), vp, vp, vp, vp])
     sig("kfpos_set_planar", [vp, C.POINTER(PlanarConfig)])
     sig("kfpos_step_sensor", [vp, i32, vp, vp, i32, vp])
@@ -564,6 +565,24 @@ class KfposBank:
                                                 stride_ranges, _ptr(err_est), stride_err, _ptr(accel), stride_accel,
                                                 _ptr(cov), _ptr(trajectory), _ptr(status_events), _ptr(status),
                                                 _ptr(stream)))
+
+    def run_events_each_dev(self, kinds, dt_events_dev, range_mm=None, stride_ranges=0, err_est=None, stride_err=0,
+                            accel=None, stride_accel=0, cov=None, trajectory=None, status_events=None, status=None,
+                            stream=None):
+        """kfpos_run_events_each_dev: run_events_dev with a timeline per tag. kinds is a host array of one entry per
+        slot; dt_events_dev is a DEVICE array [n_events][T] of float64 (a torch tensor or a pointer): each tag's timeLag
+        in each slot, < 0 where the tag sits the slot out. The j-th TOA slot reads range_mm / err_est + j * stride, the
+        i-th IMU slot accel + i * stride_accel; cov is one [9][T] array for the call. Bit for bit the same slots as
+        single step_imu_dev / step_toa_dev calls with dt_dev = dt_events_dev[e]."""
+        k = np.ascontiguousarray(kinds, dtype=np.uint8)
+        assert k.ndim == 1
+        if hasattr(dt_events_dev, "data_ptr"):
+            assert tuple(dt_events_dev.shape) == (k.size, self.T) and dt_events_dev.is_contiguous()
+            assert dt_events_dev.element_size() == 8
+        self._chk(self.lib.kfpos_run_events_each_dev(self._h, k.size, k.ctypes.data, _ptr(dt_events_dev),
+                                                     _ptr(range_mm), stride_ranges, _ptr(err_est), stride_err,
+                                                     _ptr(accel), stride_accel, _ptr(cov), _ptr(trajectory),
+                                                     _ptr(status_events), _ptr(status), _ptr(stream)))
 
     def run_planar_events_dev(self, kinds, dt_events, range_mm=None, stride_ranges=0, err_est=None, stride_err=0,
                               px4flow=None, stride_px4flow=0, imu=None, stride_imu=0, mag=None, stride_mag=0,

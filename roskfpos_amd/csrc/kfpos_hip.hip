@@ -802,6 +802,80 @@ int kfpos_run_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds
     return KFPOS_OK;
 }
 
+int kfpos_run_events_each_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds, const double *dt_events_dev,
+                              const int32_t *range_mm, int64_t stride_ranges, const void *err_est, int64_t stride_err,
+                              const void *accel, int64_t stride_accel, const void *cov, double *trajectory,
+                              uint32_t *status_events, uint32_t *status, void *stream) {
+    g_err.clear();
+    if (!h || n_events < 0) return KFPOS_ERR_ARG;
+    if (n_events == 0) return KFPOS_OK;
+    if (!kinds || !dt_events_dev) return KFPOS_ERR_ARG;
+    int n_toa = 0, n_imu = 0;
+    for (int e = 0; e < n_events; ++e) {
+        if (kinds[e] == KFPOS_EVENT_TOA) ++n_toa;
+        else if (kinds[e] == KFPOS_EVENT_IMU) ++n_imu;
+        else {
+            g_err = "kfpos_run_events_each_dev: kinds[" + std::to_string(e) + "] = " + std::to_string((int)kinds[e]) + " is no event kind";
+            return KFPOS_ERR_ARG;
+        }
+    }
+    if ((n_toa && (!range_mm || !err_est)) || (n_imu && (!accel || !cov))) return KFPOS_ERR_ARG;
+    if (h->cfg.model != KFPOS_MODEL_TOA_IMU) return KFPOS_ERR_MODEL;
+    if (n_toa && !h->have_anchors) {
+        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
+        return KFPOS_ERR_STATE;
+    }
+    DevScope dev_(h->cfg.device);
+    const size_t T = h->cfg.n_tags, r = h->msz;
+    const hipStream_t s = (hipStream_t)stream;
+    /* No "lead" split as in kfpos_run_events_dev: which tags have ranging events ahead of their first sample is in
+     * dt_events_dev, which the host never reads. The kernel switches whiteners per lane instead -- the latched
+     * covariance's until the lane's own first sample, the call's from then on -- and every launch leaves the samples it
+     * took latched with `cov`, so the next launch (and whoever calls next) finds them where single calls leave them.
+     * LDS as k_events_imu9: CovPark9 alone (39.2 KB, four workgroups per CU), beside the generic epoch scratch of up
+     * to 64 anchors 96 + 39.2 = 135.2 KB of the CU's 160. */
+    const int as = (!h->force_generic && static_anchors(h) == 8) ? 8 : 0;
+    const kfpos_k::events_each_kernel_t kern = kfpos_k::imu9_events_each_kernel(h->cfg.storage, as);
+    const size_t lds = park9_bytes() + (as == 0 ? lds_bytes(h) : 0);
+    if (lds > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kfpos_k::EvEachArgs ev;
+    fill_args(h, ev.k);
+    ev.k.stride_ranges = stride_ranges;
+    ev.k.stride_err = stride_err;
+    ev.k.stride_accel = stride_accel;
+    for (double &d : ev.k.dt_steps) d = 0.0; /* unused by this kernel */
+    const int blocks = (int)((T + WAVE - 1) / WAVE);
+    size_t j = 0, i = 0; /* ranging / IMU slots consumed so far */
+    for (int e0 = 0; e0 < n_events; e0 += h->trace_chunk) {
+        const int n = n_events - e0 < h->trace_chunk ? n_events - e0 : h->trace_chunk;
+        ev.k.n_steps = n;
+        ev.k.ranges = range_mm ? range_mm + j * stride_ranges : nullptr;
+        ev.k.err = err_est ? (const char *)err_est + j * stride_err * r : nullptr;
+        ev.k.accel = accel ? (const char *)accel + i * stride_accel * r : nullptr;
+        ev.kinds[0] = ev.kinds[1] = 0;
+        bool imu_slot = false;
+        for (int k = 0; k < n; ++k) {
+            if (kinds[e0 + k] == KFPOS_EVENT_TOA) {
+                ev.kinds[k >> 6] |= 1ull << (k & 63);
+                ++j;
+            } else {
+                imu_slot = true;
+                ++i;
+            }
+        }
+        ev.k.cov = imu_slot ? cov : nullptr; /* the kernel whitens it only where a lane can come to use it */
+        ev.dt_each = dt_events_dev + (size_t)e0 * T;
+        ev.k.traj = trajectory ? trajectory + (size_t)e0 * 3 * T : nullptr;
+        ev.status_events = status_events ? status_events + (size_t)e0 * T : nullptr;
+        ev.k.status = e0 + n == n_events ? status : nullptr;
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), lds, s, ev);
+        HIPCHK(hipGetLastError());
+        h->stepped = true;
+    }
+    return KFPOS_OK;
+}
+
 int kfpos_run_planar_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds, const double *dt_events,
                                 const kfpos_planar_inputs *in, double *trajectory, uint32_t *status_events,
                                 uint32_t *status, void *stream) {

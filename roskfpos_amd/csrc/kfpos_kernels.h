@@ -24,7 +24,7 @@
  *    shuffle and no barrier (the exception: the 8-lanes-per-tag kernel of small banks, kfpos_k_coop.hip).
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
- * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_misc (8-state planar
+ * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_misc (8-state planar
  * filter, standalone ML estimator, getPose, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
@@ -112,6 +112,20 @@ static_assert(KFPOS_TRACE_CHUNK == 128, "EvArgs::kinds is indexed as two 64-bit 
 static_assert(sizeof(EvArgs) <= 4096, "kernel arguments are limited to 4 KB");
 typedef void (*events_kernel_t)(const EvArgs);
 
+/* kfpos_run_events_each_dev (kfpos_k_imu9each.hip): the same schedule with a timeline per tag, again a block of its own
+ * around an unchanged KArgs. `kinds` as in EvArgs -- a slot's kind is shared by the bank --, but the timeLag is per tag:
+ * dt_each[e * T + t] is tag t's in slot e of the launch, < 0 = the tag sits the slot out (k.dt_steps is unused). The
+ * ordinals of ranges and samples count SLOTS, not a tag's own events. k.cov is the one covariance of the call, null in
+ * a launch without an IMU slot. */
+struct EvEachArgs {
+    KArgs k;
+    unsigned long long kinds[KFPOS_TRACE_CHUNK / 64];
+    uint32_t *status_events; /* [n_steps][T] or null */
+    const double *dt_each;   /* DEVICE, [n_steps][T], at the launch's first slot */
+};
+static_assert(sizeof(EvEachArgs) <= 4096, "kernel arguments are limited to 4 KB");
+typedef void (*events_each_kernel_t)(const EvEachArgs);
+
 /* kfpos_run_planar_events_dev (kfpos_k_planarev.hip): the planar filter's argument block around KArgs, unchanged as
  * well. k.n_steps events; k.dt_steps[e] is the timeLag of event e; its kind (0 = ranging, KFPOS_SENSOR_* otherwise)
  * is nibble e of `kinds`; the j-th ranging event of the launch reads k.ranges / k.err + j * stride, the i-th event of
@@ -135,6 +149,7 @@ step_kernel_t toa6_full_kernel(int st, int as, int heur);                  /* kf
 step_kernel_t toa6_coop_kernel(int st);                                    /* kfpos_k_coop.hip */
 step_kernel_t imu9_kernel(int st, int as, bool ranging);                   /* kfpos_k_imu9.hip */
 events_kernel_t imu9_events_kernel(int st, int as);                        /* kfpos_k_imu9ev.hip: as = 8 or 0 */
+events_each_kernel_t imu9_events_each_kernel(int st, int as);              /* kfpos_k_imu9each.hip: as = 8 or 0 */
 planar_events_kernel_t planar_events_kernel(int st, int as);               /* kfpos_k_planarev.hip: as = -8 or 0 */
 step_kernel_t ml_kernel(int st, int as);                                   /* kfpos_k_misc.hip */
 step_kernel_t planar_kernel(int st, bool sensors, int as);                 /* kfpos_k_misc.hip */

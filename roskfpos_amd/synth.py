@@ -206,3 +206,92 @@ class Workload:
     def compass(self, step: int) -> np.ndarray:
         """(T,) compass heading in radians, unwrapped on purpose (newCompassMeasurement normalises once)."""
         return self.heading(self.time_of(step)) + self.MAG_SIGMA * self._noise(step, 234, 1)[:, 0]
+
+
+# -- per-tag timelines merged into event slots (kfpos_run_events_each_dev) ---------------------------------
+class EachSchedule:
+    """What merge_timelines returns. E slots, T tags:
+    kinds (E,) uint8        0 = IMU slot, 1 = TOA slot (capi.EVENT_IMU / EVENT_TOA)
+    dt    (E, T) float64    the tag's timeLag in the slot: time since its own previous event; -1.0 where it is absent
+    step  (E, T) int32      the Workload step (ranging period) the tag's event belongs to; -1 where it is absent
+    sub   (E, T) int32      IMU slots: which of the period's n_sub[t] samples (Workload.accel_between); -1 otherwise
+    n_sub (T,)   int32      IMU samples per ranging period of every tag
+    time  (E,)   float64    the instant of the slot"""
+
+    def __init__(self, kinds, dt, step, sub, n_sub, time):
+        self.kinds, self.dt, self.step, self.sub, self.n_sub, self.time = kinds, dt, step, sub, n_sub, time
+
+    @property
+    def present(self):
+        return ~(self.dt < 0.0)
+
+
+def tag_timeline(period: float, n_sub: int, phase: float, n_periods: int):
+    """One tag's own event sequence: [(time, kind, step, sub)], n_periods ranging periods of `period` seconds that
+    start `phase` seconds after t = 0, each with n_sub evenly spaced IMU samples ahead of its ranging epoch (the
+    spacing of Workload.accel_between)."""
+    out = []
+    for p in range(n_periods):
+        for i in range(n_sub):
+            out.append((phase + period * (p + (i + 1) / (n_sub + 1)), 0, p, i))
+        out.append((phase + period * (p + 1), 1, p, -1))
+    return out
+
+
+def merge_timelines(period, n_sub, phase, n_periods: int, tick: float = 1e-9) -> EachSchedule:
+    """Merge per-tag timelines (tag_timeline of period[t], n_sub[t], phase[t]; scalars broadcast) into the slots of
+    kfpos_run_events_each_dev. Events of the same kind whose times agree to `tick` seconds share a slot; slots are
+    ordered by time, an IMU slot ahead of a TOA slot of the same instant. A tag's dt in a slot is the time since its own
+    previous event (its first: since t = 0), so its dts add up to the time of its last event."""
+    n_sub = np.atleast_1d(np.asarray(n_sub, dtype=np.int32))
+    T = max(np.size(period), n_sub.size, np.size(phase))
+    period = np.broadcast_to(np.asarray(period, dtype=np.float64), (T,))
+    phase = np.broadcast_to(np.asarray(phase, dtype=np.float64), (T,))
+    n_sub = np.broadcast_to(n_sub, (T,)).copy()
+    lines = [tag_timeline(float(period[t]), int(n_sub[t]), float(phase[t]), n_periods) for t in range(T)]
+    key = lambda ev: (int(round(ev[0] / tick)), ev[1])  # noqa: E731
+    slots = sorted({key(ev) for line in lines for ev in line})
+    index = {k: e for e, k in enumerate(slots)}
+    E = len(slots)
+    dt = np.full((E, T), -1.0)
+    step = np.full((E, T), -1, dtype=np.int32)
+    sub = np.full((E, T), -1, dtype=np.int32)
+    for t, line in enumerate(lines):
+        prev = 0.0
+        for ev in line:
+            e = index[key(ev)]
+            if step[e, t] >= 0:
+                raise ValueError("tag %d has two events in one slot: its samples are closer than `tick`" % t)
+            dt[e, t], step[e, t], sub[e, t] = ev[0] - prev, ev[2], ev[3]
+            prev = ev[0]
+    kinds = np.array([k for _, k in slots], dtype=np.uint8)
+    time = np.array([q for q, _ in slots], dtype=np.float64) * tick
+    return EachSchedule(kinds, dt, step, sub, n_sub, time)
+
+
+def slot_inputs(w: "Workload", sched: EachSchedule, dtype=np.float64, epoch=None, absent_mm: int = -1):
+    """The inputs of a merged schedule in slot order: ranges (J, T, A) int32 of the J TOA slots, accel (I, T, 3) of the
+    I IMU slots. Every participating tag reads its own step / sub-sample (sched.step, sched.sub); entries of absent
+    tags are `absent_mm` / NaN. epoch(w, step) -> (T, A) replaces w.ranges_mm (tests: cases.Case.epoch)."""
+    epoch = epoch or (lambda w_, s: w_.ranges_mm(s))
+    T, A = w.n_tags, w.n_anchors
+    rows = np.arange(T)
+    ranges, accel = [], []
+    for e, kind in enumerate(sched.kinds):
+        here = sched.step[e] >= 0
+        if kind == 1:
+            r = np.full((T, A), absent_mm, dtype=np.int32)
+            for s in np.unique(sched.step[e][here]):
+                m = here & (sched.step[e] == s)
+                r[m] = epoch(w, int(s))[rows[m]]
+            ranges.append(r)
+        else:
+            a = np.full((T, 3), np.nan, dtype=dtype)
+            combos = {(int(s), int(i), int(k)) for s, i, k in zip(sched.step[e][here], sched.sub[e][here], sched.n_sub[here])}
+            for s, i, k in sorted(combos):
+                m = here & (sched.step[e] == s) & (sched.sub[e] == i) & (sched.n_sub == k)
+                a[m] = w.accel_between(s, i, k, dtype)[rows[m]]
+            accel.append(a)
+    J = np.stack(ranges) if ranges else np.zeros((0, T, A), dtype=np.int32)
+    I = np.stack(accel) if accel else np.zeros((0, T, 3), dtype=dtype)  # noqa: E741
+    return J, I
