@@ -540,6 +540,47 @@ int kfpos_run_planar_events_dev(kfpos_handle *h, int32_t n_events,
                                 const kfpos_planar_inputs *in,
                                 double *trajectory, uint32_t *status_events, uint32_t *status, void *stream);
 
+/* kfpos_run_planar_events_dev for a bank whose tags each have a timeline of their own (the planar counterpart of
+ * kfpos_run_events_each_dev): every robot carries its PX4Flow, IMU, magnetometer and compass on its own clock, ranging
+ * rounds reach tags at different moments, and in any round some tags are absent. The caller merges the tags' timelines
+ * into event SLOTS. A slot's kind is shared by the bank; who takes part in it, and at which timeLag, is per tag:
+ * dt_events_dev[e * n_tags + t] < 0.0 means tag t sits slot e out (exactly this predicate, as in every single call with
+ * a dt array: a NaN dt runs the event). Tags that have nothing in a slot get a negative dt.
+ * Equivalent, bit for bit, to the slots as single calls in order, each with the slot's row of dt_events_dev as the
+ * per-tag dt array -- kfpos_step_toa_dev(range_j, err_j, dt_events_dev + e * n_tags, 0, ...) for a
+ * KFPOS_PLANAR_EVENT_TOA slot, kfpos_step_sensor_dev(kind, sample_i, dt_events_dev + e * n_tags, 0, ...) for a
+ * KFPOS_SENSOR_* slot: state, height, covariance as the handle stores it (compact storage is rounded after every event
+ * a tag ran), flags, all 15 latch rows, every status word and trajectory row -- but up to 128 slots run inside ONE
+ * launch (KFPOS_TRACE_CHUNK_STEPS applies). The ordinals j and i count SLOTS of that kind, not a tag's own events.
+ * A tag that sits a slot out: its status_events word is KFPOS_ST_SKIPPED, its trajectory row is its untouched x, y,
+ * height, nothing of it changes, it does NOT latch the slot's sample (dt is looked at ahead of the sample), and the
+ * slot's input entries for it are never used (they may be NaN). A present tag whose PX4Flow sample has quality 0 is
+ * dropped as in the single call: KFPOS_ST_SKIPPED, an untouched row, nothing latched. A tag that runs no event of the
+ * call keeps every stored byte: position, velocity, compact covariance planes, latch rows and the flags word (a fresh
+ * tag stays not started).
+ * Latches: a slot carries what THAT tag has latched at that moment -- a compass slot the PX4Flow and IMU rows the tag
+ * latched before it, a ranging slot everything the tag has latched. At the end only the latch rows of kinds a tag
+ * sampled itself are written; rows never latched keep what the handle holds.
+ * Ranging slots ahead of the call's first sensor slot on a handle that never had a sensor sample run the ranging-only
+ * kernel, one launch per slot, as single calls would.
+ *   kinds             HOST array of n_events entries: 0..4 as in kfpos_run_planar_events_dev
+ *   dt_events_dev     DEVICE, [n_events][n_tags] double: each tag's timeLag in each slot, < 0.0 = absent
+ *   in                device pointers, component-major; the n-th slot of a kind reads base + n * stride elements.
+ *                     Arrays of kinds that do not occur may be NULL. Zero-initialise the struct.
+ *   trajectory        [n_events][3][n_tags] double or NULL: x, y, height after every slot
+ *   status_events     [n_events][n_tags] status word of every slot, or NULL
+ *   status            [n_tags] status words of the LAST slot (KFPOS_ST_SKIPPED for tags absent from it), or NULL
+ * Decided on the host before anything is enqueued: NULL handle, n_events < 0, NULL kinds / dt_events_dev / in with
+ * n_events > 0, a kind outside 0..4, or a missing array for a kind that occurs -> KFPOS_ERR_ARG (kfpos_last_error()
+ * names the first offending slot); a handle of another model -> KFPOS_ERR_MODEL; anchors unset with at least one
+ * ranging slot -> KFPOS_ERR_STATE. n_events == 0 is KFPOS_OK and touches nothing. The call runs on the handle's device
+ * and leaves the caller's current device as it was. KFPOS_VERSION is unchanged: detect the call by symbol. */
+int kfpos_run_planar_events_each_dev(kfpos_handle *h, int32_t n_events,
+                                     const uint8_t *kinds,          /* HOST, n_events: 0..4 as kfpos_run_planar_events_dev */
+                                     const double *dt_events_dev,   /* DEVICE, [n_events][n_tags]; < 0 = tag sits the slot out */
+                                     const kfpos_planar_inputs *in,
+                                     double *trajectory, uint32_t *status_events, uint32_t *status, void *stream);
+
 /* ---- multi-GPU: contiguous tag shards + ONE collective, the RCCL all-gather of poses ----
  * The reference runs one filter in one process (node_pos.cpp:176-181) and has no counterpart. Here a node that serves
  * more tags than one GPU holds cuts the batch into contiguous ranges, one handle per GPU; the filters never talk to each

@@ -31,7 +31,7 @@ EXPORTS = [
     "kfpos_get_pose_each", "kfpos_get_predicted",
     "kfpos_state_dim", "kfpos_get_state", "kfpos_set_state", "kfpos_step_toa_dev", "kfpos_step_imu_dev",
     "kfpos_step_toa_imu_dev", "kfpos_get_pose_dev", "kfpos_run_trace_dev", "kfpos_run_events_dev",
-    "kfpos_run_events_each_dev", "kfpos_run_planar_events_dev",
+    "kfpos_run_events_each_dev", "kfpos_run_planar_events_dev", "kfpos_run_planar_events_each_dev",
     "kfpos_last_error",
     "kfpos_strerror", "kfpos_version", "kfpos_timing_begin", "kfpos_timing_end",
     "kfpos_set_planar", "kfpos_step_sensor", "kfpos_step_sensor_dev", "kfpos_get_height", "kfpos_set_height",
@@ -145,6 +145,7 @@ def load():
     sig("kfpos_run_events_dev", [vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp])
     sig("kfpos_run_events_each_dev", [vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp])
     sig("kfpos_run_planar_events_dev", [vp, i32, vp, vp, C.POINTER(PlanarInputs), vp, vp, vp, vp])
+    sig("kfpos_run_planar_events_each_dev", [vp, i32, vp, vp, C.POINTER(PlanarInputs), vp, vp, vp, vp])
     sig("kfpos_set_planar", [vp, C.POINTER(PlanarConfig)])
     sig("kfpos_step_sensor", [vp, i32, vp, vp, i32, vp])
     sig("kfpos_step_sensor_dev", [vp, i32, vp, vp, f64, vp, vp])
@@ -600,6 +601,26 @@ class KfposBank:
         self._chk(self.lib.kfpos_run_planar_events_dev(self._h, k.size, k.ctypes.data, d.ctypes.data, C.byref(inp),
                                                        _ptr(trajectory), _ptr(status_events), _ptr(status),
                                                        _ptr(stream)))
+
+    def run_planar_events_each_dev(self, kinds, dt_events_dev, range_mm=None, stride_ranges=0, err_est=None,
+                                   stride_err=0, px4flow=None, stride_px4flow=0, imu=None, stride_imu=0, mag=None,
+                                   stride_mag=0, compass=None, stride_compass=0, trajectory=None, status_events=None,
+                                   status=None, stream=None):
+        """kfpos_run_planar_events_each_dev (MODEL_PLANAR): run_planar_events_dev with a timeline per tag. kinds is a
+        host array of one entry per slot; dt_events_dev is a DEVICE array [n_events][T] of float64 (a torch tensor or a
+        pointer): each tag's timeLag in each slot, < 0 where the tag sits the slot out. The n-th slot of a kind reads
+        that kind's array + n * stride elements. Bit for bit the same slots as single step_toa_dev / step_sensor_dev
+        calls with dt_dev = dt_events_dev[e]."""
+        k = np.ascontiguousarray(kinds, dtype=np.uint8)
+        assert k.ndim == 1
+        if hasattr(dt_events_dev, "data_ptr"):
+            assert tuple(dt_events_dev.shape) == (k.size, self.T) and dt_events_dev.is_contiguous()
+            assert dt_events_dev.element_size() == 8
+        inp = PlanarInputs(_ptr(range_mm), stride_ranges, _ptr(err_est), stride_err, _ptr(px4flow), stride_px4flow,
+                           _ptr(imu), stride_imu, _ptr(mag), stride_mag, _ptr(compass), stride_compass)
+        self._chk(self.lib.kfpos_run_planar_events_each_dev(self._h, k.size, k.ctypes.data, _ptr(dt_events_dev),
+                                                            C.byref(inp), _ptr(trajectory), _ptr(status_events),
+                                                            _ptr(status), _ptr(stream)))
 
     def timing_begin(self, stream=None):
         self._chk(self.lib.kfpos_timing_begin(self._h, _ptr(stream)))

@@ -978,6 +978,106 @@ int kfpos_run_planar_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t
     return KFPOS_OK;
 }
 
+int kfpos_run_planar_events_each_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds,
+                                     const double *dt_events_dev, const kfpos_planar_inputs *in, double *trajectory,
+                                     uint32_t *status_events, uint32_t *status, void *stream) {
+    g_err.clear();
+    if (!h || n_events < 0) return KFPOS_ERR_ARG;
+    if (n_events == 0) return KFPOS_OK;
+    if (!kinds || !dt_events_dev || !in) return KFPOS_ERR_ARG;
+    static const char *const names[5] = {"range_mm / err_est", "px4flow", "imu", "mag", "compass"};
+    const bool have[5] = {in->range_mm && in->err_est, in->px4flow != nullptr, in->imu != nullptr, in->mag != nullptr,
+                          in->compass != nullptr};
+    int n_toa = 0, first_sensor = -1;
+    for (int e = 0; e < n_events; ++e) {
+        const int kind = kinds[e];
+        if (kind > KFPOS_SENSOR_COMPASS) {
+            g_err = "kfpos_run_planar_events_each_dev: kinds[" + std::to_string(e) + "] = " + std::to_string(kind) + " is no event kind";
+            return KFPOS_ERR_ARG;
+        }
+        if (!have[kind]) {
+            g_err = "kfpos_run_planar_events_each_dev: kinds[" + std::to_string(e) + "] = " + std::to_string(kind) +
+                    " but kfpos_planar_inputs." + names[kind] + " is NULL";
+            return KFPOS_ERR_ARG;
+        }
+        if (kind == KFPOS_PLANAR_EVENT_TOA) ++n_toa;
+        else if (first_sensor < 0) first_sensor = e;
+    }
+    if (first_sensor < 0) first_sensor = n_events;
+    if (h->cfg.model != KFPOS_MODEL_PLANAR) return KFPOS_ERR_MODEL;
+    if (n_toa && !h->have_anchors) {
+        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
+        return KFPOS_ERR_STATE;
+    }
+    DevScope dev_(h->cfg.device);
+    const size_t T = h->cfg.n_tags, r = h->msz;
+    const hipStream_t s = (hipStream_t)stream;
+    /* WHICH ranging kernel runs is a property of the handle: on one that never had a sensor sample a single
+     * kfpos_step_toa_dev runs the closed-form ranging-only kernel for every tag, so the ranging slots ahead of the call's
+     * first sensor slot go down launch_step there -- one slot per launch, KArgs carries a per-tag dt with n_steps == 1
+     * only. On a handle that has planar_sensors set the single call is k_step_planar<true>, whose text
+     * k_events_planar_each runs: there the new kernel takes the call from its first slot (lead = 0), one launch
+     * instead of one per leading slot. */
+    const int lead = h->planar_sensors ? 0 : first_sensor;
+    for (int e = 0; e < lead; ++e) {
+        KArgs a;
+        fill_args(h, a);
+        a.mode = MODE_TOA;
+        a.ranges = in->range_mm + (size_t)e * in->stride_ranges;
+        a.err = (const char *)in->err_est + (size_t)e * in->stride_err * r;
+        a.dt = dt_events_dev + (size_t)e * T;
+        a.traj = trajectory ? trajectory + (size_t)e * 3 * T : nullptr;
+        a.status = status_events ? status_events + (size_t)e * T : (e + 1 == n_events ? status : nullptr);
+        const int rc = launch_step(h, a, s);
+        if (rc != KFPOS_OK) return rc;
+    }
+    if (lead == n_events) {
+        if (lead > 0 && status_events && status)
+            HIPCHK(hipMemcpyAsync(status, status_events + (size_t)(n_events - 1) * T, sizeof(uint32_t) * T,
+                                  hipMemcpyDeviceToDevice, s));
+        return KFPOS_OK;
+    }
+    /* From there on: k_events_planar_each, up to trace_chunk slots per launch. Every launch leaves the samples its lanes
+     * latched in HBM, so the next one (and whoever calls next) finds them where single calls leave them. LDS as
+     * k_events_planar: the epoch scratch and CovSpill8 behind it. */
+    const int as = (!h->force_generic && static_anchors(h) == 8) ? -8 : 0;
+    const kfpos_k::planar_events_each_kernel_t kern = kfpos_k::planar_events_each_kernel(h->cfg.storage, as);
+    const size_t lds = park_bytes() + (as == 0 ? lds_bytes(h) : (size_t)3 * 8 * WAVE * sizeof(double));
+    if (lds > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kfpos_k::PevEachArgs ev;
+    fill_args(h, ev.k);
+    ev.k.stride_ranges = in->stride_ranges;
+    ev.k.stride_err = in->stride_err;
+    for (double &d : ev.k.dt_steps) d = 0.0; /* unused by this kernel */
+    const double *const base[4] = {in->px4flow, in->imu, in->mag, in->compass};
+    const int64_t stride[4] = {in->stride_px4flow, in->stride_imu, in->stride_mag, in->stride_compass};
+    for (int c = 0; c < 4; ++c) ev.stride_sens[c] = stride[c];
+    const int blocks = (int)((T + WAVE - 1) / WAVE);
+    size_t ord[5] = {(size_t)lead, 0, 0, 0, 0}; /* slots of each kind consumed so far: they carry across launches */
+    for (int e0 = lead; e0 < n_events; e0 += h->trace_chunk) {
+        const int n = n_events - e0 < h->trace_chunk ? n_events - e0 : h->trace_chunk;
+        ev.k.n_steps = n;
+        ev.k.ranges = in->range_mm ? in->range_mm + ord[0] * in->stride_ranges : nullptr;
+        ev.k.err = in->err_est ? (const char *)in->err_est + ord[0] * in->stride_err * r : nullptr;
+        for (int c = 0; c < 4; ++c) ev.sens[c] = base[c] ? base[c] + ord[c + 1] * stride[c] : nullptr;
+        std::memset(ev.kinds, 0, sizeof(ev.kinds));
+        for (int k = 0; k < n; ++k) {
+            ev.kinds[k >> 3] |= (uint32_t)kinds[e0 + k] << ((k & 7) * 4);
+            ++ord[kinds[e0 + k]];
+        }
+        ev.dt_each = dt_events_dev + (size_t)e0 * T;
+        ev.k.traj = trajectory ? trajectory + (size_t)e0 * 3 * T : nullptr;
+        ev.status_events = status_events ? status_events + (size_t)e0 * T : nullptr;
+        ev.k.status = e0 + n == n_events ? status : nullptr;
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), lds, s, ev);
+        HIPCHK(hipGetLastError());
+        h->stepped = true;
+        h->planar_sensors = true; /* ranging epochs now carry the latched samples (kfpos_step_sensor_dev) */
+    }
+    return KFPOS_OK;
+}
+
 static int launch_pose(kfpos_handle *h, double dt_ahead, const double *dt_each, double *pos, double *cov3x3,
                        double *vel, uint32_t *status, void *stream, double *full_x = nullptr,
                        double *full_P = nullptr) {

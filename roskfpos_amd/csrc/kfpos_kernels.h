@@ -24,7 +24,7 @@
  *    shuffle and no barrier (the exception: the 8-lanes-per-tag kernel of small banks, kfpos_k_coop.hip).
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
- * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_misc (8-state planar
+ * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
  * filter, standalone ML estimator, getPose, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
@@ -141,6 +141,21 @@ struct PevArgs {
 static_assert(sizeof(PevArgs) <= 4096, "kernel arguments are limited to 4 KB");
 typedef void (*planar_events_kernel_t)(const PevArgs);
 
+/* kfpos_run_planar_events_each_dev (kfpos_k_planareach.hip): the planar schedule with a timeline per tag, once more a
+ * block of its own around an unchanged KArgs. kinds, sens, stride_sens and status_events as in PevArgs -- a slot's kind
+ * is shared by the bank --, but the timeLag is per tag: dt_each[e * T + t] is tag t's in slot e of the launch, < 0 = the
+ * tag sits the slot out (k.dt_steps is unused). The ordinals of ranges and samples count SLOTS, not a tag's own events. */
+struct PevEachArgs {
+    KArgs k;
+    uint32_t kinds[KFPOS_TRACE_CHUNK / 8];
+    const double *sens[4];     /* PX4Flow [5][T], IMU [24][T], magnetometer [3][T], compass [1][T] */
+    long long stride_sens[4];
+    uint32_t *status_events;   /* [n_steps][T] or null */
+    const double *dt_each;     /* DEVICE, [n_steps][T], at the launch's first slot */
+};
+static_assert(sizeof(PevEachArgs) <= 4096, "kernel arguments are limited to 4 KB");
+typedef void (*planar_events_each_kernel_t)(const PevEachArgs);
+
 /* ---- selectors: each is defined in the translation unit that instantiates the kernels it hands out ----
  * st = KFPOS_STORE_*; as = anchor-count specialisation (8: epoch in registers; -8 / -16: compile-time loops over an
  * LDS-resident epoch; 0: run-time loop); heur: 0 = no outlier heuristic, 1 = top-N only, 2 = leave-one-out */
@@ -151,6 +166,7 @@ step_kernel_t imu9_kernel(int st, int as, bool ranging);                   /* kf
 events_kernel_t imu9_events_kernel(int st, int as);                        /* kfpos_k_imu9ev.hip: as = 8 or 0 */
 events_each_kernel_t imu9_events_each_kernel(int st, int as);              /* kfpos_k_imu9each.hip: as = 8 or 0 */
 planar_events_kernel_t planar_events_kernel(int st, int as);               /* kfpos_k_planarev.hip: as = -8 or 0 */
+planar_events_each_kernel_t planar_events_each_kernel(int st, int as);     /* kfpos_k_planareach.hip: as = -8 or 0 */
 step_kernel_t ml_kernel(int st, int as);                                   /* kfpos_k_misc.hip */
 step_kernel_t planar_kernel(int st, bool sensors, int as);                 /* kfpos_k_misc.hip */
 void launch_get_pose(int model, bool full, int st, int blocks, hipStream_t s, const PoseArgs &a); /* kfpos_k_misc.hip */

@@ -295,3 +295,107 @@ def slot_inputs(w: "Workload", sched: EachSchedule, dtype=np.float64, epoch=None
     J = np.stack(ranges) if ranges else np.zeros((0, T, A), dtype=np.int32)
     I = np.stack(accel) if accel else np.zeros((0, T, 3), dtype=dtype)  # noqa: E741
     return J, I
+
+
+# -- per-tag timelines of the planar filter merged into event slots (kfpos_run_planar_events_each_dev) ------
+PLANAR_WIDTH = {1: 5, 2: 24, 3: 3, 4: 1}   # components of a PX4Flow / IMU / magnetometer / compass sample
+
+
+class PlanarEachSchedule:
+    """What merge_planar_timelines returns. E slots, T tags:
+    kinds   (E,)   uint8     0 = ranging slot, 1..4 = PX4Flow / IMU / magnetometer / compass slot
+    dt      (E, T) float64   the tag's timeLag in the slot: time since its own previous event; -1.0 where it is absent
+    ordinal (E, T) int32     which of the tag's OWN samples of that kind the slot carries; -1 where it is absent
+    time    (E,)   float64   the instant of the slot"""
+
+    def __init__(self, kinds, dt, ordinal, time):
+        self.kinds, self.dt, self.ordinal, self.time = kinds, dt, ordinal, time
+
+    @property
+    def present(self):
+        return ~(self.dt < 0.0)
+
+
+def planar_tag_timeline(period: float, phase: float, n_periods: int, n_imu: int = 10, n_px4: int = 2, n_mag: int = 1,
+                        n_compass: int = 0):
+    """One robot's own event sequence: [(time, kind, ordinal of its own sample of that kind)], n_periods ranging
+    periods of `period` seconds that start `phase` seconds after t = 0; inside each, every sensor's samples are evenly
+    spaced ahead of the period's ranging epoch (sample i of n at (i + 1) / (n + 1) of the period)."""
+    out = []
+    for p in range(n_periods):
+        inside = []
+        for kind, n in ((1, n_px4), (2, n_imu), (3, n_mag), (4, n_compass)):
+            inside += [(phase + period * (p + (i + 1) / (n + 1)), kind, p * n + i) for i in range(n)]
+        out += sorted(inside, key=lambda ev: (ev[0], ev[1]))
+        out.append((phase + period * (p + 1), 0, p))
+    return out
+
+
+def merge_planar_timelines(lines, tick: float = 1e-9) -> PlanarEachSchedule:
+    """Merge per-tag event lists [(time, kind, ordinal of the tag's own sample of that kind)] (kind 0 = ranging, 1..4 =
+    PX4Flow, IMU, magnetometer, compass) into the slots of kfpos_run_planar_events_each_dev. Time is counted in quanta
+    of `tick` seconds, round(time / tick): events of one kind in the same quantum share a slot (times that differ by
+    less than a tick but fall either side of a rounding boundary do not); slots are ordered by quantum, and within one
+    quantum the sensor slots come in kind order 1..4 ahead of the ranging slot. A tag's dt in a slot is the time since
+    its own previous event (its first: since t = 0), so its dts add up to the time of its last event. Events of one tag
+    in the same quantum are simultaneous at the clock's resolution and run in slot order, whatever their raw times say:
+    where that order turns two raw times round, the later slot gets dt = 0.0, never a negative dt, which the call would
+    read as "absent"."""
+    T = len(lines)
+    key = lambda ev: (int(round(ev[0] / tick)), 4 if ev[1] == 0 else int(ev[1]) - 1)  # noqa: E731
+    for line in lines:
+        for ev in line:
+            if not 0 <= int(ev[1]) <= 4:
+                raise ValueError("kind %r is no planar event kind" % (ev[1],))
+    slots = sorted({key(ev) for line in lines for ev in line})
+    index = {k: e for e, k in enumerate(slots)}
+    E = len(slots)
+    dt = np.full((E, T), -1.0)
+    ordinal = np.full((E, T), -1, dtype=np.int32)
+    for t, line in enumerate(lines):
+        prev = 0.0
+        for ev in sorted(line, key=key):
+            e = index[key(ev)]
+            if ordinal[e, t] >= 0:
+                raise ValueError("tag %d has two events in one slot: its samples are closer than `tick`" % t)
+            dt[e, t], ordinal[e, t] = max(ev[0] - prev, 0.0), ev[2]
+            prev = max(prev, ev[0])
+    kinds = np.array([0 if o == 4 else o + 1 for _, o in slots], dtype=np.uint8)
+    time = np.array([q for q, _ in slots], dtype=np.float64) * tick
+    return PlanarEachSchedule(kinds, dt, ordinal, time)
+
+
+def planar_sample(w: "Workload", kind: int, n: int) -> np.ndarray:
+    """(T, PLANAR_WIDTH[kind]) sample n of a sensor kind for every tag of the workload, in the layout of
+    kfpos_step_sensor_dev (IMU: angular velocity 3, its covariance 9, linear acceleration 3, its covariance 9)."""
+    if kind == 1:
+        return w.px4flow(n)
+    if kind == 2:
+        wv, la = w.planar_imu(n)
+        cw = np.tile(np.eye(3).ravel() * 1e-4, (w.n_tags, 1))
+        return np.concatenate([wv, cw, la, w.accel_cov()], axis=1)
+    if kind == 3:
+        return w.mag(n)
+    return w.compass(n)[:, None]
+
+
+def planar_slot_inputs(w: "Workload", sched: PlanarEachSchedule, absent_mm: int = -1, epoch=None, sample=None):
+    """The inputs of a merged planar schedule in slot order: {0: ranges (J, T, A) int32, 1: (n, T, 5), 2: (n, T, 24),
+    3: (n, T, 3), 4: (n, T, 1)}. Every participating tag reads its OWN sample sched.ordinal[e, t]; entries of absent
+    tags are NaN, `absent_mm` for ranges. epoch(w, n) -> (T, A) replaces w.ranges_mm, sample(w, kind, n) planar_sample."""
+    epoch = epoch or (lambda w_, n: w_.ranges_mm(n))
+    sample = sample or planar_sample
+    T, A = w.n_tags, w.n_anchors
+    out = {0: []}
+    out.update({k: [] for k in PLANAR_WIDTH})
+    for e, kind in enumerate(sched.kinds):
+        kind = int(kind)
+        here = sched.ordinal[e] >= 0
+        a = np.full((T, A), absent_mm, dtype=np.int32) if kind == 0 else np.full((T, PLANAR_WIDTH[kind]), np.nan)
+        for n in np.unique(sched.ordinal[e][here]):
+            m = here & (sched.ordinal[e] == n)
+            a[m] = (epoch(w, int(n)) if kind == 0 else sample(w, kind, int(n)))[m]
+        out[kind].append(a)
+    empty = {0: np.zeros((0, T, A), dtype=np.int32)}
+    empty.update({k: np.zeros((0, T, c)) for k, c in PLANAR_WIDTH.items()})
+    return {k: (np.stack(v) if v else empty[k]) for k, v in out.items()}
