@@ -504,6 +504,45 @@ int kfpos_run_events_each_dev(kfpos_handle *h, int32_t n_events,
                               const void *cov,
                               double *trajectory, uint32_t *status_events, uint32_t *status, void *stream);
 
+/* kfpos_run_trace_dev for a 6-state bank (KFPOS_MODEL_TOA) whose tags each have a timeline of their own (the ranging-only
+ * counterpart of kfpos_run_events_each_dev): tags range in their own TDMA slots, so each tag's timeLag is its own, and in
+ * any round part of the bank is silent. The caller merges the tags' timelines into SLOTS, every one a ranging epoch. Who
+ * takes part in a slot, and at which timeLag, is per tag: dt_steps_dev[s * n_tags + t] < 0.0 means tag t sits slot s out
+ * (exactly this predicate, as in every single call with a dt array: a NaN dt runs the slot). Tags that have nothing in a
+ * slot get a negative dt.
+ * Equivalent, bit for bit, to the slots as single calls in order -- kfpos_step_toa_dev(range_s, err_s,
+ * dt_steps_dev + s * n_tags, 0, ...): position, velocity, covariance as the handle stores it (compact storage is
+ * rounded after every slot a tag ran), flags, every status word (KFPOS_ST_NONFINITE judged after that slot) and every
+ * trajectory row -- but up to 128 slots run inside ONE launch with every tag's state resident in registers
+ * (KFPOS_TRACE_CHUNK_STEPS applies, as in kfpos_run_trace_dev), and a wavefront in which nobody takes part in a slot
+ * passes it. The ordinal s counts SLOTS, not a tag's own epochs.
+ * A tag that sits a slot out: its status_steps word is KFPOS_ST_SKIPPED, its trajectory row is its untouched stored
+ * position (NaN for a tag still waiting for its ML initialisation), nothing of it changes, and the slot's input entries
+ * for it are never used. A tag that runs no slot of the call keeps every stored byte: the flags word (a fresh tag stays
+ * not started) and the compact covariance planes.
+ * Not fused on one kind of handle: a small plain bank that runs the 8-lanes-per-tag kernel (at most 8 192 tags, fixed
+ * start, no outlier heuristic, at most 8 anchors; KFPOS_NO_COOP=1 disables it) computes in another summation order, so
+ * there the call runs its slots through that kernel, one launch per slot: the same bits as the handle's single calls,
+ * without the saving.
+ *   dt_steps_dev      DEVICE, [n_steps][n_tags] double: each tag's timeLag in each slot, < 0.0 = absent
+ *   range_mm, err_est slot s reads base + s * stride elements (stride_err may be 0: one array)
+ *   trajectory        [n_steps][3][n_tags] double or NULL: the position after every slot
+ *   status_steps      [n_steps][n_tags] status word of every slot, or NULL
+ *   status            [n_tags] status words of the LAST slot (KFPOS_ST_SKIPPED for tags absent from it), or NULL
+ * Decided on the host before anything is enqueued, in this order: NULL handle or n_steps < 0 -> KFPOS_ERR_ARG;
+ * n_steps == 0 -> KFPOS_OK, nothing touched; NULL dt_steps_dev, range_mm or err_est -> KFPOS_ERR_ARG; a handle that is
+ * not KFPOS_MODEL_TOA -> KFPOS_ERR_MODEL (9-state banks: kfpos_run_events_each_dev with all kinds KFPOS_EVENT_TOA;
+ * planar banks: kfpos_run_planar_events_each_dev); anchors unset -> KFPOS_ERR_STATE. The call runs on the handle's
+ * device and leaves the caller's current device as it was. KFPOS_VERSION is unchanged: detect the call by symbol. */
+int kfpos_run_trace_each_dev(kfpos_handle *h, int32_t n_steps,
+                             const double *dt_steps_dev,   /* DEVICE, [n_steps][n_tags]; < 0.0 = tag sits the slot out */
+                             const int32_t *range_mm, int64_t stride_ranges,
+                             const void *err_est, int64_t stride_err,      /* stride_err may be 0: one array */
+                             double *trajectory,           /* [n_steps][3][n_tags] or NULL */
+                             uint32_t *status_steps,       /* [n_steps][n_tags] or NULL */
+                             uint32_t *status,             /* [n_tags], the LAST slot's words, or NULL */
+                             void *stream);
+
 /* Replay a multi-sensor event schedule of the 8-state planar filter (KFPOS_MODEL_PLANAR) resident in HBM, in the
  * node's own call sequence: ranging epochs plus PX4Flow, IMU, magnetometer and compass samples, each at its own rate
  * and its own timeLag (KalmanFilter.cpp:84-229). Equivalent, bit for bit, to the same events as single calls in order

@@ -32,7 +32,7 @@ EXPORTS = [
     "kfpos_state_dim", "kfpos_get_state", "kfpos_set_state", "kfpos_step_toa_dev", "kfpos_step_imu_dev",
     "kfpos_step_toa_imu_dev", "kfpos_get_pose_dev", "kfpos_run_trace_dev", "kfpos_run_events_dev",
     "kfpos_run_events_each_dev", "kfpos_run_planar_events_dev", "kfpos_run_planar_events_each_dev",
-    "kfpos_last_error",
+    "kfpos_run_trace_each_dev", "kfpos_last_error",
     "kfpos_strerror", "kfpos_version", "kfpos_timing_begin", "kfpos_timing_end",
     "kfpos_set_planar", "kfpos_step_sensor", "kfpos_step_sensor_dev", "kfpos_get_height", "kfpos_set_height",
     "kfpos_latch_dim", "kfpos_get_latch", "kfpos_set_latch",
@@ -146,6 +146,7 @@ def load():
     sig("kfpos_run_events_each_dev", [vp, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp])
     sig("kfpos_run_planar_events_dev", [vp, i32, vp, vp, C.POINTER(PlanarInputs), vp, vp, vp, vp])
     sig("kfpos_run_planar_events_each_dev", [vp, i32, vp, vp, C.POINTER(PlanarInputs), vp, vp, vp, vp])
+    sig("kfpos_run_trace_each_dev", [vp, i32, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp])
     sig("kfpos_set_planar", [vp, C.POINTER(PlanarConfig)])
     sig("kfpos_step_sensor", [vp, i32, vp, vp, i32, vp])
     sig("kfpos_step_sensor_dev", [vp, i32, vp, vp, f64, vp, vp])
@@ -621,6 +622,18 @@ class KfposBank:
         self._chk(self.lib.kfpos_run_planar_events_each_dev(self._h, k.size, k.ctypes.data, _ptr(dt_events_dev),
                                                             C.byref(inp), _ptr(trajectory), _ptr(status_events),
                                                             _ptr(status), _ptr(stream)))
+
+    def run_trace_each_dev(self, dt_steps_dev, range_mm, stride_ranges, err_est, stride_err=0, trajectory=None,
+                           status_steps=None, status=None, stream=None):
+        """kfpos_run_trace_each_dev (MODEL_TOA): ranging slots with a timeline per tag. dt_steps_dev is a DEVICE array
+        [n_steps][T] of float64 (a torch tensor; its first dimension is the number of slots): each tag's timeLag in each
+        slot, < 0 where the tag sits the slot out. Slot s reads range_mm / err_est + s * stride. Bit for bit the same
+        slots as single step_toa_dev calls with dt_dev = dt_steps_dev[s]."""
+        assert dt_steps_dev.dim() == 2 and dt_steps_dev.shape[1] == self.T and dt_steps_dev.is_contiguous()
+        assert dt_steps_dev.element_size() == 8
+        self._chk(self.lib.kfpos_run_trace_each_dev(self._h, int(dt_steps_dev.shape[0]), _ptr(dt_steps_dev),
+                                                    _ptr(range_mm), stride_ranges, _ptr(err_est), stride_err,
+                                                    _ptr(trajectory), _ptr(status_steps), _ptr(status), _ptr(stream)))
 
     def timing_begin(self, stream=None):
         self._chk(self.lib.kfpos_timing_begin(self._h, _ptr(stream)))

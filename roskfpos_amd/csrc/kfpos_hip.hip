@@ -876,6 +876,78 @@ int kfpos_run_events_each_dev(kfpos_handle *h, int32_t n_events, const uint8_t *
     return KFPOS_OK;
 }
 
+int kfpos_run_trace_each_dev(kfpos_handle *h, int32_t n_steps, const double *dt_steps_dev, const int32_t *range_mm,
+                             int64_t stride_ranges, const void *err_est, int64_t stride_err, double *trajectory,
+                             uint32_t *status_steps, uint32_t *status, void *stream) {
+    g_err.clear();
+    if (!h || n_steps < 0) return KFPOS_ERR_ARG;
+    if (n_steps == 0) return KFPOS_OK;
+    if (!dt_steps_dev || !range_mm || !err_est) return KFPOS_ERR_ARG;
+    if (h->cfg.model != KFPOS_MODEL_TOA) return KFPOS_ERR_MODEL;
+    if (!h->have_anchors) {
+        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
+        return KFPOS_ERR_STATE;
+    }
+    DevScope dev_(h->cfg.device);
+    const size_t T = h->cfg.n_tags, r = h->msz;
+    const hipStream_t s = (hipStream_t)stream;
+    /* The 8-lanes-per-tag kernel sums in another order and has a contraction mode of its own (kfpos_k_coop.hip): a
+     * one-tag-per-lane replay would not match what this handle's single calls compute. Such a handle runs its slots
+     * as those single calls, one launch each: the same bits, not fused. */
+    if (h->coop) {
+        KArgs a;
+        fill_args(h, a);
+        a.mode = MODE_TOA;
+        for (int e = 0; e < n_steps; ++e) {
+            a.ranges = range_mm + (size_t)e * stride_ranges;
+            a.err = (const char *)err_est + (size_t)e * stride_err * r;
+            a.dt = dt_steps_dev + (size_t)e * T;
+            a.traj = trajectory ? trajectory + (size_t)e * 3 * T : nullptr;
+            a.status = status_steps ? status_steps + (size_t)e * T : (e + 1 == n_steps ? status : nullptr);
+            const int rc = launch_step(h, a, s);
+            if (rc != KFPOS_OK) return rc;
+        }
+        if (status_steps && status)
+            HIPCHK(hipMemcpyAsync(status, status_steps + (size_t)(n_steps - 1) * T, sizeof(uint32_t) * T,
+                                  hipMemcpyDeviceToDevice, s));
+        return KFPOS_OK;
+    }
+    /* k_trace_toa6_each, up to trace_chunk slots per launch; a bank with more wavefronts than SIMDs runs it too (the
+     * two-wavefront build of the single calls computes the same bits). The kernel and its LDS follow the handle as
+     * step_kernel() / launch_step() do: the epoch of the LDS forms (4-byte errorEstimations kept as they are where the
+     * anchor count is a compile-time one), and Pinv6 of the non-symmetric layout behind it. */
+    const int as = h->force_generic ? 0 : static_anchors(h);
+    const int heur = h->cfg.ignore_worst != 0 ? 2 : (h->cfg.top_n != 0 ? 1 : 0);
+    const kfpos_k::trace_each_kernel_t kern = h->full ? kfpos_k::toa6_each_full_kernel(h->cfg.storage, as, heur)
+                                                      : kfpos_k::toa6_each_sym_kernel(h->cfg.storage, as, heur);
+    size_t lds = (as == 8 && !h->full) ? 0 : lds_bytes(h);
+    if (lds && as != 0 && h->msz == 4) lds = lds * 5 / 6;
+    if (h->full) lds += park_bytes();
+    if (lds > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kfpos_k::TraceEachArgs ev;
+    fill_args(h, ev.k);
+    ev.k.mode = MODE_TOA;
+    ev.k.stride_ranges = stride_ranges;
+    ev.k.stride_err = stride_err;
+    for (double &d : ev.k.dt_steps) d = 0.0; /* unused by this kernel */
+    const int blocks = (int)((T + WAVE - 1) / WAVE);
+    for (int e0 = 0; e0 < n_steps; e0 += h->trace_chunk) {
+        const int n = n_steps - e0 < h->trace_chunk ? n_steps - e0 : h->trace_chunk;
+        ev.k.n_steps = n;
+        ev.k.ranges = range_mm + (size_t)e0 * stride_ranges;
+        ev.k.err = (const char *)err_est + (size_t)e0 * stride_err * r;
+        ev.dt_each = dt_steps_dev + (size_t)e0 * T;
+        ev.k.traj = trajectory ? trajectory + (size_t)e0 * 3 * T : nullptr;
+        ev.status_steps = status_steps ? status_steps + (size_t)e0 * T : nullptr;
+        ev.k.status = e0 + n == n_steps ? status : nullptr;
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), lds, s, ev);
+        HIPCHK(hipGetLastError());
+        h->stepped = true;
+    }
+    return KFPOS_OK;
+}
+
 int kfpos_run_planar_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds, const double *dt_events,
                                 const kfpos_planar_inputs *in, double *trajectory, uint32_t *status_events,
                                 uint32_t *status, void *stream) {

@@ -24,7 +24,7 @@
  *    shuffle and no barrier (the exception: the 8-lanes-per-tag kernel of small banks, kfpos_k_coop.hip).
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
- * full covariance layout), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
+ * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
  * filter, standalone ML estimator, getPose, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
@@ -126,6 +126,19 @@ struct EvEachArgs {
 static_assert(sizeof(EvEachArgs) <= 4096, "kernel arguments are limited to 4 KB");
 typedef void (*events_each_kernel_t)(const EvEachArgs);
 
+/* kfpos_run_trace_each_dev (kfpos_k_toa6eachs.hip / kfpos_k_toa6eachf.hip): ranging slots of the 6-state filter with a
+ * timeline per tag, a block of its own around an unchanged KArgs as well. Every slot is a ranging epoch, so there are no
+ * kinds: slot e of the launch reads k.ranges / k.err + e * stride, dt_each[e * T + t] is tag t's timeLag in it, < 0 =
+ * the tag sits the slot out (k.dt_steps is unused). k.traj / status_steps start at the launch's first slot; k.status:
+ * the last slot's words, or null. */
+struct TraceEachArgs {
+    KArgs k;
+    uint32_t *status_steps;  /* [n_steps][T] or null */
+    const double *dt_each;   /* DEVICE, [n_steps][T], at the launch's first slot */
+};
+static_assert(sizeof(TraceEachArgs) <= 4096, "kernel arguments are limited to 4 KB");
+typedef void (*trace_each_kernel_t)(const TraceEachArgs);
+
 /* kfpos_run_planar_events_dev (kfpos_k_planarev.hip): the planar filter's argument block around KArgs, unchanged as
  * well. k.n_steps events; k.dt_steps[e] is the timeLag of event e; its kind (0 = ranging, KFPOS_SENSOR_* otherwise)
  * is nibble e of `kinds`; the j-th ranging event of the launch reads k.ranges / k.err + j * stride, the i-th event of
@@ -162,6 +175,8 @@ typedef void (*planar_events_each_kernel_t)(const PevEachArgs);
 step_kernel_t toa6_sym_kernel(int st, int as, int heur, bool two_waves);   /* kfpos_k_toa6s.hip */
 step_kernel_t toa6_full_kernel(int st, int as, int heur);                  /* kfpos_k_toa6f.hip */
 step_kernel_t toa6_coop_kernel(int st);                                    /* kfpos_k_coop.hip */
+trace_each_kernel_t toa6_each_sym_kernel(int st, int as, int heur);        /* kfpos_k_toa6eachs.hip */
+trace_each_kernel_t toa6_each_full_kernel(int st, int as, int heur);       /* kfpos_k_toa6eachf.hip */
 step_kernel_t imu9_kernel(int st, int as, bool ranging);                   /* kfpos_k_imu9.hip */
 events_kernel_t imu9_events_kernel(int st, int as);                        /* kfpos_k_imu9ev.hip: as = 8 or 0 */
 events_each_kernel_t imu9_events_each_kernel(int st, int as);              /* kfpos_k_imu9each.hip: as = 8 or 0 */
