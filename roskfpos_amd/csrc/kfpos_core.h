@@ -55,6 +55,13 @@
 #else
 #define KFPOS_WAVE_ALL(pred) (pred)
 #endif
+/* true when the predicate holds on at least one active lane: the ballot of the comparison itself, no detour through an
+ * integer per lane (a wave-uniform value as well) */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define KFPOS_WAVE_ANY(pred) (__builtin_amdgcn_ballot_w64(pred) != 0)
+#else
+#define KFPOS_WAVE_ANY(pred) (pred)
+#endif
 
 namespace kfpos {
 
@@ -109,6 +116,16 @@ KFPOS_FN int kf_opaque_zero() {
     asm volatile("" : "+v"(z));
 #endif
     return z;
+}
+/* keeps a value that was loaded in front of a loop in a register across it: behind this the compiler knows neither the
+ * value nor where it came from, so it can neither sink the load to the value's (conditional) use inside the loop nor
+ * repeat it there */
+KFPOS_FN void kf_pin(double &v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(v));
+#else
+    (void)v;
+#endif
 }
 /* index of the lowest set bit of a non-zero mask */
 KFPOS_FN int kf_ctz64(uint64_t m) {
@@ -183,6 +200,24 @@ KFPOS_FN bool rel_change_below(double cost, double c, double tol) {
     const bool clear = cost > 0.0 && fabs(lhs - rhs) > 1e-13 * rhs; /* false for NaN and for cost <= 0 or inf */
     if (KFPOS_WAVE_ALL(clear)) return lhs < rhs;
     return lhs / cost < tol;
+}
+
+/* The same test -- the same two sides, the same `clear`, the same decision for every input -- shaped for the trip loop of
+ * the 9-state gain iteration, where every instruction is paid twenty times per epoch: the vote is the ballot of the
+ * comparison itself (no bool rebuilt from an integer per lane), the product form is evaluated unconditionally and the
+ * cold side overwrites it with the exact quotient -- one way in, one way out, nothing to re-test on the hot side.
+ * Only that loop uses it. The other callers of rel_change_below / _above (6-state and planar iterations, the (I + M B)
+ * form, every Gauss-Newton loop) keep their text on purpose: they are inlined into kernels that sit at their register
+ * or occupancy limits, where any change of this text -- even sharing the three first lines through a helper -- moves
+ * the schedule of every one of them; in ml_estimate the new shape made k_events_imu9<p48,float,8> spill inside its
+ * loop (profiles/HISTORY.md), and none of those kernels has been measured with it. Whoever changes one of the three
+ * changes all three. */
+KFPOS_FN bool rel_change_below_voted(double cost, double c, double tol) {
+    const double lhs = fabs(cost - c), rhs = tol * cost;
+    const bool clear = cost > 0.0 && fabs(lhs - rhs) > 1e-13 * rhs; /* false for NaN and for cost <= 0 or inf */
+    bool below = lhs < rhs;
+    if (KFPOS_WAVE_ANY(!clear)) below = lhs / cost < tol;
+    return below;
 }
 
 /* The Gauss-Newton loop's test  fabs(cost - newCost) / cost > tol  (MLLocation.cpp:168; :79 for the 2-D solver), the same

@@ -21,7 +21,7 @@ struct Imu {
     double acc[3]; /* linearAcceleration */
     double *ci;    /* 12 entries, entry k at ci[k * ci_stride]: 0-5 the inverse Cholesky factor of the covariance, lower
                       {00,10,20,11,21,22} (Sigma^-1 = Ci' Ci; used once per step, in the covariance update), 6-11
-                      Sigma^-1 itself, symmetric {00,01,02,11,12,22} (six reads per pass of the gain iteration).
+                      Sigma^-1 itself, symmetric {00,01,02,11,12,22} (read once per step, in front of the gain iteration).
                       Constant over a launch, so both wait outside the register file (LDS on the GPU) */
     int ci_stride;
     KFPOS_HD double Wi(int k) const { return ci[(6 + k) * ci_stride]; }
@@ -505,11 +505,14 @@ KFPOS_FN void iekf9_sweep(const double p[3], const SC &sc, const Params &pr, Swe
     }
 }
 
-/* One pass at the iterate xhat_e + it.ve, whose anchor sums are sw: cost, convergence test (false: converged, nothing
- * changed) and -- if the iteration goes on -- the solve that yields the next iterate. */
-/* What a pass reads from the park: B^-1 and Sigma^-1. Fetched at the top of every trip, BEFORE the sweep, so that the
- * LDS round trip hides behind the sweep's arithmetic instead of stalling the solve (one wavefront per SIMD: nothing else
- * would cover it); 54 registers that are free while the sweep runs. */
+/* One pass at the iterate xhat_e + it.ve, whose anchor sums are sw: cost, convergence test and -- if the iteration goes
+ * on -- the solve that yields the next iterate. */
+/* What a pass reads from the park: B^-1 and the entries of Sigma^-1 its form uses (DIAG: the diagonal). Both are fixed
+ * while a step iterates. The one-tag-per-lane loop (iekf9_info) fetches them ONCE, in front of its trips, and holds them
+ * in registers across the loop: 21 + 3 (6) values; Sigma^-1 is pinned there (kf_pin) -- its only use sits under the
+ * per-lane `imu.has`, and left alone the compiler sinks the read to that use, i.e. into every trip, with an lgkmcnt wait
+ * five instructions behind it and nothing else on the SIMD to cover the round trip (one wavefront per SIMD).
+ * tools/trip_loop_shape.py keeps DS instructions and their waits out of the trips at build time. */
 /* The pairs' loop reads its parked values in every trip; this asks the scheduler to spread those reads over the sweep,
  * one per ten arithmetic instructions, instead of queueing them in a row at the top of the trip (a wavefront issues in
  * order, and the CU's four wavefronts share one LDS queue). For the one-tag-per-lane loop neither placement beat letting
@@ -526,15 +529,28 @@ KFPOS_FN void iekf9_spread_reads() {
 struct Iekf9Parked {
     double binv[21], wi[6];
 };
-template <bool EVERY_TRIP>
+/* EVERY_TRIP: the pairs' loop, which has no registers to hold them; otherwise once per step, pinned (PIN) */
+template <bool EVERY_TRIP, bool DIAG, bool PIN = !EVERY_TRIP>
 KFPOS_FN void iekf9_fetch(const double *binv, int binv_stride, const Imu &imu, Iekf9Parked &pk) {
-    const int z = EVERY_TRIP ? kf_opaque_zero() : 0; /* (read in every trip / wherever the compiler sees fit) */
+    const int z = EVERY_TRIP ? kf_opaque_zero() : 0;
     KFPOS_UNROLL
     for (int k = 0; k < 21; ++k) pk.binv[k] = binv[k * binv_stride + z];
     KFPOS_UNROLL
     for (int k = 0; k < 6; ++k) pk.wi[k] = imu.ci[(6 + k) * imu.ci_stride + z]; /* (never looked at without a sample) */
+    if constexpr (PIN) {
+        KFPOS_UNROLL
+        for (int k = 0; k < 6; ++k) {
+            if (!DIAG || k == 0 || k == 3 || k == 5) kf_pin(pk.wi[k]);
+        }
+    }
 }
-template <bool DIAG>
+/* Returns whether the lane goes on: false = it has converged, nothing of it changed. Everything a lane keeps is written
+ * inside the one region under that condition; a trip of the caller's loop then has four branches: the vote of the
+ * convergence test, the skip of that region for the lanes that have converged, the loop's exit and its back-edge.
+ * ALLIMU: every lane that is here has an accelerometer sample (wave-uniform, the caller's vote): the sample's terms are
+ * formed without looking at imu.has -- no mask, no branch, no zeros to start from. Same operations on the same numbers
+ * in the same order as the per-lane form. */
+template <bool DIAG, bool ALLIMU>
 KFPOS_FN bool iekf9_pass(const double xhat[9], const Iekf9Parked &pk, const Imu &imu, double tol,
                          const Sweep9 &sw, Iekf9Iter &it, Iekf9Out &o) {
     const double *ve = it.ve;
@@ -545,7 +561,7 @@ KFPOS_FN bool iekf9_pass(const double xhat[9], const Iekf9Parked &pk, const Imu 
     double u[6] = {sw.u[0] + (m0 * ve[0] + m1 * ve[1] + m2 * ve[2]), sw.u[1] + (m1 * ve[0] + m3 * ve[1] + m4 * ve[2]),
                    sw.u[2] + (m2 * ve[0] + m4 * ve[1] + m5 * ve[2]), 0.0, 0.0, 0.0};
     double ma[6] = {0, 0, 0, 0, 0, 0}; /* M_a = D Sigma^-1 D, symmetric {00,01,02,11,12,22} */
-    if (imu.has) {
+    if (ALLIMU || imu.has) {
         const double ya[3] = {imu.acc[0] - acc[0], imu.acc[1] - acc[1], imu.acc[2] - acc[2]};
         const double va[3] = {ya[0] + acc[0] * ve[3], ya[1] + acc[1] * ve[4], ya[2] + acc[2] * ve[5]};
         if constexpr (DIAG) {
@@ -571,42 +587,44 @@ KFPOS_FN bool iekf9_pass(const double xhat[9], const Iekf9Parked &pk, const Imu 
             ma[3] = acc[1] * acc[1] * wm[1][1]; ma[4] = acc[1] * acc[2] * wm[1][2]; ma[5] = acc[2] * acc[2] * wm[2][2];
         }
     }
-    if (rel_change_below(it.cost, c, tol)) return false; /* KalmanFilterTOAIMU.cpp:316 */
+    const bool go = !rel_change_below_voted(it.cost, c, tol); /* KalmanFilterTOAIMU.cpp:316 */
+    if (go) {
 #ifdef KFPOS_EMU_ITER_TRACE /* tools/exp/iter_cycle.py: a host build that records every iterate */
-    kfpos_emu_iter_trace(o.gain_iters, ve, c);
+        kfpos_emu_iter_trace(o.gain_iters, ve, c);
 #endif
-    it.cost = c;
-    KFPOS_UNROLL
-    for (int k = 0; k < 6; ++k) o.mrlast[k] = m[k];
-    o.dlast[0] = acc[0]; o.dlast[1] = acc[1]; o.dlast[2] = acc[2];
+        it.cost = c;
+        KFPOS_UNROLL
+        for (int k = 0; k < 6; ++k) o.mrlast[k] = m[k];
+        o.dlast[0] = acc[0]; o.dlast[1] = acc[1]; o.dlast[2] = acc[2];
 
-    /* (B^-1 + M) v = u */
-    Cov<6, true> K;
-    KFPOS_UNROLL
-    for (int k = 0; k < 21; ++k) K.a[k] = pk.binv[k];
-    K(0, 0) += m[0]; K(0, 1) += m[1]; K(0, 2) += m[2]; K(1, 1) += m[3]; K(1, 2) += m[4]; K(2, 2) += m[5];
-    K(3, 3) += ma[0]; K(4, 4) += ma[3]; K(5, 5) += ma[5];
-    if constexpr (!DIAG) { K(3, 4) += ma[1]; K(3, 5) += ma[2]; K(4, 5) += ma[4]; }
-    double v[6];
-    sym6_solve(K, u, v);
-    /* w = u - M v ; delta' pinv(P) delta = w . P_ee w = w . v */
-    double *wl = it.wl;
-    wl[0] = u[0] - (m[0] * v[0] + m[1] * v[1] + m[2] * v[2]);
-    wl[1] = u[1] - (m[1] * v[0] + m[3] * v[1] + m[4] * v[2]);
-    wl[2] = u[2] - (m[2] * v[0] + m[4] * v[1] + m[5] * v[2]);
-    /* (written out in full for the diagonal case too: a shorter form would round differently, and a tag must not
-     * see which wave-mates it has) */
-    wl[3] = u[3] - (ma[0] * v[3] + ma[1] * v[4] + ma[2] * v[5]);
-    wl[4] = u[4] - (ma[1] * v[3] + ma[3] * v[4] + ma[4] * v[5]);
-    wl[5] = u[5] - (ma[2] * v[3] + ma[4] * v[4] + ma[5] * v[5]);
-    double qd = 0.0;
-    KFPOS_UNROLL
-    for (int i = 0; i < 6; ++i) qd += wl[i] * v[i];
-    it.qd = qd;
-    KFPOS_UNROLL
-    for (int i = 0; i < 6; ++i) it.ve[i] = v[i];
-    o.gain_iters++;
-    return true;
+        /* (B^-1 + M) v = u */
+        Cov<6, true> K;
+        KFPOS_UNROLL
+        for (int k = 0; k < 21; ++k) K.a[k] = pk.binv[k];
+        K(0, 0) += m[0]; K(0, 1) += m[1]; K(0, 2) += m[2]; K(1, 1) += m[3]; K(1, 2) += m[4]; K(2, 2) += m[5];
+        K(3, 3) += ma[0]; K(4, 4) += ma[3]; K(5, 5) += ma[5];
+        if constexpr (!DIAG) { K(3, 4) += ma[1]; K(3, 5) += ma[2]; K(4, 5) += ma[4]; }
+        double v[6];
+        sym6_solve(K, u, v);
+        /* w = u - M v ; delta' pinv(P) delta = w . P_ee w = w . v */
+        double *wl = it.wl;
+        wl[0] = u[0] - (m[0] * v[0] + m[1] * v[1] + m[2] * v[2]);
+        wl[1] = u[1] - (m[1] * v[0] + m[3] * v[1] + m[4] * v[2]);
+        wl[2] = u[2] - (m[2] * v[0] + m[4] * v[1] + m[5] * v[2]);
+        /* (written out in full for the diagonal case too: a shorter form would round differently, and a tag must not
+         * see which wave-mates it has) */
+        wl[3] = u[3] - (ma[0] * v[3] + ma[1] * v[4] + ma[2] * v[5]);
+        wl[4] = u[4] - (ma[1] * v[3] + ma[3] * v[4] + ma[4] * v[5]);
+        wl[5] = u[5] - (ma[2] * v[3] + ma[4] * v[4] + ma[5] * v[5]);
+        double qd = 0.0;
+        KFPOS_UNROLL
+        for (int i = 0; i < 6; ++i) qd += wl[i] * v[i];
+        it.qd = qd;
+        KFPOS_UNROLL
+        for (int i = 0; i < 6; ++i) it.ve[i] = v[i];
+        o.gain_iters++;
+    }
+    return go;
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -695,7 +713,7 @@ KFPOS_FN void iekf9_pairs(uint64_t m, const double xhat[9], const double *binv, 
         KFPOS_UNROLL
         for (int k = 3; k < 12; ++k) bb[k] = b4[k + z];
         Iekf9Parked pk;
-        iekf9_fetch<true>(cbinv, binv_stride, ci, pk);
+        iekf9_fetch<true, DIAG>(cbinv, binv_stride, ci, pk);
         const double p[3] = {xh[0] + ct.ve[0], xh[1] + ct.ve[1], xh[2] + ct.ve[2]};
         Sweep9 sw, other;
         iekf9_sweep4(p, r4, w4, bb, sw);
@@ -707,7 +725,7 @@ KFPOS_FN void iekf9_pairs(uint64_t m, const double xhat[9], const double *binv, 
         /* the lower lane holds (0-3) and adds (4-7); the upper one adds them the other way round: same sums */
         sweep9_add(sw, other);
         iekf9_spread_reads();
-        const bool more = iekf9_pass<DIAG>(xh, pk, ci, tol, sw, ct, co);
+        const bool more = iekf9_pass<DIAG, false>(xh, pk, ci, tol, sw, ct, co);
         act = more && co.gain_iters < max_steps;
     }
     /* back to the owners: the k-th survivor reads lane 2k */
@@ -731,8 +749,11 @@ KFPOS_FN void iekf9_pairs(uint64_t m, const double xhat[9], const double *binv, 
 #endif
 
 /* ACC0: the predicted acceleration xhat[6..8] is the literal 0 on every lane (KalmanFilterTOAIMU.cpp restarts it at
- * every step), so a pair does not fetch it */
-template <bool DIAG, bool RANGING, bool ACC0 = false, class SC>
+ * every step), so a pair does not fetch it.
+ * ALLIMU: see iekf9_pass. HOLD: B^-1 and Sigma^-1 are read once in front of the trips and held (iekf9_fetch); false
+ * leaves the read inside the trip, to be placed as the compiler sees fit -- for a kernel that has no registers to hold
+ * them and would spill inside its epoch loop instead. */
+template <bool DIAG, bool ALLIMU, bool RANGING, bool ACC0 = false, bool HOLD = true, class SC>
 KFPOS_FN void iekf9_info(const double xhat[9], const double *binv, int binv_stride, SC &sc, const Params &pr,
                          const Imu &imu, int max_steps, double tol, Iekf9Out &o) {
     Iekf9Iter it;
@@ -755,14 +776,15 @@ KFPOS_FN void iekf9_info(const double xhat[9], const double *binv, int binv_stri
      * per-lane loop more than the pairs give back (measured: 1.2 us per epoch for a ballot and a branch per trip). */
     if (pairs) stop = 8 < max_steps ? 8 : max_steps;
 #endif
+    Iekf9Parked pk;
+    if constexpr (HOLD) iekf9_fetch<false, DIAG, true>(binv, binv_stride, imu, pk);
     for (;;) {
         while (more && o.gain_iters < stop) {
-            Iekf9Parked pk;
-            iekf9_fetch<false>(binv, binv_stride, imu, pk);
+            if constexpr (!HOLD) iekf9_fetch<false, DIAG, false>(binv, binv_stride, imu, pk);
             const double p[3] = {xhat[0] + it.ve[0], xhat[1] + it.ve[1], xhat[2] + it.ve[2]};
             Sweep9 sw;
             iekf9_sweep<RANGING>(p, sc, pr, sw);
-            more = iekf9_pass<DIAG>(xhat, pk, imu, tol, sw, it, o);
+            more = iekf9_pass<DIAG, ALLIMU>(xhat, pk, imu, tol, sw, it, o);
         }
 #if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (PAIRS) {
@@ -822,7 +844,7 @@ KFPOS_FN void cov_update9(Cov<9, true> &P, const double mr[6], const double d[3]
  * RANGING = false is the IMU-only call of newIMUMeasurement (:91): its own instantiation (and kernel), so that a
  * ranging epoch carries no code of it. */
 /* where the 45 covariance entries wait while the information-form iteration runs (it does not touch P), followed by
- * the 21 entries of B^-1, which each iteration reads back, and the 6 of the accelerometer whitener (Imu::ci): element k
+ * the 21 entries of B^-1, which the iteration reads back once per step, and the 6 of the accelerometer whitener (Imu::ci): element k
  * at a[k * stride] -- LDS on the GPU ([78][lane] with Imu::ci behind them: 39 KB per wavefront), a stack array in the host emulation. The iteration then has the directly addressable half of
  * the register file to itself instead of shuffling P and B^-1 through the accumulation registers. */
 struct CovPark9 {
@@ -835,12 +857,16 @@ struct CovPark9 {
  *   step_imu9_state  everything up to the updated position and velocity. false: the step is over, `status` is its
  *                    status word (ML initialisation, too few ranges, update skipped); true: step_imu9_cov is still due.
  *   step_imu9_cov    the covariance update; returns the status word.
- * diag: the accelerometer covariance is diagonal -- Sigma^-1 of this tag has exact zeros off its diagonal -- so the gain
- * iteration takes the DIAG form of its pass: same operations on the same numbers in the same order, minus the terms that
- * are exact zeros, i.e. the same bits (the kernel decides once per launch and per wavefront; false is always right). */
-template <bool RANGING, class SC>
+ * fast: wave-uniform, the caller's vote over the lanes that run this step: the accelerometer covariance of every one of
+ * them is diagonal -- Sigma^-1 has exact zeros off its diagonal -- AND every one of them has a sample (imu.has). The gain
+ * iteration then takes the DIAG form of its pass, with the sample's terms unconditional: same operations on the same
+ * numbers in the same order, minus the terms that are exact zeros, i.e. the same bits. false is always right: the full
+ * form, which looks at imu.has lane by lane. (Two forms, not four: a third and a fourth copy of the trip loop for
+ * diagonal-but-partly-latched and full-and-all-sampled wavefronts would add 2 x ~570 instructions to an epoch loop of
+ * ~10 400 for wavefronts that are rare -- latched lanes exist only in MODE_TOA calls -- and lose 0.9 us an epoch.) */
+template <bool RANGING, bool HOLD = true, class SC>
 KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, const Imu &imu, const CovPark9 &park,
-                              bool diag, Iekf9Out &o, uint32_t &status) {
+                              bool fast, Iekf9Out &o, uint32_t &status) {
     constexpr bool has_ranging = RANGING;
     const int n_valid = has_ranging ? count_used(sc, pr, 0) : 0;
     if (!pr.use_init_pos && (isnan(tg.pos[0]) || isnan(tg.pos[1]))) { /* :121-122, z is not tested */
@@ -896,14 +922,14 @@ KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, con
     /* per lane, not per wavefront: a tag's arithmetic must not depend on its wave-mates (a wavefront whose lanes
      * disagree runs both forms one after the other, each under its lanes' mask) */
     if (invertible) {
-        if (diag) iekf9_info<true, RANGING, true>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
-        else iekf9_info<false, RANGING, true>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
+        if (fast) iekf9_info<true, true, RANGING, true, HOLD>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
+        else iekf9_info<false, false, RANGING, true, HOLD>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
         KFPOS_UNROLL
         for (int k = 0; k < 45; ++k) tg.P.a[k] = park.a[k * park.stride];
     } else {
         KFPOS_UNROLL
         for (int k = 0; k < 45; ++k) tg.P.a[k] = park.a[k * park.stride];
-        if (diag) iekf9<true, RANGING>(xhat, tg.P, sc, pr, imu, 20, 1e-4, o);
+        if (fast) iekf9<true, RANGING>(xhat, tg.P, sc, pr, imu, 20, 1e-4, o);
         else iekf9<false, RANGING>(xhat, tg.P, sc, pr, imu, 20, 1e-4, o);
     }
     KFPOS_UNROLL

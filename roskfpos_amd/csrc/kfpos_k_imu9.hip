@@ -98,6 +98,10 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
         const bool mine = !imu.has || (imu.Wi(1) == 0.0 && imu.Wi(2) == 0.0 && imu.Wi(4) == 0.0);
         diag = __builtin_amdgcn_ballot_w64(mine) == __builtin_amdgcn_ballot_w64(true);
     }
+    /* ... and every lane has a sample (imu.has does not change during this launch; always so with a fresh sample per
+     * epoch): the pass then forms the sample's terms without a per-lane branch. A wavefront with a lane that has
+     * nothing latched (MODE_TOA) takes the full per-lane form, diagonal or not: two forms of the trip loop, not four */
+    const bool fast = imu9_fast(diag, imu.has);
 
     /* dt: in a multi-epoch launch it is wave-uniform and sits in the kernel arguments -- read one epoch ahead with a
      * scalar load, so that the epoch loop holds no vector load (and no vmcnt wait) for it; the per-tag dt of a
@@ -150,7 +154,7 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
 #pragma unroll
                 for (int k = 0; k < AS; ++k) sc.r[k] = sc.e[k] = sc.w[k] = 0.0;
             }
-            finish(step_imu9_state<RANGING>(tg, sc, pr, dt, imu, park, diag, o, s));
+            finish(step_imu9_state<RANGING>(tg, sc, pr, dt, imu, park, fast, o, s));
             if constexpr (!AHEAD) { /* 8-byte measurements: the next epoch is fetched when this one is over */
                 if (e + 1 < a.n_steps) {
                     if (fresh_imu) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
@@ -160,7 +164,7 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
         } else {
             Scratch sc{nullptr, nullptr, nullptr, WAVE};
             if (has_ranging) sc = stage_epoch_lds<MREAL>(a, lds, lane, t, opaque_uniform(e));
-            finish(step_imu9_state<RANGING>(tg, sc, pr, dt, imu, park, diag, o, s));
+            finish(step_imu9_state<RANGING>(tg, sc, pr, dt, imu, park, fast, o, s));
             if constexpr (!AHEAD) { /* the ranges are staged per epoch above; the next accelerometer sample is not */
                 if (e + 1 < a.n_steps && fresh_imu) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
             }

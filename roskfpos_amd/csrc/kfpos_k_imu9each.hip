@@ -152,11 +152,11 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9_each(const kfpos_k::EvEach
                 RegScratch<AS> sc;
                 unpack_epoch<MREAL, AS>(raw, sc);
                 if constexpr (AHEAD) fetch_small();
-                if (run) update = step_imu9_state<true>(tg, sc, pr, dt, imu, park, diag, o, s);
+                if (run) update = step_imu9_state<true>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
             } else {
                 Scratch sc = stage_epoch_lds<MREAL>(a, lds, lane, t, opaque_uniform(cur)); /* the whole wavefront */
                 if constexpr (AHEAD) fetch_small();
-                if (run) update = step_imu9_state<true>(tg, sc, pr, dt, imu, park, diag, o, s);
+                if (run) update = step_imu9_state<true>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
             }
         } else { /* newIMUMeasurement: latch the sample, predict + IMU-only update */
             if (run) {
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9_each(const kfpos_k::EvEach
             }
             if constexpr (AHEAD) fetch_small();
             Scratch sc{nullptr, nullptr, nullptr, WAVE};
-            if (run) update = step_imu9_state<false>(tg, sc, pr, dt, imu, park, diag, o, s);
+            if (run) update = step_imu9_state<false>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
         }
         ran |= run;
         /* the pose store between the state part and the covariance part (k_step_imu9); a lane that sits the slot out

@@ -419,6 +419,11 @@ __device__ inline void latch_imu_cov(const KArgs &a, size_t T, uint32_t t32, con
     strow<MREAL>(a.imu_cov, 5, T, t32, cv[8]);
 }
 
+/* step_imu9_state's `fast`: the wavefront's accelerometer covariances are diagonal (diag: decided per launch) and every
+ * lane that is about to run the step has a sample -- one ballot over the lanes that are here */
+__device__ inline bool imu9_fast(bool diag, bool has) {
+    return diag && __builtin_amdgcn_ballot_w64(!has) == 0;
+}
 /* A wave-uniform epoch index the optimiser cannot see through: addresses derived from it are formed anew in every
  * epoch (a few scalar instructions) instead of living as two dozen running row pointers across the whole epoch loop,
  * where they exhaust the scalar registers and end up as spilled 64-bit per-lane addresses. */
