@@ -328,6 +328,34 @@ int kfpos_step_toa_imu_rows(kfpos_handle *h, const int32_t *rows, int32_t n, con
 int kfpos_step_sensor_rows(kfpos_handle *h, const int32_t *rows, int32_t n, int32_t kind, const double *data /* n x C */,
                            const double *dt, int32_t dt_len, uint32_t *status);
 
+/* ---- pose for a row list: getPose for the tags that REPORTED ----
+ * What a node publishes is getPose -- position, its 3x3 covariance and the velocity, extrapolated by "now minus my last
+ * estimate" (Posgenerator.cpp:541-548). kfpos_get_pose / kfpos_get_pose_each / kfpos_get_predicted compute it for the
+ * whole bank; these take a list, like the lifecycle calls and the row-list steps: `rows` = n row indices, and what
+ * crosses the bus -- the list, dt_ahead, the listed entries' results -- and what the GPU touches follows n, not n_tags.
+ *   semantics   entry i of every output is, bit for bit, row rows[i] of what kfpos_get_pose_each / kfpos_get_predicted
+ *               return when that row's dt_ahead is dt_ahead[dt_len == 1 ? 0 : i] (the same per-tag code runs). Outputs
+ *               are row-major per listed ENTRY: pos n x 3, cov3x3 n x 9, vel n x 3, x n x dim, P n x dim x dim, status
+ *               n. dt_ahead belongs to the entry, not to the row: a row listed twice with two values comes back twice,
+ *               extrapolated by each. A tag that has not started reports KFPOS_ST_NOT_STARTED and NaN. Any output of
+ *               kfpos_get_pose_rows may be NULL; x and P of kfpos_get_predicted_rows may not. The filter state is not
+ *               touched.
+ *   validation  on the host before anything is enqueued: h == NULL, n < 0, rows == NULL with n > 0, a row outside
+ *               [0, n_tags), dt_ahead == NULL, dt_len other than 1 or n, x or P == NULL -> KFPOS_ERR_ARG;
+ *               kfpos_last_error() names the first offending entry. Rows may repeat, as in kfpos_get_tags. Nothing has
+ *               been written after an error. This check IS the bounds check: the kernel never sees an unchecked index.
+ *   n == 0      KFPOS_OK, nothing happens.
+ *   ordering    like kfpos_get_tags: first everything the streaming slots have in flight completes, and the call returns
+ *               when its own work is complete. Runs on the handle's device, leaves the caller's current device as it was.
+ * KFPOS_VERSION is unchanged by them: detect them by symbol. */
+int kfpos_get_pose_rows(kfpos_handle *h, const int32_t *rows, int32_t n,
+                        const double *dt_ahead, int32_t dt_len /* 1 or n */,
+                        double *pos /* n x 3 */, double *cov3x3 /* n x 9 */, double *vel /* n x 3 */,
+                        uint32_t *status /* n */);
+int kfpos_get_predicted_rows(kfpos_handle *h, const int32_t *rows, int32_t n,
+                             const double *dt_ahead, int32_t dt_len,
+                             double *x /* n x dim */, double *P /* n x dim x dim */, uint32_t *status);
+
 /* ---- streaming host API: epochs pipelined through kfpos_slot_count() slots of pinned host memory ----
  * For a node that feeds epoch after epoch from the CPU (PosGenerator's table flushes, Posgenerator.cpp:155-198, batched
  * over many tags): the synchronous calls above copy pageable arrays, turn their layout on the device and wait; here
@@ -388,6 +416,19 @@ typedef struct kfpos_rows_slot {
 } kfpos_rows_slot;
 int kfpos_slot_acquire_rows(kfpos_handle *h, int32_t slot, kfpos_rows_slot *out);
 int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t n, double dt_shared);
+
+/* A row-list round that returns what is published. KFPOS_SLOT_POSE_COV is honoured by kfpos_slot_submit_rows only
+ * (kfpos_slot_submit ignores the bit): after the round's scatter, getPose at timeLag 0 runs on the compute stream for the
+ * round's list, and the covariance and the velocity travel back behind status and pos. kfpos_slot_pose_rows hands out
+ * the slot's pinned arrays -- cov3x3 [n][9] and vel [n][3], row-major per listed tag --, valid after kfpos_slot_wait
+ * until the slot's next submission: entry i is, bit for bit, what kfpos_get_pose_rows(rows, n, &zero, 1, ...) returns
+ * right after that round. The arrays (capacity x 12 doubles, pinned and on the device) are allocated by the slot's first
+ * round that carries the flag; rounds without it enqueue what they always did.
+ *   KFPOS_SLOT_POSE_COV | KFPOS_SLOT_NO_POSE -> KFPOS_ERR_ARG
+ *   kfpos_slot_pose_rows on a slot whose last row-list round did not carry the flag (or enqueued nothing: n == 0, the
+ *   IMU round of a filter without one) -> KFPOS_ERR_STATE. Either pointer may be NULL. */
+#define KFPOS_SLOT_POSE_COV   0x1000
+int kfpos_slot_pose_rows(kfpos_handle *h, int32_t slot, double **cov3x3 /* [n][9] */, double **vel /* [n][3] */);
 
 /* ---- asynchronous device-buffer API (inputs already resident in HBM) ----
  * All pointers are device pointers; `stream` is a hipStream_t (NULL = the default stream). Calls

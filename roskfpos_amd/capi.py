@@ -40,6 +40,7 @@ EXPORTS = [
     "kfpos_slot_count", "kfpos_slot_acquire", "kfpos_slot_submit", "kfpos_slot_wait",
     "kfpos_step_toa_rows", "kfpos_step_imu_rows", "kfpos_step_toa_imu_rows", "kfpos_step_sensor_rows",
     "kfpos_slot_acquire_rows", "kfpos_slot_submit_rows",
+    "kfpos_get_pose_rows", "kfpos_get_predicted_rows", "kfpos_slot_pose_rows",
     "kfpos_shard_range", "kfpos_comm_unique_id", "kfpos_comm_create", "kfpos_comm_create_all", "kfpos_comm_destroy",
     "kfpos_comm_world", "kfpos_comm_rank", "kfpos_comm_set_total", "kfpos_allgather_poses",
     "kfpos_allgather_poses_multi", "kfpos_comm_wait", "kfpos_comm_sync", "kfpos_assemble_poses_dev",
@@ -51,6 +52,7 @@ SLOT_TOA, SLOT_IMU, SLOT_TOA_IMU = 0, 1, 2
 EVENT_IMU, EVENT_TOA = 0, 1  # kfpos_run_events_dev: newIMUMeasurement / newTOAMeasurement
 PLANAR_EVENT_TOA = 0  # kfpos_run_planar_events_dev: newTOAMeasurement; the other kinds are SENSOR_PX4FLOW .. SENSOR_COMPASS
 SLOT_DT_PER_TAG, SLOT_REUSE_ERR, SLOT_REUSE_COV, SLOT_NO_POSE = 0x100, 0x200, 0x400, 0x800
+SLOT_POSE_COV = 0x1000  # slot_submit_rows only: the round also returns cov3x3 and vel of its tags (slot_pose_rows)
 
 
 class KfposError(RuntimeError):
@@ -168,6 +170,9 @@ def load():
     sig("kfpos_step_sensor_rows", [vp, vp, i32, i32, vp, vp, i32, vp])
     sig("kfpos_slot_acquire_rows", [vp, i32, C.POINTER(_RowsSlot)])
     sig("kfpos_slot_submit_rows", [vp, i32, i32, i32, f64])
+    sig("kfpos_get_pose_rows", [vp, vp, i32, vp, i32, vp, vp, vp, vp])
+    sig("kfpos_get_predicted_rows", [vp, vp, i32, vp, i32, vp, vp, vp])
+    sig("kfpos_slot_pose_rows", [vp, i32, C.POINTER(vp), C.POINTER(vp)])
     sig("kfpos_timing_begin", [vp, vp])
     sig("kfpos_timing_end", [vp, vp, C.POINTER(C.c_float)])
     i64 = C.c_int64
@@ -477,6 +482,30 @@ class KfposBank:
                                                   d.ctypes.data, d.size, st.ctypes.data))
         return st
 
+    # ---- pose for a row list: getPose for the listed rows only (cost follows len(rows), not T) ----
+    def get_pose_rows(self, rows, dt_ahead):
+        """get_pose_each for the entries of `rows` (rows may repeat): dt_ahead is one value or one per ENTRY. Returns
+        (pos (m, 3), cov (m, 3, 3), vel (m, 3), status (m,)), bit for bit the whole-bank call's rows."""
+        r = self._rows(rows)
+        m = r.size
+        d = self._dt_rows(dt_ahead, m)
+        pos, cov, vel = np.zeros((m, 3)), np.zeros((m, 9)), np.zeros((m, 3))
+        st = np.zeros(m, dtype=np.uint32)
+        self._chk(self.lib.kfpos_get_pose_rows(self._h, r.ctypes.data, m, d.ctypes.data, d.size, pos.ctypes.data,
+                                               cov.ctypes.data, vel.ctypes.data, st.ctypes.data))
+        return pos, cov.reshape(m, 3, 3), vel, st
+
+    def get_predicted_rows(self, rows, dt_ahead):
+        """get_predicted for the entries of `rows`: (x (m, n), P (m, n, n), status (m,))."""
+        r = self._rows(rows)
+        m = r.size
+        d = self._dt_rows(dt_ahead, m)
+        x, P = np.zeros((m, self.n)), np.zeros((m, self.n, self.n))
+        st = np.zeros(m, dtype=np.uint32)
+        self._chk(self.lib.kfpos_get_predicted_rows(self._h, r.ctypes.data, m, d.ctypes.data, d.size, x.ctypes.data,
+                                                    P.ctypes.data, st.ctypes.data))
+        return x, P, st
+
     # ---- streaming host API: epochs assembled in place in pinned, component-major slots ----
     def slot_acquire(self, slot):
         """Wait for the slot's previous submission; returns numpy views over the slot's pinned memory:
@@ -522,6 +551,19 @@ class KfposBank:
 
     def slot_submit_rows(self, slot, flags, n, dt_shared=0.0):
         self._chk(self.lib.kfpos_slot_submit_rows(self._h, slot, int(flags), int(n), float(dt_shared)))
+
+    def slot_pose_rows(self, slot, n):
+        """After slot_wait of a round submitted with SLOT_POSE_COV: views (cov (n, 3, 3), vel (n, 3)) over the slot's
+        pinned arrays -- what get_pose_rows(rows, 0.0) returned right after that round."""
+        cov, vel = C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.kfpos_slot_pose_rows(self._h, slot, C.byref(cov), C.byref(vel)))
+
+        def view(ptr, shape):
+            cnt = int(np.prod(shape))
+            buf = (C.c_char * (cnt * 8)).from_address(ptr)
+            return np.frombuffer(buf, dtype=np.float64, count=cnt).reshape(shape)
+
+        return view(cov.value, (int(n), 3, 3)), view(vel.value, (int(n), 3))
 
     # ---- device-buffer API (pointers: ints or torch tensors; layouts in include/kfpos.h) ----
     def step_toa_dev(self, range_mm, err_est, dt, status=None, stream=None, dt_dev=None):

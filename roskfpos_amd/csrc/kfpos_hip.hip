@@ -500,6 +500,8 @@ int kfpos_destroy(kfpos_handle *h) {
     for (auto &sl : h->slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.rows) (void)hipHostFree(sl.rows);
+        if (sl.pose_host) (void)hipHostFree(sl.pose_host);
+        if (sl.pose_dev) (void)hipFree(sl.pose_dev);
         if (sl.dev) (void)hipFree(sl.dev);
         if (sl.copied) (void)hipEventDestroy(sl.copied);
         if (sl.copied2) (void)hipEventDestroy(sl.copied2);
@@ -1150,25 +1152,31 @@ int kfpos_run_planar_events_each_dev(kfpos_handle *h, int32_t n_events, const ui
     return KFPOS_OK;
 }
 
+/* the bank as the pose kernels read it; outputs and extrapolation times: null / 0 until the caller sets them */
+static void pose_bank_args(const kfpos_handle *h, PoseArgs &a) {
+    std::memset(&a, 0, sizeof(a));
+    a.T = h->cfg.n_tags;
+    a.model = h->cfg.model;
+    a.full = h->full;
+    a.accel_noise = h->cfg.accel_noise;
+    a.jolt = h->cfg.jolt;
+    a.pos_in = h->d_pos;
+    a.vel_in = h->d_vel;
+    a.P = h->d_P;
+    a.flags = h->d_flags;
+}
+
 static int launch_pose(kfpos_handle *h, double dt_ahead, const double *dt_each, double *pos, double *cov3x3,
                        double *vel, uint32_t *status, void *stream, double *full_x = nullptr,
                        double *full_P = nullptr) {
     if (!h) return KFPOS_ERR_ARG;
     DevScope dev_(h->cfg.device);
     PoseArgs a;
+    pose_bank_args(h, a);
     a.dt_each = dt_each;
     a.full_x = full_x;
     a.full_P = full_P;
-    a.T = h->cfg.n_tags;
-    a.model = h->cfg.model;
-    a.full = h->full;
-    a.accel_noise = h->cfg.accel_noise;
-    a.jolt = h->cfg.jolt;
     a.dt_ahead = dt_ahead;
-    a.pos_in = h->d_pos;
-    a.vel_in = h->d_vel;
-    a.P = h->d_P;
-    a.flags = h->d_flags;
     a.pos = pos;
     a.cov = cov3x3;
     a.vel = vel;
@@ -2066,6 +2074,89 @@ int kfpos_reset_tags(kfpos_handle *h, const int32_t *rows, int32_t n, const doub
     return KFPOS_OK;
 }
 
+/* ---- pose for a row list: kfpos_get_pose_rows / kfpos_get_predicted_rows (kernel: k_get_pose_rows, kfpos_k_misc.hip) ---- */
+/* both calls: out[k] = the caller's k-th array of w[k] doubles per entry (null = not wanted). Staged like the lifecycle
+ * calls: per chunk of m entries the list and dt go up, one launch writes the entries' results row-major, and they come
+ * down as they are -- nothing here is sized by n_tags. */
+static int pose_rows_host(kfpos_handle *h, const char *who, const int32_t *rows, int32_t n, const double *dt_ahead,
+                          int32_t dt_len, bool predicted, double *const out[3], const int w[3], uint32_t *status) {
+    if (!h) return KFPOS_ERR_ARG;
+    int rc = tags_check(h, who, rows, n, false);
+    if (rc) return rc;
+    if (!dt_ahead || (dt_len != 1 && dt_len != n)) {
+        g_err = std::string(who) + (!dt_ahead ? ": dt_ahead == NULL" : ": dt_len = " + std::to_string(dt_len) + " is neither 1 nor n = " + std::to_string(n));
+        return KFPOS_ERR_ARG;
+    }
+    if (predicted && (!out[0] || !out[1])) {
+        g_err = std::string(who) + (!out[0] ? ": x == NULL" : ": P == NULL");
+        return KFPOS_ERR_ARG;
+    }
+    if (n == 0) return KFPOS_OK;
+    DevScope dev_(h->cfg.device);
+    if ((rc = drain_slots(h))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    const bool each = dt_len != 1; /* (dt_len == n == 1: the shared value is that entry's) */
+    size_t wsum = 0;
+    for (int k = 0; k < 3; ++k) wsum += out[k] ? (size_t)w[k] : 0;
+    if (wsum == 0 && !status) return KFPOS_OK;
+    /* per entry: its results and its dt (doubles), its status word, its row index */
+    const size_t rec = (wsum + (each ? 1 : 0)) * sizeof(double) + sizeof(uint32_t) + sizeof(int32_t);
+    TagStage st;
+    if ((rc = tag_stage(h, rec, (size_t)n, st))) return rc;
+    kfpos_k::PoseRowsArgs a = {};
+    pose_bank_args(h, a.p);
+    a.p.dt_ahead = dt_ahead[0];
+    const size_t chunk = st.chunk;
+    for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
+        const size_t m = (size_t)n - c0 < chunk ? (size_t)n - c0 : chunk;
+        size_t off[3], o = 0;
+        for (int k = 0; k < 3; ++k) {
+            off[k] = o;
+            o += out[k] ? m * w[k] * sizeof(double) : 0;
+        }
+        const size_t off_dt = o, off_st = off_dt + (each ? m * sizeof(double) : 0), off_rows = off_st + m * sizeof(uint32_t);
+        HIPCHK(tag_up(st, off_rows, rows + c0, m * sizeof(int32_t)));
+        if (each) HIPCHK(tag_up(st, off_dt, dt_ahead + c0, m * sizeof(double)));
+        double *d[3];
+        for (int k = 0; k < 3; ++k) d[k] = out[k] ? (double *)(st.dev + off[k]) : nullptr;
+        if (predicted) {
+            a.p.full_x = d[0];
+            a.p.full_P = d[1];
+        } else {
+            a.p.pos = d[0];
+            a.p.cov = d[1];
+            a.p.vel = d[2];
+        }
+        a.p.dt_each = each ? (const double *)(st.dev + off_dt) : nullptr;
+        a.p.status = status ? (uint32_t *)(st.dev + off_st) : nullptr;
+        a.rows = (const int32_t *)(st.dev + off_rows);
+        a.n = (int)m;
+        kfpos_k::launch_get_pose_rows(h->cfg.model, h->full != 0, h->cfg.storage, nullptr, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(nullptr)); /* the staging is free again; a mapped block's results are visible */
+        for (int k = 0; k < 3; ++k)
+            if (out[k]) HIPCHK(tag_down(st, out[k] + c0 * w[k], off[k], m * w[k] * sizeof(double)));
+        if (status) HIPCHK(tag_down(st, status + c0, off_st, m * sizeof(uint32_t)));
+    }
+    return KFPOS_OK;
+}
+
+int kfpos_get_pose_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const double *dt_ahead, int32_t dt_len,
+                        double *pos, double *cov3x3, double *vel, uint32_t *status) {
+    g_err.clear();
+    double *const out[3] = {pos, cov3x3, vel};
+    const int w[3] = {3, 9, 3};
+    return pose_rows_host(h, "kfpos_get_pose_rows", rows, n, dt_ahead, dt_len, false, out, w, status);
+}
+
+int kfpos_get_predicted_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const double *dt_ahead, int32_t dt_len,
+                             double *x, double *P, uint32_t *status) {
+    g_err.clear();
+    double *const out[3] = {x, P, nullptr};
+    const int w[3] = {h ? h->n : 0, h ? h->n * h->n : 0, 0};
+    return pose_rows_host(h, "kfpos_get_predicted_rows", rows, n, dt_ahead, dt_len, true, out, w, status);
+}
+
 /* ---- row-list steps: kfpos_step_*_rows, kfpos_slot_acquire_rows / kfpos_slot_submit_rows ----
  * The step kernels are not touched and see no row index: the listed tags' stored bits are gathered into a compact work
  * bank (kfpos_k_tags.hip: k_rows_work), the kernel this handle runs anyway steps that bank with KArgs::T = n, and the
@@ -2310,12 +2401,18 @@ int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t
         g_err = "kfpos_slot_submit_rows: KFPOS_SLOT_REUSE_* belongs to whole-bank rounds (a row-list round brings the listed tags' own values)";
         return KFPOS_ERR_ARG;
     }
+    const bool pose_cov = (flags & KFPOS_SLOT_POSE_COV) != 0;
+    if (pose_cov && (flags & KFPOS_SLOT_NO_POSE)) {
+        g_err = "kfpos_slot_submit_rows: KFPOS_SLOT_POSE_COV with KFPOS_SLOT_NO_POSE (a round that returns what is published returns pos)";
+        return KFPOS_ERR_ARG;
+    }
     if (n > h->cfg.n_tags) {
         g_err = "kfpos_slot_submit_rows: n exceeds the slot's capacity (n_tags)";
         return KFPOS_ERR_ARG;
     }
     int rc = rows_check(h, "kfpos_slot_submit_rows", sl.rows, n);
     if (rc) return rc;
+    sl.pose_round = false; /* until this round has enqueued its own (a round that enqueues nothing publishes nothing) */
     if (n == 0) return KFPOS_OK;
     if (h->cfg.model == KFPOS_MODEL_PLANAR && kind != KFPOS_SLOT_TOA) return KFPOS_ERR_MODEL; /* its sensors: kfpos_step_sensor_rows */
     const bool imu9 = h->cfg.model == KFPOS_MODEL_TOA_IMU;
@@ -2328,6 +2425,11 @@ int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t
     if (has_rng && !h->have_anchors) {
         g_err = "kfpos_set_anchors has not been called";
         return KFPOS_ERR_STATE;
+    }
+    const size_t cap = h->cfg.n_tags;
+    if (pose_cov && !sl.pose_host) { /* first use of the flag in this slot */
+        HIPCHK(hipHostMalloc((void **)&sl.pose_host, cap * 12 * sizeof(double), hipHostMallocDefault));
+        HIPCHK(hipMalloc((void **)&sl.pose_dev, cap * 12 * sizeof(double)));
     }
     if ((rc = rows_reserve(h, (size_t)n))) return rc;
     const RowsLayout L = rows_layout(h, h->work_cap, (size_t)n);
@@ -2374,13 +2476,41 @@ int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t
     const bool want_pose = !(flags & KFPOS_SLOT_NO_POSE);
     a.traj = want_pose ? (double *)(in + L.i_pos) : nullptr;
     if ((rc = rows_step(h, h->s_comp, L, (const int32_t *)(in + L.i_rows), n, a))) return rc;
+    if (pose_cov) { /* what is published for the round's tags: getPose at timeLag 0 of the bank the scatter just wrote */
+        kfpos_k::PoseRowsArgs g = {};
+        pose_bank_args(h, g.p);
+        g.p.cov = sl.pose_dev;
+        g.p.vel = sl.pose_dev + cap * 9;
+        g.rows = (const int32_t *)(in + L.i_rows);
+        g.n = n;
+        kfpos_k::launch_get_pose_rows(h->cfg.model, h->full != 0, h->cfg.storage, h->s_comp, g);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipEventRecord(sl.computed, h->s_comp));
     /* 3. status [n] and pos [3][n] back */
     HIPCHK(hipStreamWaitEvent(h->s_back, sl.computed, 0));
     HIPCHK(hipMemcpyAsync(sl.host + h->so_status, in + L.i_status, N * sizeof(uint32_t), hipMemcpyDeviceToHost, h->s_back));
     if (want_pose) HIPCHK(hipMemcpyAsync(sl.host + h->so_pos, in + L.i_pos, N * 3 * sizeof(double), hipMemcpyDeviceToHost, h->s_back));
+    if (pose_cov) { /* cov3x3 [n][9], vel [n][3] behind them */
+        HIPCHK(hipMemcpyAsync(sl.pose_host, sl.pose_dev, N * 9 * sizeof(double), hipMemcpyDeviceToHost, h->s_back));
+        HIPCHK(hipMemcpyAsync(sl.pose_host + cap * 9, sl.pose_dev + cap * 9, N * 3 * sizeof(double), hipMemcpyDeviceToHost, h->s_back));
+    }
     HIPCHK(hipEventRecord(sl.done, h->s_back));
     sl.busy = true;
+    sl.pose_round = pose_cov;
+    return KFPOS_OK;
+}
+
+int kfpos_slot_pose_rows(kfpos_handle *h, int32_t slot, double **cov3x3, double **vel) {
+    g_err.clear();
+    if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
+    const auto &sl = h->slot[slot];
+    if (!sl.pose_round) {
+        g_err = "kfpos_slot_pose_rows: the slot's last row-list round did not carry KFPOS_SLOT_POSE_COV";
+        return KFPOS_ERR_STATE;
+    }
+    if (cov3x3) *cov3x3 = sl.pose_host;
+    if (vel) *vel = sl.pose_host + (size_t)h->cfg.n_tags * 9;
     return KFPOS_OK;
 }
 

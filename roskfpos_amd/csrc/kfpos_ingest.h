@@ -299,6 +299,19 @@ public:
     /* the tags' estimator clocks, for getPose extrapolation: seconds since each tag's last estimate */
     double sinceLastEstimate(int row, double now) const { return tags_[row].started ? now - tags_[row].last : 0.0; }
     bool started(int row) const { return tags_[row].started; }
+    /* The publish tick of a sparse node: getPose for the n listed rows (the tags that reported since the last tick), each
+     * extrapolated by "now minus my last estimate" (Posgenerator.cpp:541-548). pos n x 3, cov n x 9, vel n x 3, status
+     * n, any of them NULL. What crosses the bus follows n (kfpos_get_pose_rows); like every synchronous call it first
+     * waits for what poll() left in flight. Returns the KFPOS_* code; rows outside the bank are refused there. */
+    int getPoseRows(const int *rows, int n, double now, double *pos, double *cov, double *vel, uint32_t *status) {
+        std::vector<int32_t> list((size_t)(n > 0 ? n : 0));
+        std::vector<double> ahead(list.size() ? list.size() : 1, 0.0);
+        for (size_t i = 0; i < list.size(); ++i) {
+            list[i] = rows[i];
+            ahead[i] = (rows[i] >= 0 && rows[i] < T_) ? sinceLastEstimate(rows[i], now) : 0.0;
+        }
+        return kfpos_get_pose_rows(h_, list.data(), n, ahead.data(), n > 1 ? n : 1, pos, cov, vel, status);
+    }
     int rows() const { return T_; }
     uint64_t messages() const { return messages_; }    /* ranging messages taken in so far */
     uint64_t overflowCalls() const { return overflowed_; } /* calls that had to wait for a later round */

@@ -84,6 +84,10 @@ struct kfpos_handle {
         hipEvent_t err_reader = nullptr, cov_reader = nullptr;
         bool busy = false;
         int32_t *rows = nullptr; /* pinned [n_tags]: the row list of a row-list round (kfpos_slot_acquire_rows) */
+        /* KFPOS_SLOT_POSE_COV, allocated by the first round that carries it: cov3x3 [n][9] at 0 and vel [n][3] at
+         * 9 * n_tags doubles, pinned and on the device; pose_round: the slot's last row-list round filled them */
+        double *pose_host = nullptr, *pose_dev = nullptr;
+        bool pose_round = false;
     } slot[KFPOS_N_SLOTS];
     size_t so_ranges = 0, so_err = 0, so_accel = 0, so_cov = 0, so_dt = 0, so_status = 0, so_pos = 0, so_bytes = 0;
     hipStream_t s_copy = nullptr, s_copy2 = nullptr, s_comp = nullptr, s_back = nullptr;

@@ -1,5 +1,5 @@
 /*
- * kfpos_k_misc.hip -- k_step_ml (MLLocation as the estimator), k_step_planar (KalmanFilter, 8 states), k_get_pose, layout turns
+ * kfpos_k_misc.hip -- k_step_ml (MLLocation as the estimator), k_step_planar (KalmanFilter, 8 states), k_get_pose, k_get_pose_rows, layout turns
  */
 #include "kfpos_kernels.h"
 
@@ -212,26 +212,41 @@ __global__ __launch_bounds__(WAVE) void k_step_planar(const KArgs a) {
 }
 
 /* ------------------------------------------------------------------ pose kernel (getPose) */
-template <int MODEL, bool SYMM, typename REAL>
-__global__ __launch_bounds__(WAVE) void k_get_pose(const PoseArgs a) {
-    const size_t t = (size_t)blockIdx.x * WAVE + threadIdx.x;
-    if (t >= (size_t)a.T) return;
+/* Where component k (of C) of output entry o goes: the whole-bank call writes component-major arrays of extent E =
+ * n_tags ([C][E], coalesced; the host turns them), the row-list call writes the caller's row-major layout directly
+ * ([E][C], E = the length of the list: a list is short, and its results leave over the bus as they are). */
+template <bool ROWMAJOR>
+__device__ inline double &pose_out(double *base, int k, int C, size_t E, uint32_t o) {
+    if constexpr (ROWMAJOR) {
+        (void)E;
+        return base[(size_t)o * C + k];
+    } else {
+        (void)C;
+        return (base + (size_t)k * E)[o];
+    }
+}
+
+/* getPose of ONE tag, the text both pose kernels run: the tag is row t32 of the bank (extent T = a.T), its results are
+ * entry o of outputs of extent E, `ahead` its extrapolation time. k_get_pose: o = t32, E = T, component-major;
+ * k_get_pose_rows: t32 = rows[o], E = n, row-major. */
+template <int MODEL, bool SYMM, typename REAL, bool ROWMAJOR>
+__device__ inline void pose_of_tag(const PoseArgs &a, const uint32_t t32, const uint32_t o, const size_t E, const double ahead) {
     const size_t T = a.T;
-    const uint32_t t32 = (uint32_t)t;
+    constexpr int N = MODEL == 6 ? 6 : (MODEL == 3 ? 3 : (MODEL == 8 ? 8 : 9));
+    auto fx = [&](int i) -> double & { return pose_out<ROWMAJOR>(a.full_x, i, N, E, o); };
+    auto fP = [&](int i) -> double & { return pose_out<ROWMAJOR>(a.full_P, i, N * N, E, o); };
     double pos[3], vel[3] = {0, 0, 0}, cov[9];
     uint32_t s = 0;
-    const double ahead = a.dt_each ? a.dt_each[t] : a.dt_ahead;
-    if (!(a.flags[t] & FL_STARTED)) {
+    if (!(a.flags[t32] & FL_STARTED)) {
         s = ST_NOT_STARTED;
 #pragma unroll
         for (int k = 0; k < 3; ++k) pos[k] = vel[k] = NAN;
 #pragma unroll
         for (int k = 0; k < 9; ++k) cov[k] = NAN;
         if (a.full_P) {
-            constexpr int N = MODEL == 6 ? 6 : (MODEL == 3 ? 3 : (MODEL == 8 ? 8 : 9));
 #pragma unroll
-            for (int i = 0; i < N; ++i) (a.full_x + i * T)[t32] = NAN;
-            for (int i = 0; i < N * N; ++i) (a.full_P + (size_t)i * T)[t32] = NAN;
+            for (int i = 0; i < N; ++i) fx(i) = NAN;
+            for (int i = 0; i < N * N; ++i) fP(i) = NAN;
         }
     } else if (MODEL == 3) { /* MLLocation::getPose: the estimate as it is */
 #pragma unroll
@@ -242,9 +257,9 @@ __global__ __launch_bounds__(WAVE) void k_get_pose(const PoseArgs a) {
         cov[6] = c[2]; cov[7] = c[4]; cov[8] = c[5];
         if (a.full_P) {
 #pragma unroll
-            for (int i = 0; i < 3; ++i) (a.full_x + i * T)[t32] = pos[i];
+            for (int i = 0; i < 3; ++i) fx(i) = pos[i];
 #pragma unroll
-            for (int i = 0; i < 9; ++i) (a.full_P + (size_t)i * T)[t32] = cov[i];
+            for (int i = 0; i < 9; ++i) fP(i) = cov[i];
         }
     } else if (MODEL == 8) { /* KalmanFilter::getPose, KalmanFilter.cpp:709-745 */
         Tag8 tg;
@@ -269,9 +284,9 @@ __global__ __launch_bounds__(WAVE) void k_get_pose(const PoseArgs a) {
         if (a.full_P) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                (a.full_x + i * T)[t32] = x8[i];
+                fx(i) = x8[i];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) (a.full_P + (size_t)(i * 8 + j) * T)[t32] = Pp(i, j);
+                for (int j = 0; j < 8; ++j) fP(i * 8 + j) = Pp(i, j);
             }
         }
     } else if (MODEL == 6) {
@@ -285,9 +300,9 @@ __global__ __launch_bounds__(WAVE) void k_get_pose(const PoseArgs a) {
             predict6(tg.P, ahead, a.accel_noise);
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
-                (a.full_x + i * T)[t32] = i < 3 ? tg.pos[i] : 0.0;
+                fx(i) = i < 3 ? tg.pos[i] : 0.0;
 #pragma unroll
-                for (int j = 0; j < 6; ++j) (a.full_P + (size_t)(i * 6 + j) * T)[t32] = tg.P(i, j);
+                for (int j = 0; j < 6; ++j) fP(i * 6 + j) = tg.P(i, j);
             }
         }
     } else {
@@ -304,22 +319,40 @@ __global__ __launch_bounds__(WAVE) void k_get_pose(const PoseArgs a) {
             predict9(tg.P, ahead, a.jolt);
 #pragma unroll
             for (int i = 0; i < 9; ++i) {
-                (a.full_x + i * T)[t32] = i < 3 ? pos[i] : (i < 6 ? vel[i - 3] : 0.0);
+                fx(i) = i < 3 ? pos[i] : (i < 6 ? vel[i - 3] : 0.0);
 #pragma unroll
-                for (int j = 0; j < 9; ++j) (a.full_P + (size_t)(i * 9 + j) * T)[t32] = tg.P(i, j);
+                for (int j = 0; j < 9; ++j) fP(i * 9 + j) = tg.P(i, j);
             }
         }
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        if (a.pos) (a.pos + k * T)[t32] = pos[k];
-        if (a.vel) (a.vel + k * T)[t32] = vel[k];
+        if (a.pos) pose_out<ROWMAJOR>(a.pos, k, 3, E, o) = pos[k];
+        if (a.vel) pose_out<ROWMAJOR>(a.vel, k, 3, E, o) = vel[k];
     }
     if (a.cov) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) (a.cov + k * T)[t32] = cov[k];
+        for (int k = 0; k < 9; ++k) pose_out<ROWMAJOR>(a.cov, k, 9, E, o) = cov[k];
     }
-    if (a.status) a.status[t] = s;
+    if (a.status) a.status[o] = s;
+}
+
+template <int MODEL, bool SYMM, typename REAL>
+__global__ __launch_bounds__(WAVE) void k_get_pose(const PoseArgs a) {
+    const size_t t = (size_t)blockIdx.x * WAVE + threadIdx.x;
+    if (t >= (size_t)a.T) return;
+    pose_of_tag<MODEL, SYMM, REAL, false>(a, (uint32_t)t, (uint32_t)t, (size_t)a.T, a.dt_each ? a.dt_each[t] : a.dt_ahead);
+}
+
+/* getPose for a LIST of tags (kfpos_get_pose_rows / kfpos_get_predicted_rows, KFPOS_SLOT_POSE_COV): lane i gathers row
+ * rows[i] of the component-major bank -- one scattered access per stored component, as the per-tag kernels of
+ * kfpos_k_tags.hip --, runs the text above and writes entry i of row-major outputs of length n. dt_each is per ENTRY:
+ * a row listed twice with two values is extrapolated twice. The rows were validated on the host before the launch. */
+template <int MODEL, bool SYMM, typename REAL>
+__global__ __launch_bounds__(WAVE) void k_get_pose_rows(const PoseRowsArgs a) {
+    const size_t i = (size_t)blockIdx.x * WAVE + threadIdx.x;
+    if (i >= (size_t)a.n) return;
+    pose_of_tag<MODEL, SYMM, REAL, true>(a.p, (uint32_t)a.rows[i], (uint32_t)i, (size_t)a.n, a.p.dt_each ? a.p.dt_each[i] : a.p.dt_ahead);
 }
 
 /* ------------------------------------------------------------------ layout kernels of the host-buffer API */
@@ -381,6 +414,22 @@ void kfpos_k::launch_get_pose(int model, bool full, int st, int blocks, hipStrea
     else if (model == KFPOS_MODEL_TOA_IMU) pose_by_storage<9, true>(st, blocks, s, a);
     else if (full) pose_by_storage<6, false>(st, blocks, s, a);
     else pose_by_storage<6, true>(st, blocks, s, a);
+}
+
+template <int MODEL, bool SYMM>
+static void pose_rows_by_storage(int st, int blocks, hipStream_t s, const PoseRowsArgs &a) {
+    if (st == KFPOS_STORE_F32) hipLaunchKernelGGL((k_get_pose_rows<MODEL, SYMM, float>), dim3(blocks), dim3(WAVE), 0, s, a);
+    else if (st == KFPOS_STORE_P48) hipLaunchKernelGGL((k_get_pose_rows<MODEL, SYMM, p48>), dim3(blocks), dim3(WAVE), 0, s, a);
+    else hipLaunchKernelGGL((k_get_pose_rows<MODEL, SYMM, double>), dim3(blocks), dim3(WAVE), 0, s, a);
+}
+void kfpos_k::launch_get_pose_rows(int model, bool full, int st, hipStream_t s, const PoseRowsArgs &a) {
+    if (a.n <= 0) return;
+    const int blocks = (a.n + WAVE - 1) / WAVE;
+    if (model == KFPOS_MODEL_PLANAR) pose_rows_by_storage<8, true>(st, blocks, s, a);
+    else if (model == KFPOS_MODEL_ML) pose_rows_by_storage<3, true>(st, blocks, s, a);
+    else if (model == KFPOS_MODEL_TOA_IMU) pose_rows_by_storage<9, true>(st, blocks, s, a);
+    else if (full) pose_rows_by_storage<6, false>(st, blocks, s, a);
+    else pose_rows_by_storage<6, true>(st, blocks, s, a);
 }
 
 void kfpos_k::launch_rows_to_cols(size_t esz, hipStream_t s, const void *src, void *dst, int T, int C) {

@@ -25,7 +25,7 @@
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
  * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
- * filter, standalone ML estimator, getPose, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
+ * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
 #define KFPOS_KERNELS_H
@@ -94,6 +94,16 @@ struct PoseArgs {
     double *pos, *cov, *vel; /* [3][T], [9][T], [3][T]; any may be null */
     double *full_x, *full_P; /* [n][T], [n*n][T] predicted state / covariance (row-major index first), or null */
     uint32_t *status;
+};
+
+/* k_get_pose_rows (kfpos_k_misc.hip): getPose for a list of tags, a block of its own around an unchanged PoseArgs. p.T,
+ * p.pos_in / vel_in / P / flags describe the bank as ever; entry i of the list is row rows[i] of it, p.dt_each (or null:
+ * p.dt_ahead) is indexed by ENTRY, and the outputs are row-major per entry: pos [n][3], cov [n][9], vel [n][3],
+ * full_x [n][dim], full_P [n][dim * dim], status [n]; any may be null (full_x and full_P together). */
+struct PoseRowsArgs {
+    PoseArgs p;
+    const int32_t *rows; /* DEVICE (or mapped), [n], validated by the host */
+    int n;
 };
 
 typedef void (*step_kernel_t)(const KArgs);
@@ -185,6 +195,7 @@ planar_events_each_kernel_t planar_events_each_kernel(int st, int as);     /* kf
 step_kernel_t ml_kernel(int st, int as);                                   /* kfpos_k_misc.hip */
 step_kernel_t planar_kernel(int st, bool sensors, int as);                 /* kfpos_k_misc.hip */
 void launch_get_pose(int model, bool full, int st, int blocks, hipStream_t s, const PoseArgs &a); /* kfpos_k_misc.hip */
+void launch_get_pose_rows(int model, bool full, int st, hipStream_t s, const PoseRowsArgs &a);    /* kfpos_k_misc.hip */
 void launch_rows_to_cols(size_t esz, hipStream_t s, const void *src, void *dst, int T, int C);    /* kfpos_k_misc.hip */
 void launch_cols_to_rows(hipStream_t s, const double *src, double *dst, int T, int C);            /* kfpos_k_misc.hip */
 
@@ -234,6 +245,7 @@ namespace {
 using namespace kfpos;
 using kfpos_k::KArgs;
 using kfpos_k::PoseArgs;
+using kfpos_k::PoseRowsArgs;
 using kfpos_k::step_kernel_t;
 using kfpos_k::COOP_LANES;
 using kfpos_k::COOP_TAGS_PER_WAVE;

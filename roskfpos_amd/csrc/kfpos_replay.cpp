@@ -51,6 +51,7 @@ struct NodeParams { /* names and defaults: node_pos.cpp:48-109, kfpos_toa.launch
     std::string targetDeviceId = "", nodeName = "/kfpos"; /* topic names, node_pos.cpp:119-135 */
     int dumpMessages = 0; /* not a reference parameter: print every published message field on P ticks */
     std::string tagIds = ""; /* not a reference parameter: comma-separated hex tag ids -> batched multi-tag mode */
+    std::string publishTags = ""; /* not a reference parameter: batched mode prints only these tags (a subset of tagIds) on P ticks */
 };
 
 static bool set_param(NodeParams &p, const std::string &k, const std::string &v) {
@@ -78,6 +79,7 @@ static bool set_param(NodeParams &p, const std::string &k, const std::string &v)
     else if (k == "configIMU") p.configIMU = v;
     else if (k == "configMAG") p.configMAG = v;
     else if (k == "tagIds") p.tagIds = v;
+    else if (k == "publishTags") p.publishTags = v;
     else if (k == "targetDeviceId") p.targetDeviceId = v;
     else if (k == "nodeName") p.nodeName = v;
     else if (k == "dumpMessages") p.dumpMessages = atoi(v.c_str());
@@ -172,7 +174,9 @@ struct EpochAssembler {
  * line per tag: "P <t> <tagId> <ok> <x> <y> <z> <cov00> <cov11> <cov22>". Sensor messages carry the tag they
  * belong to (a multi-tag node has one sensor topic per vehicle): lower-case kinds with the hex tag id after the
  * time stamp -- "j <t> <tag> ...", "x <t> <tag> ...", "c <t> <tag> <heading>", "g <t> <tag> <mx> <my> <mz>" --
- * and the same subscription switches as the single-tag node. */
+ * and the same subscription switches as the single-tag node. With publishTags:=<hex,hex,...> (a subset of tagIds) a
+ * 'P' line prints those tags only, in the order given, and asks the GPU for those rows only (getPoseRows): each line is
+ * character for character the one the run without the parameter prints for that tag at that tick. */
 static int run_batched(const NodeParams &p, const std::string &trace) {
     std::vector<int> tagIds;
     {
@@ -181,6 +185,19 @@ static int run_batched(const NodeParams &p, const std::string &trace) {
         while (std::getline(ss, tok, ',')) tagIds.push_back((int)strtol(tok.c_str(), nullptr, 16));
     }
     const int T = (int)tagIds.size();
+    std::vector<int> publishRows; /* rows of the tags named by publishTags */
+    {
+        std::stringstream ss(p.publishTags);
+        std::string tok;
+        while (std::getline(ss, tok, ',')) {
+            const int id = (int)strtol(tok.c_str(), nullptr, 16);
+            int row = -1;
+            for (int r = 0; r < T && row < 0; ++r)
+                if (tagIds[r] == id) row = r;
+            if (row < 0) throw std::invalid_argument("publishTags: tag " + tok + " is not in tagIds");
+            publishRows.push_back(row);
+        }
+    }
     std::vector<int> anchorIds;
     std::vector<double> anchorXyz;
     kfpos_handle *h = nullptr;
@@ -267,6 +284,18 @@ static int run_batched(const NodeParams &p, const std::string &trace) {
             double t; ss >> t;
             ensure();
             node->poll(t);
+            if (!p.publishTags.empty()) {
+                const int n = (int)publishRows.size();
+                std::vector<double> pos(3 * n), cov(9 * n), vel(3 * n);
+                std::vector<uint32_t> st(n);
+                if (node->getPoseRows(publishRows.data(), n, t, pos.data(), cov.data(), vel.data(), st.data()) != KFPOS_OK)
+                    throw std::runtime_error(std::string("kfpos_get_pose_rows: ") + kfpos_last_error());
+                for (int i = 0; i < n; ++i)
+                    printf("P %.9f %x %d %.17g %.17g %.17g %.17g %.17g %.17g\n", t, tagIds[publishRows[i]],
+                           (st[i] & KFPOS_ST_NOT_STARTED) ? 0 : 1, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2],
+                           cov[9 * i], cov[9 * i + 4], cov[9 * i + 8]);
+                continue;
+            }
             std::vector<double> ahead(T), pos(3 * T), cov(9 * T), vel(3 * T);
             std::vector<uint32_t> st(T);
             for (int r = 0; r < T; ++r) ahead[r] = node->sinceLastEstimate(r, t);
