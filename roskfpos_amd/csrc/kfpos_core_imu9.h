@@ -752,8 +752,11 @@ KFPOS_FN void iekf9_pairs(uint64_t m, const double xhat[9], const double *binv, 
  * every step), so a pair does not fetch it.
  * ALLIMU: see iekf9_pass. HOLD: B^-1 and Sigma^-1 are read once in front of the trips and held (iekf9_fetch); false
  * leaves the read inside the trip, to be placed as the compiler sees fit -- for a kernel that has no registers to hold
- * them and would spill inside its epoch loop instead. */
-template <bool DIAG, bool ALLIMU, bool RANGING, bool ACC0 = false, bool HOLD = true, class SC>
+ * them and would spill inside its epoch loop instead.
+ * SETTLE: the held values have arrived before the first trip. A caller in whose step nothing else stands between the
+ * fetch and the loop sets it: the compiler otherwise waits for the last of them where a trip first uses them, and that
+ * wait is then executed in every trip. */
+template <bool DIAG, bool ALLIMU, bool RANGING, bool ACC0 = false, bool HOLD = true, bool SETTLE = false, class SC>
 KFPOS_FN void iekf9_info(const double xhat[9], const double *binv, int binv_stride, SC &sc, const Params &pr,
                          const Imu &imu, int max_steps, double tol, Iekf9Out &o) {
     Iekf9Iter it;
@@ -778,6 +781,9 @@ KFPOS_FN void iekf9_info(const double xhat[9], const double *binv, int binv_stri
 #endif
     Iekf9Parked pk;
     if constexpr (HOLD) iekf9_fetch<false, DIAG, true>(binv, binv_stride, imu, pk);
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (HOLD && SETTLE) __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0), the other counters untouched */
+#endif
     for (;;) {
         while (more && o.gain_iters < stop) {
             if constexpr (!HOLD) iekf9_fetch<false, DIAG, false>(binv, binv_stride, imu, pk);
@@ -851,6 +857,90 @@ struct CovPark9 {
     double *a;
     int stride;
 };
+
+/* ---- the statements of step_imu9_state (below) once more, as the pieces that the phase functions behind it
+ * (step_imu9_head / step_imu9_state_parked) put together in another order, for a caller whose covariance stays in the
+ * park from one epoch to the next. No operation changes its operands: same bits either way. (step_imu9_state itself
+ * keeps its own text: written with these pieces it computes the same, but the event kernels, which inline it three
+ * times, then allocate registers differently and spill inside their loops.) */
+/* the tag runs the prediction (false: it still waits for its ML initialisation, :121-122 -- z is not tested) */
+KFPOS_FN bool imu9_started(const Tag9 &tg, const Params &pr) {
+    return pr.use_init_pos || !(isnan(tg.pos[0]) || isnan(tg.pos[1]));
+}
+/* ML initialisation of a tag that has not started (:121-137). true: pos is the ML position and c its covariance, of
+ * which the filter keeps {00,01,11}; false: nothing changed. status is the step's status word either way. */
+template <bool RANGING, class SC>
+KFPOS_FN bool imu9_ml_init(double pos[3], SC &sc, const Params &pr, int n_valid, double c[6], uint32_t &status) {
+    status = 0;
+    if (!RANGING) return false;
+    status = ST_FEW_RANGES;
+    if (n_valid < 4) return false;
+    double p[3] = {1.0, 1.0, 4.0}, sse;
+    set_weights_ml(sc, pr, 0ull);
+    const int it = ml_estimate(p, sc, pr, 0, n_valid, sse);
+    status = ST_UPDATE_SKIPPED;
+    if (ml_covariance_throws(sc, pr, 0, n_valid, sse)) return false; /* reference: abort */
+    if (!ml_covariance(p, sc, pr, sse, c)) return false;
+    pos[0] = p[0]; pos[1] = p[1]; pos[2] = p[2];
+    status = pack_status(ST_ML_INIT, 0, it, -1);
+    return true;
+}
+KFPOS_FN void imu9_predict_state(const Tag9 &tg, double dt, double xhat[9]) {
+    const double c = dt * dt / 2;
+    KFPOS_UNROLL
+    for (int k = 0; k < 3; ++k) { /* acceleration restarts at 0 */
+        xhat[k] = tg.pos[k] + dt * tg.vel[k] + c * 0.0;
+        xhat[3 + k] = tg.vel[k] + dt * 0.0;
+        xhat[6 + k] = 0.0;
+    }
+}
+KFPOS_FN void imu9_park(const Cov<9, true> &P, const CovPark9 &park) {
+    KFPOS_UNROLL
+    for (int k = 0; k < 45; ++k) park.a[k * park.stride] = P.a[k];
+}
+KFPOS_FN void imu9_unpark(Cov<9, true> &P, const CovPark9 &park) {
+    KFPOS_UNROLL
+    for (int k = 0; k < 45; ++k) P.a[k] = park.a[k * park.stride];
+}
+/* Prediction of the covariance, then B = P_ee and its inverse, both into the park. Returns whether B is safely
+ * invertible: the information-form iteration (the usual case); otherwise -- right after a fixed start, B is singular --
+ * the (I + M B) form. */
+KFPOS_FN bool imu9_predict_park(Cov<9, true> &P, double dt, double jolt, const CovPark9 &park) {
+    predict9(P, dt, jolt);
+    Cov<6, true> B;
+    KFPOS_UNROLL
+    for (int i = 0; i < 6; ++i) {
+        KFPOS_UNROLL
+        for (int j = i; j < 6; ++j) B(i, j) = P(e9(i), e9(j));
+    }
+    imu9_park(P, park);
+    return sym6_inverse(B, park.a + 45 * park.stride, park.stride, INFO_FORM_MIN_PIVOT);
+}
+/* the gain iteration on the parked covariance, which it leaves in P, and the updated position and velocity */
+template <bool RANGING, bool HOLD, bool SETTLE, class SC>
+KFPOS_FN void imu9_iterate(Tag9 &tg, const double xhat[9], SC &sc, const Params &pr, const Imu &imu,
+                           const CovPark9 &park, bool fast, bool invertible, Iekf9Out &o) {
+    double *binv = park.a + 45 * park.stride;
+    /* per lane, not per wavefront: a tag's arithmetic must not depend on its wave-mates (a wavefront whose lanes
+     * disagree runs both forms one after the other, each under its lanes' mask) */
+    if (invertible) {
+        if (fast) iekf9_info<true, true, RANGING, true, HOLD, SETTLE>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
+        else iekf9_info<false, false, RANGING, true, HOLD, SETTLE>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
+        imu9_unpark(tg.P, park);
+    } else {
+        imu9_unpark(tg.P, park);
+        if (fast) iekf9<true, RANGING>(xhat, tg.P, sc, pr, imu, 20, 1e-4, o);
+        else iekf9<false, RANGING>(xhat, tg.P, sc, pr, imu, 20, 1e-4, o);
+    }
+    KFPOS_UNROLL
+    for (int i = 0; i < 6; ++i) { /* x = xhat + P E' w: position and velocity are what the filter keeps (:189-194) */
+        double v = 0.0;
+        KFPOS_UNROLL
+        for (int k = 0; k < 6; ++k) v += tg.P(i, e9(k)) * o.w[k];
+        if (i < 3) tg.pos[i] = xhat[i] + v;
+        else tg.vel[i - 3] = xhat[i] + v;
+    }
+}
 
 /* The step in two parts, so that a caller can act between them (the kernel stores the pose there: it is final, and the
  * covariance update -- 630 instructions without a memory access -- covers the store):
@@ -940,6 +1030,48 @@ KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, con
         if (i < 3) tg.pos[i] = xhat[i] + v;
         else tg.vel[i - 3] = xhat[i] + v;
     }
+    status = 0;
+    return true;
+}
+/* The state part in two phases, for the epoch loop of k_step_imu9, whose covariance is at home in the park: between two
+ * epochs nothing of it is in registers, so the loop's back-edge carries position, velocity and a few words, and the
+ * epoch's measurements are unpacked while the register file is empty.
+ *   step_imu9_head          the head of an epoch's covariance work, run as soon as the covariance is known -- behind
+ *                           the previous epoch's update, or behind the loads: a started tag predicts, parks P and
+ *                           B^-1 and says whether B is invertible; a tag that waits for its ML initialisation parks P
+ *                           as it is.
+ *   step_imu9_state_parked  the rest of step_imu9_state. P is in the park when it is called and in tg.P when it
+ *                           returns, whichever way the step went.
+ * tg.pos must not change between the two (it decides which way the tag goes). */
+KFPOS_FN bool step_imu9_head(Tag9 &tg, const Params &pr, double dt, const CovPark9 &park) {
+    if (imu9_started(tg, pr)) return imu9_predict_park(tg.P, dt, pr.jolt, park);
+    imu9_park(tg.P, park);
+    return false;
+}
+template <bool RANGING, bool HOLD = true, class SC>
+KFPOS_FN bool step_imu9_state_parked(Tag9 &tg, SC &sc, const Params &pr, double dt, const Imu &imu,
+                                     const CovPark9 &park, bool fast, bool invertible, Iekf9Out &o, uint32_t &status) {
+    constexpr bool has_ranging = RANGING;
+    const int n_valid = has_ranging ? count_used(sc, pr, 0) : 0;
+    if (!imu9_started(tg, pr)) {
+        double c[6];
+        if (imu9_ml_init<RANGING>(tg.pos, sc, pr, n_valid, c, status)) { /* xy block only, :134-137 */
+            park.a[Cov<9, true>::idx(0, 0) * park.stride] = c[0];
+            park.a[Cov<9, true>::idx(0, 1) * park.stride] = c[1];
+            park.a[Cov<9, true>::idx(1, 1) * park.stride] = c[3];
+        }
+        imu9_unpark(tg.P, park);
+        return false;
+    }
+    double xhat[9];
+    imu9_predict_state(tg, dt, xhat);
+    iekf9_weights(xhat, sc, pr, has_ranging, n_valid, o); /* position + epoch only */
+    if (o.flags & ST_UPDATE_SKIPPED) { /* (the park holds the predicted covariance) */
+        imu9_unpark(tg.P, park);
+        status = ST_UPDATE_SKIPPED;
+        return false;
+    }
+    imu9_iterate<RANGING, HOLD, true>(tg, xhat, sc, pr, imu, park, fast, invertible, o);
     status = 0;
     return true;
 }

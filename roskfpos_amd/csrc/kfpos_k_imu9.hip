@@ -5,6 +5,16 @@
 
 namespace {
 
+/* a 4-byte value that is (and stays) in an accumulation register at this point */
+template <typename W>
+__device__ inline void in_agpr(W &w) {
+    static_assert(sizeof(W) == 4, "one register");
+    asm volatile("" : "+a"(w));
+}
+
+/* v holds nothing in particular from here on: ends the life of whatever it held, without an instruction */
+__device__ inline void forget(double &v) { asm volatile("" : "=v"(v)); }
+
 /* ------------------------------------------------------------------ 9-state step kernel */
 /* RANGING = false: the IMU-only call (MODE_IMU_ONLY), a kernel of its own */
 template <typename REAL, typename MREAL, int AS, bool RANGING = true>
@@ -110,12 +120,88 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
     double dt_next = multi ? a.dt_steps[0] : dt_tag;
     /* the accelerometer sample of the next epoch travels with its ranges where the two are fetched together (below) */
     constexpr bool IMU_WITH_EPOCH = AHEAD && AS > 0 && RANGING;
+    /* the order of an epoch's phases: rotated (below) in the KFPOS_STORE_MIXED instantiation with 8 anchors, the bench
+     * kernel; the others keep the order of step_imu9_state. KFPOS_STORE_P48 with 8 anchors was built and measured in the
+     * rotated order too: its register allocation came out with as many copies as before, in other places, and 0.5 %
+     * slower (profiles/HISTORY.md); 8-byte measurements, 4-byte covariance, the generic anchor loop and the IMU-only
+     * kernel do not fetch ahead and were left alone */
+    constexpr bool ROTATE = IMU_WITH_EPOCH && AS == 8 && std::is_same<REAL, double>::value;
 
     /* Everything loaded so far has arrived before the loop is entered (the first thing a step does is predict the
      * covariance, so nothing is lost): a wait for these loads INSIDE the loop would be repeated in every epoch, where it
      * waits for the epoch that was only just prefetched. 0x0F70 = vmcnt(0), the other counters untouched. */
     __builtin_amdgcn_s_waitcnt(0x0F70);
     uint32_t s = 0;
+    if constexpr (ROTATE) {
+        /* The covariance is at home in the park: the head of an epoch's covariance work (prediction, B, the park stores,
+         * B^-1) runs behind the update of the epoch before it -- on the P that is in registers there anyway, with the dt
+         * that is in a scalar register one epoch ahead -- and the first one here, behind the loads. Across the back-edge a
+         * lane carries position, velocity, its words and `invertible`, nothing of P: the ways a step can end (ML
+         * initialisation, too few ranges, update skipped, either form of the iteration) all end with P read from the park,
+         * so their join copies nothing. The epoch's measurements are unpacked at the top of the body, where the register
+         * file is empty, and the next epoch is fetched right there, once, on a path every lane takes. */
+        /* (a launch holds at least one epoch -- no host entry point launches a kernel for none --, so the P this head
+         * predicts is always consumed by a body) */
+        bool invertible = step_imu9_head(tg, pr, dt_next, park);
+        double latched[3] = {0.0, 0.0, 0.0};
+        if (!fresh_imu && imu.has) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) latched[k] = imu.acc[k];
+        }
+        for (int e = 0; e < a.n_steps; ++e) {
+            const double dt = dt_next;
+            const bool more = e + 1 < a.n_steps;
+            if (multi && more) dt_next = a.dt_steps[opaque_uniform(e + 1)];
+            /* the raw words are read where the prefetch put them (accumulation registers: the directly addressable half
+             * of the file is taken while they arrive) -- said aloud, so that they cross the back-edge there instead of
+             * being copied out in front of it and back in behind it */
+#pragma unroll
+            for (int k = 0; k < NA; ++k) { in_agpr(raw.mm[k]); in_agpr(raw.e[k]); }
+            if (fresh_imu) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) in_agpr(rawi.acc[k]);
+            }
+            /* (written as a choice between the fresh sample and the latched one, which does not change during a launch:
+             * the sample is then formed anew in every epoch instead of being carried round the loop) */
+#pragma unroll
+            for (int k = 0; k < 3; ++k) imu.acc[k] = fresh_imu ? (double)rawi.acc[k] : latched[k];
+            RegScratch<NA> sc;
+            unpack_epoch<MREAL, NA>(raw, sc);
+            /* unpacked before the next epoch is fetched: the new words then land in the registers the old ones leave */
+#pragma unroll
+            for (int k = 0; k < NA; ++k) { kfpos::kf_pin(sc.r[k]); kfpos::kf_pin(sc.e[k]); }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) kfpos::kf_pin(imu.acc[k]);
+            asm volatile("" ::: "memory");
+            /* (unconditional: behind a test of `more` the raw words would be carried round the loop as a choice between
+             * the old and the new ones, through a second set of registers; the last epoch fetches itself once more) */
+            const int ahead = opaque_uniform(more ? e + 1 : e);
+            fetch_epoch<MREAL, NA>(a, opaque_lane(t), ahead, raw);
+            if (fresh_imu) fetch_imu<MREAL>(a, opaque_lane(t), ahead, rawi);
+            Iekf9Out o;
+            /* a step that ends early leaves `o` unwritten, and the compiler then carries the last epoch's values round
+             * the loop for it: say that they start out as nothing in particular (no instruction) */
+#pragma unroll
+            for (int k = 0; k < 6; ++k) { forget(o.w[k]); forget(o.mrlast[k]); }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) forget(o.dlast[k]);
+            const bool update = step_imu9_state_parked<RANGING>(tg, sc, pr, dt, imu, park, fast, invertible, o, s);
+            if (a.traj) { /* the pose store between the two parts: see the other order below */
+#pragma unroll
+                for (int k = 0; k < 3; ++k) (a.traj + ((size_t)opaque_uniform(e) * 3 + k) * T)[t32] = tg.pos[k];
+            }
+            if (update) s = step_imu9_cov(tg, o, imu);
+            if (more) {
+                static_assert(!cov_is_rounded<REAL>(), "a rounded covariance is rounded here, in front of the head");
+                invertible = step_imu9_head(tg, pr, dt_next, park);
+                /* P is in the park now, and the next body reads it from there whichever way it goes: nothing of it is
+                 * alive in registers (the compiler does not see that `more` means one more trip, and would keep all 45
+                 * entries through the inversion for the stores behind the loop) */
+#pragma unroll
+                for (int k = 0; k < 45; ++k) forget(tg.P.a[k]);
+            }
+        }
+    } else
     for (int e = 0; e < a.n_steps; ++e) { /* the state stays in registers from epoch to epoch */
         const double dt = dt_next;
         if (multi && e + 1 < a.n_steps) dt_next = a.dt_steps[opaque_uniform(e + 1)];
