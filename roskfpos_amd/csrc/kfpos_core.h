@@ -261,6 +261,7 @@ struct Params {
     const double *pair_anchor_tab = nullptr; /* 9-state kernel: [8][3] copy of the anchor table that lanes can index
                                                 individually (LDS); non-null = the tail of the gain iteration runs two
                                                 lanes per tag (iekf9_pairs) */
+    bool pair9 = false; /* the same for a kernel whose pairs read the anchors from the kernel arguments (iekf9_pairs_held) */
 };
 
 /* ------------------------------------------------------------------ 3x3 helpers */

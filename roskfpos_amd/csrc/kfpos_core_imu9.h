@@ -424,7 +424,8 @@ KFPOS_FN void sym6_solve(const Cov<6, true> &K, const double b[6], double x[6]) 
 
 /* ---- the information-form iteration, in pieces: sweep (sums over the anchors at the current iterate), pass (cost,
  * convergence test, next iterate). One tag per lane runs sweep + pass in a loop; once at most half of a wavefront's
- * lanes are still iterating, iekf9_pairs hands every survivor to a PAIR of lanes that splits its sweep. */
+ * lanes are still iterating, iekf9_pairs / iekf9_pairs_held hand every survivor to a PAIR of lanes that splits its sweep
+ * (Params::pair9 / pair_anchor_tab: the host decides, kfpos_create). */
 struct Sweep9 {
     double c, m[6], u[3]; /* sum of w y^2; M = sum of w g g' {00,01,02,11,12,22}; sum of w y g */
 };
@@ -657,7 +658,11 @@ KFPOS_FN int nth_set_bit(uint64_t m, int n) {
  * owner would have formed -- and both lanes run the pass on identical numbers. Results go back to the owners, which
  * cannot tell that it happened: same bits. (The sweep is written with explicit fma for that; the pass is the same
  * inlined function at both places, and that the compiler contracts it the same way twice is what
- * tests/test_pairs9_gpu.py checks on every build -- it is not a guarantee of the language.) */
+ * tests/test_pairs9_gpu.py checks on every build -- it is not a guarantee of the language.)
+ * This text reads B^-1, Sigma^-1 and nine anchor coordinates from LDS in EVERY trip. It is what the 8-anchor step
+ * kernels with 8-byte measurements or a 4-byte covariance run (held in registers, those values make them spill inside
+ * the epoch loop) and what the event kernels compile without ever running it (they never form pairs; taking the text
+ * away makes them spill too). The two headline kernels run iekf9_pairs_held, below, by default; these run theirs with KFPOS_PAIR9=1. */
 template <bool DIAG, bool ACC0>
 KFPOS_FN void iekf9_pairs(uint64_t m, const double xhat[9], const double *binv, int binv_stride,
                           const RegScratch<8> &sc, const double *anchor_tab, const Imu &imu, int max_steps, double tol,
@@ -746,6 +751,111 @@ KFPOS_FN void iekf9_pairs(uint64_t m, const double xhat[9], const double *binv, 
     const int gi = __builtin_amdgcn_ds_bpermute(from4, co.gain_iters);
     if (owner) { it.cost = cst; o.gain_iters = gi; }
 }
+/* The same tail for a kernel that has the registers (TAIL of iekf9_info: the KFPOS_STORE_MIXED and KFPOS_STORE_P48
+ * 8-anchor step kernels): same pairs, same sweep, same exchange, same pass, same bits (tests/test_pairs9_tail_gpu.py).
+ * A pair trip pays for arithmetic only, like a trip of the one-tag-per-lane loop (tools/pairs_loop_shape.py keeps it so
+ * at build time): everything it reads is in registers in front of the loop.
+ *   going in   by ds_bpermute, what the iteration carries and what a sweep reads: position, ve, qd, cost, the sample, the
+ *              ranges and weights (both halves; parity selects), the count. NOT wl / mrlast / dlast: they are results of
+ *              the last solve, which a pass that goes on overwrites and a pass that stops does not look at.
+ *   B^-1, Sigma^-1   read ONCE from the owner's column of the park, pinned, and arrived before the first trip. The
+ *              iteration ends in this function, so they take the registers of the lane's own copy.
+ *   anchors    from the kernel arguments: a lane's four are a parity select between two wave-uniform values, held.
+ *   coming out wl, mrlast, dlast, cost and the count, for the owners whose count moved here; an owner whose survivor
+ *              converged in the pair's first pass keeps its own values, untouched.
+ * ALLIMU: as in iekf9_pass -- the pair pass takes the form its wavefront runs; imu.has is then neither pulled nor looked
+ * at. */
+template <bool DIAG, bool ALLIMU, bool ACC0>
+KFPOS_FN void iekf9_pairs_held(uint64_t m, const double xhat[9], const double *binv, int binv_stride,
+                               const RegScratch<8> &sc, const Params &pr, const Imu &imu, int max_steps, double tol,
+                               Iekf9Iter &it, Iekf9Out &o) {
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int g = lane >> 1;
+    const bool h = lane & 1;
+    const int n_surv = __popcll(m);
+    bool act = g < n_surv;
+    const int src = nth_set_bit(m, act ? g : 0);
+    const int src4 = src << 2;
+    /* the owner's column of the park first: LDS answers in order, the pulls queue up behind these reads */
+    Imu ci;
+    ci.ci = imu.ci + (src - lane);
+    ci.ci_stride = imu.ci_stride;
+    Iekf9Parked pk;
+    iekf9_fetch<false, DIAG, false>(binv + (src - lane), binv_stride, ci, pk);
+    double xh[9];
+    KFPOS_UNROLL
+    for (int k = 0; k < 3; ++k) {
+        xh[k] = lane_pull(xhat[k], src4);
+        xh[3 + k] = 0.0; /* (the velocity prediction plays no role in the iteration) */
+        xh[6 + k] = ACC0 ? 0.0 : lane_pull(xhat[6 + k], src4);
+    }
+    Iekf9Iter ct;
+    KFPOS_UNROLL
+    for (int k = 0; k < 6; ++k) { ct.ve[k] = lane_pull(it.ve[k], src4); ct.wl[k] = 0.0; }
+    ct.qd = lane_pull(it.qd, src4);
+    ct.cost = lane_pull(it.cost, src4);
+    Iekf9Out co;
+    KFPOS_UNROLL
+    for (int k = 0; k < 6; ++k) co.mrlast[k] = 0.0;
+    KFPOS_UNROLL
+    for (int k = 0; k < 3; ++k) co.dlast[k] = 0.0;
+    co.gain_iters = __builtin_amdgcn_ds_bpermute(src4, o.gain_iters);
+    ci.has = ALLIMU || __builtin_amdgcn_ds_bpermute(src4, imu.has ? 1 : 0) != 0;
+    KFPOS_UNROLL
+    for (int k = 0; k < 3; ++k) ci.acc[k] = lane_pull(imu.acc[k], src4);
+    double r4[4], w4[4], bb[12];
+    KFPOS_UNROLL
+    for (int k = 0; k < 4; ++k) {
+        const double r0 = lane_pull(sc.r[k], src4), r1 = lane_pull(sc.r[4 + k], src4);
+        const double w0 = lane_pull(sc.w[k], src4), w1 = lane_pull(sc.w[4 + k], src4);
+        r4[k] = h ? r1 : r0;
+        w4[k] = h ? w1 : w0;
+    }
+    KFPOS_UNROLL
+    for (int k = 0; k < 12; ++k) { /* this lane's four anchors, xyz */
+        bb[k] = h ? pr.anchors[12 + k] : pr.anchors[k];
+        kf_pin(bb[k]);
+    }
+    KFPOS_UNROLL
+    for (int k = 0; k < 21; ++k) kf_pin(pk.binv[k]);
+    KFPOS_UNROLL
+    for (int k = 0; k < 6; ++k) {
+        if (!DIAG || k == 0 || k == 3 || k == 5) kf_pin(pk.wi[k]);
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0): nothing is on its way when the first trip starts */
+    while (act) { /* (both lanes of a pair leave together) */
+        const double p[3] = {xh[0] + ct.ve[0], xh[1] + ct.ve[1], xh[2] + ct.ve[2]};
+        Sweep9 sw, other;
+        iekf9_sweep4(p, r4, w4, bb, sw);
+        other.c = dpp_exchange(sw.c, 0);
+        KFPOS_UNROLL
+        for (int k = 0; k < 6; ++k) other.m[k] = dpp_exchange(sw.m[k], 0);
+        KFPOS_UNROLL
+        for (int k = 0; k < 3; ++k) other.u[k] = dpp_exchange(sw.u[k], 0);
+        /* the lower lane holds (0-3) and adds (4-7); the upper one adds them the other way round: same sums */
+        sweep9_add(sw, other);
+        const bool more = iekf9_pass<DIAG, ALLIMU>(xh, pk, ci, tol, sw, ct, co);
+        act = more && co.gain_iters < max_steps;
+    }
+    /* back to the owners: the k-th survivor reads lane 2k. Only a pass that went on has written anything */
+    const bool owner = (m >> lane) & 1ull;
+    const int rank = __popcll(m & ((1ull << lane) - 1ull));
+    const int from4 = (owner ? 2 * rank : lane) << 2;
+    const int gi = __builtin_amdgcn_ds_bpermute(from4, co.gain_iters);
+    const bool moved = owner && gi != o.gain_iters;
+    KFPOS_UNROLL
+    for (int k = 0; k < 6; ++k) {
+        const double a = lane_pull(ct.wl[k], from4), b = lane_pull(co.mrlast[k], from4);
+        if (moved) { it.wl[k] = a; o.mrlast[k] = b; }
+    }
+    KFPOS_UNROLL
+    for (int k = 0; k < 3; ++k) {
+        const double a = lane_pull(co.dlast[k], from4);
+        if (moved) o.dlast[k] = a;
+    }
+    const double cst = lane_pull(ct.cost, from4);
+    if (moved) { it.cost = cst; o.gain_iters = gi; }
+}
 #endif
 
 /* ACC0: the predicted acceleration xhat[6..8] is the literal 0 on every lane (KalmanFilterTOAIMU.cpp restarts it at
@@ -755,8 +865,13 @@ KFPOS_FN void iekf9_pairs(uint64_t m, const double xhat[9], const double *binv, 
  * them and would spill inside its epoch loop instead.
  * SETTLE: the held values have arrived before the first trip. A caller in whose step nothing else stands between the
  * fetch and the loop sets it: the compiler otherwise waits for the last of them where a trip first uses them, and that
- * wait is then executed in every trip. */
-template <bool DIAG, bool ALLIMU, bool RANGING, bool ACC0 = false, bool HOLD = true, bool SETTLE = false, class SC>
+ * wait is then executed in every trip.
+ * TAIL: the pairs' tail is iekf9_pairs_held (Params::pair9 says whether it runs) instead of iekf9_pairs. Set by the
+ * 8-anchor step kernels that have the registers to hold what a pair trip reads (k_step_imu9 says which); every other
+ * caller compiles the text it always compiled -- the event kernels, which never form pairs at run time, sit at the top
+ * of the register file and spill inside their loops when that text changes, even when it only goes away. */
+template <bool DIAG, bool ALLIMU, bool RANGING, bool ACC0 = false, bool HOLD = true, bool SETTLE = false,
+          bool TAIL = false, class SC>
 KFPOS_FN void iekf9_info(const double xhat[9], const double *binv, int binv_stride, SC &sc, const Params &pr,
                          const Imu &imu, int max_steps, double tol, Iekf9Out &o) {
     Iekf9Iter it;
@@ -769,7 +884,7 @@ KFPOS_FN void iekf9_info(const double xhat[9], const double *binv, int binv_stri
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool PAIRS = RANGING && SC::NA == 8 && SC::CHUNK == 0 && !SC::COOP;
     /* every lane of the wavefront is here (none left early, none took the other form): pairs can be formed */
-    const bool pairs = PAIRS && pr.pair_anchor_tab && __builtin_amdgcn_ballot_w64(true) == ~0ull;
+    const bool pairs = PAIRS && (TAIL ? pr.pair9 : pr.pair_anchor_tab != nullptr) && __builtin_amdgcn_ballot_w64(true) == ~0ull;
 #endif
     bool more = true; /* false: converged */
     int stop = max_steps;
@@ -798,7 +913,8 @@ KFPOS_FN void iekf9_info(const double xhat[9], const double *binv, int binv_stri
                 const uint64_t m = __builtin_amdgcn_ballot_w64(more && o.gain_iters < max_steps);
                 if (m == 0) break;
                 if (__popcll(m) <= 32) {
-                    iekf9_pairs<DIAG, ACC0>(m, xhat, binv, binv_stride, sc, pr.pair_anchor_tab, imu, max_steps, tol, it, o);
+                    if constexpr (TAIL) iekf9_pairs_held<DIAG, ALLIMU, ACC0>(m, xhat, binv, binv_stride, sc, pr, imu, max_steps, tol, it, o);
+                    else iekf9_pairs<DIAG, ACC0>(m, xhat, binv, binv_stride, sc, pr.pair_anchor_tab, imu, max_steps, tol, it, o);
                     break;
                 }
                 stop = stop + 4 < max_steps ? stop + 4 : max_steps;
@@ -917,15 +1033,15 @@ KFPOS_FN bool imu9_predict_park(Cov<9, true> &P, double dt, double jolt, const C
     return sym6_inverse(B, park.a + 45 * park.stride, park.stride, INFO_FORM_MIN_PIVOT);
 }
 /* the gain iteration on the parked covariance, which it leaves in P, and the updated position and velocity */
-template <bool RANGING, bool HOLD, bool SETTLE, class SC>
+template <bool RANGING, bool HOLD, bool SETTLE, bool TAIL, class SC>
 KFPOS_FN void imu9_iterate(Tag9 &tg, const double xhat[9], SC &sc, const Params &pr, const Imu &imu,
                            const CovPark9 &park, bool fast, bool invertible, Iekf9Out &o) {
     double *binv = park.a + 45 * park.stride;
     /* per lane, not per wavefront: a tag's arithmetic must not depend on its wave-mates (a wavefront whose lanes
      * disagree runs both forms one after the other, each under its lanes' mask) */
     if (invertible) {
-        if (fast) iekf9_info<true, true, RANGING, true, HOLD, SETTLE>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
-        else iekf9_info<false, false, RANGING, true, HOLD, SETTLE>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
+        if (fast) iekf9_info<true, true, RANGING, true, HOLD, SETTLE, TAIL>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
+        else iekf9_info<false, false, RANGING, true, HOLD, SETTLE, TAIL>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
         imu9_unpark(tg.P, park);
     } else {
         imu9_unpark(tg.P, park);
@@ -954,7 +1070,7 @@ KFPOS_FN void imu9_iterate(Tag9 &tg, const double xhat[9], SC &sc, const Params 
  * form, which looks at imu.has lane by lane. (Two forms, not four: a third and a fourth copy of the trip loop for
  * diagonal-but-partly-latched and full-and-all-sampled wavefronts would add 2 x ~570 instructions to an epoch loop of
  * ~10 400 for wavefronts that are rare -- latched lanes exist only in MODE_TOA calls -- and lose 0.9 us an epoch.) */
-template <bool RANGING, bool HOLD = true, class SC>
+template <bool RANGING, bool HOLD = true, bool TAIL = false, class SC>
 KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, const Imu &imu, const CovPark9 &park,
                               bool fast, Iekf9Out &o, uint32_t &status) {
     constexpr bool has_ranging = RANGING;
@@ -1012,8 +1128,8 @@ KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, con
     /* per lane, not per wavefront: a tag's arithmetic must not depend on its wave-mates (a wavefront whose lanes
      * disagree runs both forms one after the other, each under its lanes' mask) */
     if (invertible) {
-        if (fast) iekf9_info<true, true, RANGING, true, HOLD>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
-        else iekf9_info<false, false, RANGING, true, HOLD>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
+        if (fast) iekf9_info<true, true, RANGING, true, HOLD, false, TAIL>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
+        else iekf9_info<false, false, RANGING, true, HOLD, false, TAIL>(xhat, binv, park.stride, sc, pr, imu, 20, 1e-4, o);
         KFPOS_UNROLL
         for (int k = 0; k < 45; ++k) tg.P.a[k] = park.a[k * park.stride];
     } else {
@@ -1048,7 +1164,7 @@ KFPOS_FN bool step_imu9_head(Tag9 &tg, const Params &pr, double dt, const CovPar
     imu9_park(tg.P, park);
     return false;
 }
-template <bool RANGING, bool HOLD = true, class SC>
+template <bool RANGING, bool HOLD = true, bool TAIL = false, class SC>
 KFPOS_FN bool step_imu9_state_parked(Tag9 &tg, SC &sc, const Params &pr, double dt, const Imu &imu,
                                      const CovPark9 &park, bool fast, bool invertible, Iekf9Out &o, uint32_t &status) {
     constexpr bool has_ranging = RANGING;
@@ -1071,7 +1187,7 @@ KFPOS_FN bool step_imu9_state_parked(Tag9 &tg, SC &sc, const Params &pr, double 
         status = ST_UPDATE_SKIPPED;
         return false;
     }
-    imu9_iterate<RANGING, HOLD, true>(tg, xhat, sc, pr, imu, park, fast, invertible, o);
+    imu9_iterate<RANGING, HOLD, true, TAIL>(tg, xhat, sc, pr, imu, park, fast, invertible, o);
     status = 0;
     return true;
 }

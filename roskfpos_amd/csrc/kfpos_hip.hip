@@ -367,8 +367,12 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
             if (!(ow && ow[0] == '1') && hipGetDeviceProperties(&prop, cfg->device) == hipSuccess)
                 h->two_waves = ((size_t)cfg->n_tags + WAVE - 1) / WAVE > (size_t)prop.multiProcessorCount * 4;
         }
+        /* the pairs' tail of the 9-state gain iteration (8 anchors): on where it was measured to win -- the two kernels
+         * whose pair trips read registers only (4-byte measurements with an 8- or 6-byte covariance); the other two
+         * storage modes keep it opt-in. KFPOS_PAIR9=0 / =1 overrides either way */
         const char *np = getenv("KFPOS_PAIR9");
-        h->pair9 = np && np[0] == '1';
+        h->pair9 = np && np[0] ? np[0] == '1'
+                               : (cfg->storage == KFPOS_STORE_MIXED || cfg->storage == KFPOS_STORE_P48);
         const char *nd = getenv("KFPOS_IMU9_DIAG");
         h->imu9_diag = !(nd && nd[0] == '0');
         const char *nc = getenv("KFPOS_NO_COOP");

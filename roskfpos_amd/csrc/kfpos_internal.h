@@ -45,7 +45,7 @@ struct kfpos_handle {
     int trace_chunk;    /* epochs per launch in kfpos_run_trace_dev (KFPOS_TRACE_CHUNK_STEPS, 1..128) */
     bool force_generic; /* KFPOS_GENERIC_KERNEL=1: always the LDS-staged kernel (A/B measurements, tests) */
     bool two_waves;     /* n_tags / 64 exceeds the device's SIMD count (KFPOS_ONE_WAVE_BUILD=1: never) */
-    bool pair9;         /* 9-state bank: iekf9_pairs for the tail of the gain iteration; KFPOS_PAIR9=1 enables (built, bit-identical, measured: no gain worth having -- DESIGN 6a) */
+    bool pair9;         /* 9-state bank: iekf9_pairs for the tail of the gain iteration; bit-identical either way. Default: on in KFPOS_STORE_MIXED and KFPOS_STORE_P48, whose pair trips read registers only (2.8 % fewer cycles per epoch), off in the other two; KFPOS_PAIR9=0 / =1 overrides (profiles/HISTORY.md, "The pairs' tail") */
     bool imu9_diag;     /* 9-state bank: wavefronts with diagonal accelerometer covariances take the diagonal form of the gain iteration (bit-identical); KFPOS_IMU9_DIAG=0 disables */
     bool coop;          /* small plain 6-state bank: one tag per 8 lanes (k_step_toa6_coop); KFPOS_NO_COOP=1 disables */
     double anchors[KFPOS_MAX_ANCHORS * 3];

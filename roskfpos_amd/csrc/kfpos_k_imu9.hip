@@ -66,7 +66,13 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
     imu.has = false;
     imu.ci = park.a + 66 * WAVE;
     imu.ci_stride = WAVE;
-    if constexpr (AS == 8 && RANGING) { /* the anchor table once more, where lanes can index it one by one (iekf9_pairs) */
+    /* The tail of the gain iteration on pairs of lanes. TAIL: a pair trip reads registers only (iekf9_pairs_held) -- the
+     * 4-byte-measurement kernels with an 8-byte or 6-byte covariance, the two the bench configurations run. With 8-byte
+     * measurements (22 more registers across the step) or the 4-byte covariance's rounding code the held values do not
+     * fit: those two keep the tail that reads the park and a copy of the anchor table in every trip (iekf9_pairs). */
+    constexpr bool TAIL = AS == 8 && RANGING && sizeof(MREAL) == 4 && !std::is_same<REAL, float>::value;
+    if constexpr (TAIL) pr.pair9 = a.pair9 != 0;
+    else if constexpr (AS == 8 && RANGING) { /* the anchor table once more, where lanes can index it one by one */
         if (a.pair9) {
             double *tab = lds + 78 * WAVE;
 #pragma unroll
@@ -185,7 +191,7 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
             for (int k = 0; k < 6; ++k) { forget(o.w[k]); forget(o.mrlast[k]); }
 #pragma unroll
             for (int k = 0; k < 3; ++k) forget(o.dlast[k]);
-            const bool update = step_imu9_state_parked<RANGING>(tg, sc, pr, dt, imu, park, fast, invertible, o, s);
+            const bool update = step_imu9_state_parked<RANGING, true, TAIL>(tg, sc, pr, dt, imu, park, fast, invertible, o, s);
             if (a.traj) { /* the pose store between the two parts: see the other order below */
 #pragma unroll
                 for (int k = 0; k < 3; ++k) (a.traj + ((size_t)opaque_uniform(e) * 3 + k) * T)[t32] = tg.pos[k];
@@ -240,7 +246,7 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
 #pragma unroll
                 for (int k = 0; k < AS; ++k) sc.r[k] = sc.e[k] = sc.w[k] = 0.0;
             }
-            finish(step_imu9_state<RANGING>(tg, sc, pr, dt, imu, park, fast, o, s));
+            finish(step_imu9_state<RANGING, true, TAIL>(tg, sc, pr, dt, imu, park, fast, o, s));
             if constexpr (!AHEAD) { /* 8-byte measurements: the next epoch is fetched when this one is over */
                 if (e + 1 < a.n_steps) {
                     if (fresh_imu) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
@@ -250,7 +256,7 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
         } else {
             Scratch sc{nullptr, nullptr, nullptr, WAVE};
             if (has_ranging) sc = stage_epoch_lds<MREAL>(a, lds, lane, t, opaque_uniform(e));
-            finish(step_imu9_state<RANGING>(tg, sc, pr, dt, imu, park, fast, o, s));
+            finish(step_imu9_state<RANGING, true, TAIL>(tg, sc, pr, dt, imu, park, fast, o, s));
             if constexpr (!AHEAD) { /* the ranges are staged per epoch above; the next accelerometer sample is not */
                 if (e + 1 < a.n_steps && fresh_imu) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
             }

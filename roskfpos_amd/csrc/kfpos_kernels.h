@@ -49,7 +49,7 @@ struct KArgs {
     int T, A;
     double accel_noise, jolt, cost_threshold;
     int ignore_worst, top_n, use_init_pos, ml_variant;
-    int pair9;        /* 9-state kernel: two lanes per tag for the tail of the gain iteration (KFPOS_PAIR9=1; off by default: DESIGN 6a) */
+    int pair9;        /* 9-state kernel: two lanes per tag for the tail of the gain iteration (default: on in the mixed and p48 storage modes; KFPOS_PAIR9=0 / =1 overrides: profiles/HISTORY.md "The pairs' tail") */
     int imu9_diag;    /* 9-state kernel: a wavefront whose accelerometer covariances are all diagonal runs the diagonal form of the gain iteration's pass (same bits; KFPOS_IMU9_DIAG=0: never) */
     /* planar filter configuration (kfpos_planar_config) */
     int use_fixed_height, imu_fixed_cov_acc, imu_fixed_cov_w;

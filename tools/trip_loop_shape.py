@@ -21,8 +21,8 @@ blocks, as long as a part of it still holds that many -- and fails when one of t
     than one `s_and_saveexec` in the loop; the fast form has one, around the solve). Every kernel must have a fast
     form: if the per-lane branch came back into it, no loop with a single masked region would be left, and that fails.
 Two kinds of loop are listed but not judged:
-  * the pairs' loop (iekf9_pairs: two lanes per tag, off by default), which reads its parked values in every trip by
-    design; it is recognised by its DPP exchange (an instruction with a quad_perm modifier);
+  * the pairs' loop (two lanes per tag), which has a rule of its own (tools/pairs_loop_shape.py); it is recognised by its
+    DPP exchange (an instruction with a quad_perm modifier);
   * loops with more than --max-fp64 (700) fp64 instructions: the (I + M B) form of the iteration, taken right after a
     fixed start while B is singular, whose loop holds an adjugate and a pivoted solve side by side (~950).
 It prints the instruction mix of every loop it looked at.
