@@ -149,17 +149,17 @@ struct Iekf9Out {
 
 /* kalmanStep3D (KalmanFilterTOAIMU.cpp:242-340, with the 3-token repair), first part (:268-276): ML
  * position -> observation covariance of the ranging rows. Independent of P. */
-template <class SC>
+template <bool SELECTS = true, class SC>
 KFPOS_FN void iekf9_weights(const double xhat[9], SC &sc, const Params &pr, bool has_ranging, int n_used,
                             Iekf9Out &o) {
     o.flags = (has_ranging && n_used < 4) ? ST_FEW_RANGES : 0u;
     o.ml_iters = 0;
     if (has_ranging) {
         double pml[3] = {xhat[0], xhat[1], xhat[2]}, e_ml;
-        set_weights_ml(sc, pr, 0ull);
+        set_weights_ml<SELECTS>(sc, pr, 0ull);
         o.ml_iters = ml_estimate(pml, sc, pr, 0ull, n_used, e_ml); /* no NaN fallback in this filter */
-        if (ml_covariance_throws(sc, pr, 0ull, n_used, e_ml)) o.flags |= ST_UPDATE_SKIPPED;
-        set_weights_iekf(sc, pr, e_ml, 0ull);
+        if (ml_covariance_throws<SELECTS>(sc, pr, 0ull, n_used, e_ml)) o.flags |= ST_UPDATE_SKIPPED;
+        set_weights_iekf<SELECTS>(sc, pr, e_ml, 0ull);
     }
 }
 
@@ -841,20 +841,22 @@ KFPOS_FN void iekf9_pairs_held(uint64_t m, const double xhat[9], const double *b
     const bool owner = (m >> lane) & 1ull;
     const int rank = __popcll(m & ((1ull << lane) - 1ull));
     const int from4 = (owner ? 2 * rank : lane) << 2;
+    /* every pull issued back to back, one round trip; then selects: assigned under `if (moved)` value by value, the
+     * return compiles to nine masked regions with a wait in front of each */
     const int gi = __builtin_amdgcn_ds_bpermute(from4, co.gain_iters);
-    const bool moved = owner && gi != o.gain_iters;
+    double back[16];
     KFPOS_UNROLL
-    for (int k = 0; k < 6; ++k) {
-        const double a = lane_pull(ct.wl[k], from4), b = lane_pull(co.mrlast[k], from4);
-        if (moved) { it.wl[k] = a; o.mrlast[k] = b; }
-    }
+    for (int k = 0; k < 6; ++k) { back[k] = lane_pull(ct.wl[k], from4); back[6 + k] = lane_pull(co.mrlast[k], from4); }
     KFPOS_UNROLL
-    for (int k = 0; k < 3; ++k) {
-        const double a = lane_pull(co.dlast[k], from4);
-        if (moved) o.dlast[k] = a;
-    }
-    const double cst = lane_pull(ct.cost, from4);
-    if (moved) { it.cost = cst; o.gain_iters = gi; }
+    for (int k = 0; k < 3; ++k) back[12 + k] = lane_pull(co.dlast[k], from4);
+    back[15] = lane_pull(ct.cost, from4);
+    const bool moved = owner & (gi != o.gain_iters);
+    KFPOS_UNROLL
+    for (int k = 0; k < 6; ++k) { it.wl[k] = moved ? back[k] : it.wl[k]; o.mrlast[k] = moved ? back[6 + k] : o.mrlast[k]; }
+    KFPOS_UNROLL
+    for (int k = 0; k < 3; ++k) o.dlast[k] = moved ? back[12 + k] : o.dlast[k];
+    it.cost = moved ? back[15] : it.cost;
+    o.gain_iters = moved ? gi : o.gain_iters;
 }
 #endif
 
@@ -1069,8 +1071,11 @@ KFPOS_FN void imu9_iterate(Tag9 &tg, const double xhat[9], SC &sc, const Params 
  * numbers in the same order, minus the terms that are exact zeros, i.e. the same bits. false is always right: the full
  * form, which looks at imu.has lane by lane. (Two forms, not four: a third and a fourth copy of the trip loop for
  * diagonal-but-partly-latched and full-and-all-sampled wavefronts would add 2 x ~570 instructions to an epoch loop of
- * ~10 400 for wavefronts that are rare -- latched lanes exist only in MODE_TOA calls -- and lose 0.9 us an epoch.) */
-template <bool RANGING, bool HOLD = true, bool TAIL = false, class SC>
+ * ~10 400 for wavefronts that are rare -- latched lanes exist only in MODE_TOA calls -- and lose 0.9 us an epoch.)
+ * SELECTS: the weights of the epoch (set_weights_ml, ml_covariance_throws, set_weights_iekf) in their select forms.
+ * false keeps the conditional text, same results: k_events_imu9 sets it, which spills inside its event loop with the
+ * select forms (make check's scratch rule decides, as for HOLD). */
+template <bool RANGING, bool HOLD = true, bool TAIL = false, bool SELECTS = true, class SC>
 KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, const Imu &imu, const CovPark9 &park,
                               bool fast, Iekf9Out &o, uint32_t &status) {
     constexpr bool has_ranging = RANGING;
@@ -1081,10 +1086,10 @@ KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, con
         status = ST_FEW_RANGES;
         if (n_valid < 4) return false;
         double p[3] = {1.0, 1.0, 4.0}, sse, c[6];
-        set_weights_ml(sc, pr, 0ull);
+        set_weights_ml<SELECTS>(sc, pr, 0ull);
         const int it = ml_estimate(p, sc, pr, 0, n_valid, sse);
         status = ST_UPDATE_SKIPPED;
-        if (ml_covariance_throws(sc, pr, 0, n_valid, sse)) return false; /* reference: abort */
+        if (ml_covariance_throws<SELECTS>(sc, pr, 0, n_valid, sse)) return false; /* reference: abort */
         if (!ml_covariance(p, sc, pr, sse, c)) return false;
         tg.pos[0] = p[0]; tg.pos[1] = p[1]; tg.pos[2] = p[2];
         tg.P(0, 0) = c[0]; tg.P(0, 1) = c[1]; tg.P(1, 1) = c[3]; /* xy block only, :134-137 */
@@ -1116,7 +1121,7 @@ KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, con
     /* B safely invertible on every lane: the information-form iteration (the usual case); otherwise -- right after a
      * fixed start, B is singular -- the (I + M B) form */
     const bool invertible = sym6_inverse(B, binv, park.stride, INFO_FORM_MIN_PIVOT);
-    iekf9_weights(xhat, sc, pr, has_ranging, n_valid, o); /* position + epoch only */
+    iekf9_weights<SELECTS>(xhat, sc, pr, has_ranging, n_valid, o); /* position + epoch only */
     /* The 9-state filter has no try/catch: the reference node aborts here. This core keeps the predicted
      * covariance and reports the tag instead. */
     if (o.flags & ST_UPDATE_SKIPPED) {

@@ -188,13 +188,22 @@ KFPOS_FN bool ml_covariance(const double p[3], const SC &sc, const Params &pr, d
  * The first one throws std::runtime_error when an entry is exactly 0 -- which is what an errorEstimation of 0
  * leads to: the 1/e weights make the ML position NaN, e_ML is NaN, std::max(e_i, NaN) = e_i = 0. The
  * 6-state filter swallows the exception and skips the update (KalmanFilterTOA.cpp:151-153). */
-template <class SC>
+template <bool SELECTS = true, class SC>
 KFPOS_FN bool ml_covariance_throws(const SC &sc, const Params &pr, uint64_t drop, int n_used, double sse,
                                    int min_used = 4) {
     if (n_used < min_used) return false; /* estimatePosition returned before getting there */
     bool bad = false;
-    for_anchors<SC>(pr, [&](int a) { bad = bad || (used(sc, a, drop) && stdmax(sc.E(a), sse) == 0.0); });
-    if constexpr (SC::COOP) bad = group_sum(sc, bad ? 1.0 : 0.0) > 0.0;
+    if constexpr (SC::COOP || !SELECTS) { /* one anchor per lane; a kernel that keeps the short-circuit */
+        for_anchors<SC>(pr, [&](int a) { bad = bad || (used(sc, a, drop) && stdmax(sc.E(a), sse) == 0.0); });
+        if constexpr (SC::COOP) bad = group_sum(sc, bad ? 1.0 : 0.0) > 0.0;
+    } else {
+        /* every predicate formed, then OR: no short-circuit, which the compiler turns into one masked region per
+         * anchor, nested. The errorEstimation of an absent range is compared and its verdict thrown away. */
+        for_anchors<SC>(pr, [&](int a) {
+            const bool on = used(sc, a, drop), zero = stdmax(sc.E(a), sse) == 0.0;
+            bad = bad | (on & zero);
+        });
+    }
     return bad;
 }
 
@@ -204,22 +213,42 @@ KFPOS_FN bool ml_covariance_throws(const SC &sc, const Params &pr, uint64_t drop
  * form that covariance (an extra sweep per solve, 3-14 % of a step, for a measure-zero geometry); the ML
  * initialisation, which needs the covariance anyway, does report it (ml_covariance / ml2d_covariance). */
 /* Working weights. An absent or dropped range gets weight 0 HERE (a select, so a garbage errorEstimation of a
- * missing range never enters): the sweeps, which run 10-60 times per step, then read the weight as it is. */
-template <class SC>
+ * missing range never enters): the sweeps, which run 10-60 times per step, then read the weight as it is.
+ * The reciprocal is formed for EVERY anchor and selected afterwards: written as `used ? kf_rcp(e) : 0` it compiles to
+ * one masked region per anchor (saveexec, branch, restore around five instructions). The garbage errorEstimation of an
+ * absent range enters a reciprocal whose result is thrown away; nothing here traps. */
+template <bool SELECTS = true, class SC>
 KFPOS_FN void set_weights_ml(SC &sc, const Params &pr, uint64_t drop) {
-    for_anchors<SC>(pr, [&](int a) { sc.setW(a, used(sc, a, drop) ? kf_rcp(sc.E(a)) : 0.0); });
+    if constexpr (SC::COOP || !SELECTS) { /* one anchor per lane; a kernel that keeps the conditional form */
+        for_anchors<SC>(pr, [&](int a) { sc.setW(a, used(sc, a, drop) ? kf_rcp(sc.E(a)) : 0.0); });
+        return;
+    }
+    for_anchors<SC>(pr, [&](int a) {
+        const double rcp = kf_rcp(sc.E(a));
+        sc.setW(a, used(sc, a, drop) ? rcp : 0.0);
+    });
 }
 /* REQUIRES the weights of set_weights_ml(sc, pr, drop) in place: 1 / max(e_ML, e_a) is either that weight (1 / e_a,
  * the same kf_rcp of the same number) or 1 / e_ML, one reciprocal for all anchors instead of one per anchor */
-template <class SC>
+template <bool SELECTS = true, class SC>
 KFPOS_FN void set_weights_iekf(SC &sc, const Params &pr, double e_ml, uint64_t drop) {
     if constexpr (SC::COOP) { /* one anchor per lane: one reciprocal either way, the direct form is shorter */
         sc.setW(0, used(sc, 0, drop) ? kf_rcp(stdmax(e_ml, sc.E(0))) : 0.0);
         return;
     }
     const double r_ml = kf_rcp(e_ml);
+    if constexpr (!SELECTS) {
+        for_anchors<SC>(pr, [&](int a) { sc.setW(a, used(sc, a, drop) ? ((e_ml < sc.E(a)) ? sc.W(a) : r_ml) : 0.0); });
+        return;
+    }
     for_anchors<SC>(pr, [&](int a) { /* KalmanFilterTOA.cpp:281; stdmax(e_ml, e) = e_ml < e ? e : e_ml */
-        sc.setW(a, used(sc, a, drop) ? ((e_ml < sc.E(a)) ? sc.W(a) : r_ml) : 0.0);
+        /* two selects on values that are all there already (nested conditionals compile to nested masked regions).
+         * `on &`: the comparison with an absent range's errorEstimation decides nothing, and says so to a build that
+         * may branch on it (the host emulation under MemorySanitizer, tests/emu/msan_audit.sh) */
+        const bool on = used(sc, a, drop), own = on & (e_ml < sc.E(a));
+        const double w_own = sc.W(a);
+        const double w = own ? w_own : r_ml;
+        sc.setW(a, on ? w : 0.0);
     });
 }
 
