@@ -1,7 +1,8 @@
 /*
  * kfpos_hip.hip -- host side of libkfpos_hip.so: the handle, launch selection, the three ways in (synchronous
  * host-buffer API, streaming slots, device-buffer API) and the C ABI of include/kfpos.h. The kernels live in
- * kfpos_k_*.hip (kfpos_kernels.h says which is where); the RCCL pose gather in kfpos_comm.hip.
+ * kfpos_k_*.hip (kfpos_kernels.h says which is where); the replay entry points (kfpos_run_*_dev: whole schedules in few
+ * launches) in kfpos_hip_replay.hip; the RCCL pose gather in kfpos_comm.hip.
  */
 #include <algorithm>
 #include <cmath>
@@ -20,25 +21,8 @@ std::string &kfpos_error_text() {
     return text;
 }
 
-namespace {
-
 /* ------------------------------------------------------------------ host side */
-#define g_err (kfpos_error_text())
-
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                            \
-            return KFPOS_ERR_HIP;                                                                 \
-        }                                                                                         \
-    } while (0)
-
-} // namespace
-
-
-namespace {
-
+/* shared with kfpos_hip_replay.hip (declared in kfpos_kernels.h) */
 size_t lds_bytes(const kfpos_handle *h) { return (size_t)3 * h->cfg.max_anchors * WAVE * sizeof(double); }
 size_t park_bytes() { return (size_t)36 * WAVE * sizeof(double); } /* 36 doubles per lane: CovSpill8 (planar), Pinv6 (6-state, full) */
 size_t park9_bytes() { return (size_t)78 * WAVE * sizeof(double) + 24 * sizeof(double); } /* CovPark9: the 9-state covariance (45) and B^-1 (21) during the gain iteration, the accelerometer whitener and Sigma^-1 (12), a lane-addressable copy of 8 anchors: 39.2 KB per wavefront, four wavefronts per CU */
@@ -90,6 +74,7 @@ void fill_args(const kfpos_handle *h, KArgs &a) {
     a.traj = nullptr;
 }
 
+namespace {
 
 /* Anchor-count specialisation. 8 anchors (BASELINE configs 2-4): epoch in registers (RegScratch), returns 8. 16 anchors
  * (config 5, 6-state): a register-resident epoch costs 96 more live registers and spills to scratch, which is no faster
@@ -107,12 +92,17 @@ bool toa6_two_waves(const kfpos_handle *h) {
     return h->two_waves && h->cfg.model == KFPOS_MODEL_TOA && !h->full && !h->force_generic && !h->coop &&
            h->cfg.max_anchors == 8 && h->cfg.ignore_worst == 0 && h->cfg.top_n == 0;
 }
+
+} // namespace
+
 int static_anchors(const kfpos_handle *h) {
     if (h->cfg.max_anchors == 8) return 8;
     /* 16 anchors (BASELINE config 5): compile-time loops over an LDS-resident epoch (StaticScratch), 6-state only */
     if (h->cfg.max_anchors == 16 && h->cfg.model == KFPOS_MODEL_TOA) return -16;
     return 0;
 }
+
+namespace {
 
 step_kernel_t step_kernel(const kfpos_handle *h, bool sensor_call = false, bool imu_only = false) {
     const int st = h->cfg.storage, as = (h->force_generic || sensor_call) ? 0 : static_anchors(h);
@@ -129,6 +119,8 @@ step_kernel_t step_kernel(const kfpos_handle *h, bool sensor_call = false, bool 
     }
     return kfpos_k::imu9_kernel(st, as, !imu_only);
 }
+
+} // namespace
 
 /* a.T tags: the whole bank, or the n tags of a work bank (row-list steps). WHICH kernel runs is a property of the handle,
  * never of a.T: a row-list step computes bit for bit what the whole-bank call does */
@@ -158,6 +150,8 @@ int launch_step(kfpos_handle *h, const KArgs &a, hipStream_t s) {
     h->stepped = true;
     return KFPOS_OK;
 }
+
+namespace {
 
 /* a region of the row-major staging area; regions live until the next stage_reset() (start of an API call) */
 int stage_region(kfpos_handle *h, size_t bytes, void **out) {
@@ -280,8 +274,6 @@ int drain_slots(kfpos_handle *h) {
         }
     return KFPOS_OK;
 }
-
-using DevScope = KfposDevScope; /* kfpos_internal.h */
 
 /* packed index of the stored covariance entry (i, j) */
 inline int pidx(const kfpos_handle *h, int i, int j) {
@@ -667,493 +659,6 @@ int kfpos_step_toa_imu_dev(kfpos_handle *h, const int32_t *range_mm, const void 
     a.mode = MODE_FUSED;
     a.latch = latch ? 1 : 0;
     return launch_step(h, a, (hipStream_t)stream);
-}
-
-int kfpos_run_trace_dev(kfpos_handle *h, int32_t n_steps, const int32_t *range_mm, int64_t stride_ranges,
-                        const void *err_est, int64_t stride_err, const void *accel, int64_t stride_accel,
-                        const void *cov, int64_t stride_cov, const double *dt_steps, double *trajectory,
-                        uint32_t *status, void *stream) {
-    g_err.clear();
-    if (!h || n_steps < 0 || !range_mm || !err_est || !dt_steps) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (accel && (!cov || h->cfg.model != KFPOS_MODEL_TOA_IMU)) return KFPOS_ERR_MODEL;
-    if (!h->have_anchors) return KFPOS_ERR_STATE;
-    KArgs a;
-    fill_args(h, a);
-    a.status = status;
-    a.mode = accel ? MODE_FUSED : MODE_TOA;
-    a.stride_ranges = stride_ranges;
-    a.stride_err = stride_err;
-    a.stride_accel = stride_accel;
-    a.stride_cov = stride_cov;
-    const size_t r = h->msz;
-    /* the kernels whiten the accelerometer covariance once per launch: a covariance per epoch means one epoch per launch */
-    const int chunk = (accel && stride_cov != 0) ? 1 : h->trace_chunk;
-    /* Up to `chunk` epochs per launch: the kernel keeps every tag's state in registers across them, so
-     * state traffic and launch boundaries are paid once per chunk instead of once per epoch. */
-    for (int s0 = 0; s0 < n_steps; s0 += chunk) {
-        const int n = n_steps - s0 < chunk ? n_steps - s0 : chunk;
-        a.n_steps = n;
-        a.ranges = range_mm + (size_t)s0 * stride_ranges;
-        a.err = (const char *)err_est + (size_t)s0 * stride_err * r;
-        if (accel) {
-            a.accel = (const char *)accel + (size_t)s0 * stride_accel * r;
-            a.cov = (const char *)cov + (size_t)s0 * stride_cov * r;
-            a.latch = (s0 + n == n_steps) ? 1 : 0; /* leave the last sample latched, as n separate calls would */
-        }
-        for (int k = 0; k < n; ++k) a.dt_steps[k] = dt_steps[s0 + k];
-        a.dt_shared = dt_steps[s0];
-        a.traj = trajectory ? trajectory + (size_t)s0 * 3 * h->cfg.n_tags : nullptr;
-        const int rc = launch_step(h, a, (hipStream_t)stream);
-        if (rc != KFPOS_OK) return rc;
-    }
-    return KFPOS_OK;
-}
-
-int kfpos_run_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds, const double *dt_events,
-                         const int32_t *range_mm, int64_t stride_ranges, const void *err_est, int64_t stride_err,
-                         const void *accel, int64_t stride_accel, const void *cov, double *trajectory,
-                         uint32_t *status_events, uint32_t *status, void *stream) {
-    g_err.clear();
-    if (!h || n_events < 0) return KFPOS_ERR_ARG;
-    if (n_events == 0) return KFPOS_OK;
-    if (!kinds || !dt_events) return KFPOS_ERR_ARG;
-    int n_toa = 0, n_imu = 0, lead = -1; /* lead: ranging events ahead of the call's first sample */
-    for (int e = 0; e < n_events; ++e) {
-        if (kinds[e] == KFPOS_EVENT_TOA) ++n_toa;
-        else if (kinds[e] == KFPOS_EVENT_IMU) {
-            if (lead < 0) lead = e;
-            ++n_imu;
-        } else {
-            g_err = "kfpos_run_events_dev: kinds[" + std::to_string(e) + "] = " + std::to_string((int)kinds[e]) + " is no event kind";
-            return KFPOS_ERR_ARG;
-        }
-    }
-    if (lead < 0) lead = n_events;
-    if ((n_toa && (!range_mm || !err_est)) || (n_imu && (!accel || !cov))) return KFPOS_ERR_ARG;
-    if (h->cfg.model != KFPOS_MODEL_TOA_IMU) return KFPOS_ERR_MODEL;
-    if (n_toa && !h->have_anchors) {
-        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
-        return KFPOS_ERR_STATE;
-    }
-    DevScope dev_(h->cfg.device);
-    const size_t T = h->cfg.n_tags, r = h->msz;
-    const hipStream_t s = (hipStream_t)stream;
-    /* Ranging events ahead of the first sample re-fuse what the handle held latched, with THAT sample's covariance:
-     * the multi-epoch ranging path of kfpos_run_trace_dev, which reads the latch. It reports the last status word of
-     * a launch only, so with status_events every one of these events is a launch of its own. */
-    if (lead > 0) {
-        KArgs a;
-        fill_args(h, a);
-        a.mode = MODE_TOA;
-        a.stride_ranges = stride_ranges;
-        a.stride_err = stride_err;
-        const int chunk = status_events ? 1 : h->trace_chunk;
-        for (int s0 = 0; s0 < lead; s0 += chunk) {
-            const int n = lead - s0 < chunk ? lead - s0 : chunk;
-            a.n_steps = n;
-            a.ranges = range_mm + (size_t)s0 * stride_ranges;
-            a.err = (const char *)err_est + (size_t)s0 * stride_err * r;
-            for (int k = 0; k < n; ++k) a.dt_steps[k] = dt_events[s0 + k];
-            a.dt_shared = dt_events[s0];
-            a.traj = trajectory ? trajectory + (size_t)s0 * 3 * T : nullptr;
-            a.status = status_events ? status_events + (size_t)s0 * T : (s0 + n == n_events ? status : nullptr);
-            const int rc = launch_step(h, a, s);
-            if (rc != KFPOS_OK) return rc;
-        }
-        if (lead == n_events && status_events && status)
-            HIPCHK(hipMemcpyAsync(status, status_events + (size_t)(n_events - 1) * T, sizeof(uint32_t) * T,
-                                  hipMemcpyDeviceToDevice, s));
-    }
-    if (lead == n_events) return KFPOS_OK;
-    /* From the first sample on: k_events_imu9, up to trace_chunk events per launch. Every launch leaves its last
-     * sample and `cov` latched, so the next one (and whoever calls next) finds them where single calls leave them. */
-    const int as = (!h->force_generic && static_anchors(h) == 8) ? 8 : 0;
-    const kfpos_k::events_kernel_t kern = kfpos_k::imu9_events_kernel(h->cfg.storage, as);
-    const size_t lds = park9_bytes() + (as == 0 ? lds_bytes(h) : 0);
-    if (lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kfpos_k::EvArgs ev;
-    fill_args(h, ev.k);
-    ev.k.stride_ranges = stride_ranges;
-    ev.k.stride_err = stride_err;
-    ev.k.stride_accel = stride_accel;
-    ev.k.cov = cov;
-    const int blocks = (int)((T + WAVE - 1) / WAVE);
-    size_t j = (size_t)lead, i = 0; /* ranging epochs / samples consumed so far */
-    for (int e0 = lead; e0 < n_events; e0 += h->trace_chunk) {
-        const int n = n_events - e0 < h->trace_chunk ? n_events - e0 : h->trace_chunk;
-        ev.k.n_steps = n;
-        ev.k.ranges = range_mm ? range_mm + j * stride_ranges : nullptr;
-        ev.k.err = err_est ? (const char *)err_est + j * stride_err * r : nullptr;
-        ev.k.accel = (const char *)accel + i * stride_accel * r;
-        ev.kinds[0] = ev.kinds[1] = 0;
-        for (int k = 0; k < n; ++k) {
-            ev.k.dt_steps[k] = dt_events[e0 + k];
-            if (kinds[e0 + k] == KFPOS_EVENT_TOA) {
-                ev.kinds[k >> 6] |= 1ull << (k & 63);
-                ++j;
-            } else {
-                ++i;
-            }
-        }
-        ev.k.dt_shared = dt_events[e0];
-        ev.k.traj = trajectory ? trajectory + (size_t)e0 * 3 * T : nullptr;
-        ev.status_events = status_events ? status_events + (size_t)e0 * T : nullptr;
-        ev.k.status = e0 + n == n_events ? status : nullptr;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), lds, s, ev);
-        HIPCHK(hipGetLastError());
-        h->stepped = true;
-    }
-    return KFPOS_OK;
-}
-
-int kfpos_run_events_each_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds, const double *dt_events_dev,
-                              const int32_t *range_mm, int64_t stride_ranges, const void *err_est, int64_t stride_err,
-                              const void *accel, int64_t stride_accel, const void *cov, double *trajectory,
-                              uint32_t *status_events, uint32_t *status, void *stream) {
-    g_err.clear();
-    if (!h || n_events < 0) return KFPOS_ERR_ARG;
-    if (n_events == 0) return KFPOS_OK;
-    if (!kinds || !dt_events_dev) return KFPOS_ERR_ARG;
-    int n_toa = 0, n_imu = 0;
-    for (int e = 0; e < n_events; ++e) {
-        if (kinds[e] == KFPOS_EVENT_TOA) ++n_toa;
-        else if (kinds[e] == KFPOS_EVENT_IMU) ++n_imu;
-        else {
-            g_err = "kfpos_run_events_each_dev: kinds[" + std::to_string(e) + "] = " + std::to_string((int)kinds[e]) + " is no event kind";
-            return KFPOS_ERR_ARG;
-        }
-    }
-    if ((n_toa && (!range_mm || !err_est)) || (n_imu && (!accel || !cov))) return KFPOS_ERR_ARG;
-    if (h->cfg.model != KFPOS_MODEL_TOA_IMU) return KFPOS_ERR_MODEL;
-    if (n_toa && !h->have_anchors) {
-        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
-        return KFPOS_ERR_STATE;
-    }
-    DevScope dev_(h->cfg.device);
-    const size_t T = h->cfg.n_tags, r = h->msz;
-    const hipStream_t s = (hipStream_t)stream;
-    /* No "lead" split as in kfpos_run_events_dev: which tags have ranging events ahead of their first sample is in
-     * dt_events_dev, which the host never reads. The kernel switches whiteners per lane instead -- the latched
-     * covariance's until the lane's own first sample, the call's from then on -- and every launch leaves the samples it
-     * took latched with `cov`, so the next launch (and whoever calls next) finds them where single calls leave them.
-     * LDS as k_events_imu9: CovPark9 alone (39.2 KB, four workgroups per CU), beside the generic epoch scratch of up
-     * to 64 anchors 96 + 39.2 = 135.2 KB of the CU's 160. */
-    const int as = (!h->force_generic && static_anchors(h) == 8) ? 8 : 0;
-    const kfpos_k::events_each_kernel_t kern = kfpos_k::imu9_events_each_kernel(h->cfg.storage, as);
-    const size_t lds = park9_bytes() + (as == 0 ? lds_bytes(h) : 0);
-    if (lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kfpos_k::EvEachArgs ev;
-    fill_args(h, ev.k);
-    ev.k.stride_ranges = stride_ranges;
-    ev.k.stride_err = stride_err;
-    ev.k.stride_accel = stride_accel;
-    for (double &d : ev.k.dt_steps) d = 0.0; /* unused by this kernel */
-    const int blocks = (int)((T + WAVE - 1) / WAVE);
-    size_t j = 0, i = 0; /* ranging / IMU slots consumed so far */
-    for (int e0 = 0; e0 < n_events; e0 += h->trace_chunk) {
-        const int n = n_events - e0 < h->trace_chunk ? n_events - e0 : h->trace_chunk;
-        ev.k.n_steps = n;
-        ev.k.ranges = range_mm ? range_mm + j * stride_ranges : nullptr;
-        ev.k.err = err_est ? (const char *)err_est + j * stride_err * r : nullptr;
-        ev.k.accel = accel ? (const char *)accel + i * stride_accel * r : nullptr;
-        ev.kinds[0] = ev.kinds[1] = 0;
-        bool imu_slot = false;
-        for (int k = 0; k < n; ++k) {
-            if (kinds[e0 + k] == KFPOS_EVENT_TOA) {
-                ev.kinds[k >> 6] |= 1ull << (k & 63);
-                ++j;
-            } else {
-                imu_slot = true;
-                ++i;
-            }
-        }
-        ev.k.cov = imu_slot ? cov : nullptr; /* the kernel whitens it only where a lane can come to use it */
-        ev.dt_each = dt_events_dev + (size_t)e0 * T;
-        ev.k.traj = trajectory ? trajectory + (size_t)e0 * 3 * T : nullptr;
-        ev.status_events = status_events ? status_events + (size_t)e0 * T : nullptr;
-        ev.k.status = e0 + n == n_events ? status : nullptr;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), lds, s, ev);
-        HIPCHK(hipGetLastError());
-        h->stepped = true;
-    }
-    return KFPOS_OK;
-}
-
-int kfpos_run_trace_each_dev(kfpos_handle *h, int32_t n_steps, const double *dt_steps_dev, const int32_t *range_mm,
-                             int64_t stride_ranges, const void *err_est, int64_t stride_err, double *trajectory,
-                             uint32_t *status_steps, uint32_t *status, void *stream) {
-    g_err.clear();
-    if (!h || n_steps < 0) return KFPOS_ERR_ARG;
-    if (n_steps == 0) return KFPOS_OK;
-    if (!dt_steps_dev || !range_mm || !err_est) return KFPOS_ERR_ARG;
-    if (h->cfg.model != KFPOS_MODEL_TOA) return KFPOS_ERR_MODEL;
-    if (!h->have_anchors) {
-        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
-        return KFPOS_ERR_STATE;
-    }
-    DevScope dev_(h->cfg.device);
-    const size_t T = h->cfg.n_tags, r = h->msz;
-    const hipStream_t s = (hipStream_t)stream;
-    /* The 8-lanes-per-tag kernel sums in another order and has a contraction mode of its own (kfpos_k_coop.hip): a
-     * one-tag-per-lane replay would not match what this handle's single calls compute. Such a handle runs its slots
-     * as those single calls, one launch each: the same bits, not fused. */
-    if (h->coop) {
-        KArgs a;
-        fill_args(h, a);
-        a.mode = MODE_TOA;
-        for (int e = 0; e < n_steps; ++e) {
-            a.ranges = range_mm + (size_t)e * stride_ranges;
-            a.err = (const char *)err_est + (size_t)e * stride_err * r;
-            a.dt = dt_steps_dev + (size_t)e * T;
-            a.traj = trajectory ? trajectory + (size_t)e * 3 * T : nullptr;
-            a.status = status_steps ? status_steps + (size_t)e * T : (e + 1 == n_steps ? status : nullptr);
-            const int rc = launch_step(h, a, s);
-            if (rc != KFPOS_OK) return rc;
-        }
-        if (status_steps && status)
-            HIPCHK(hipMemcpyAsync(status, status_steps + (size_t)(n_steps - 1) * T, sizeof(uint32_t) * T,
-                                  hipMemcpyDeviceToDevice, s));
-        return KFPOS_OK;
-    }
-    /* k_trace_toa6_each, up to trace_chunk slots per launch; a bank with more wavefronts than SIMDs runs it too (the
-     * two-wavefront build of the single calls computes the same bits). The kernel and its LDS follow the handle as
-     * step_kernel() / launch_step() do: the epoch of the LDS forms (4-byte errorEstimations kept as they are where the
-     * anchor count is a compile-time one), and Pinv6 of the non-symmetric layout behind it. */
-    const int as = h->force_generic ? 0 : static_anchors(h);
-    const int heur = h->cfg.ignore_worst != 0 ? 2 : (h->cfg.top_n != 0 ? 1 : 0);
-    const kfpos_k::trace_each_kernel_t kern = h->full ? kfpos_k::toa6_each_full_kernel(h->cfg.storage, as, heur)
-                                                      : kfpos_k::toa6_each_sym_kernel(h->cfg.storage, as, heur);
-    size_t lds = (as == 8 && !h->full) ? 0 : lds_bytes(h);
-    if (lds && as != 0 && h->msz == 4) lds = lds * 5 / 6;
-    if (h->full) lds += park_bytes();
-    if (lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kfpos_k::TraceEachArgs ev;
-    fill_args(h, ev.k);
-    ev.k.mode = MODE_TOA;
-    ev.k.stride_ranges = stride_ranges;
-    ev.k.stride_err = stride_err;
-    for (double &d : ev.k.dt_steps) d = 0.0; /* unused by this kernel */
-    const int blocks = (int)((T + WAVE - 1) / WAVE);
-    for (int e0 = 0; e0 < n_steps; e0 += h->trace_chunk) {
-        const int n = n_steps - e0 < h->trace_chunk ? n_steps - e0 : h->trace_chunk;
-        ev.k.n_steps = n;
-        ev.k.ranges = range_mm + (size_t)e0 * stride_ranges;
-        ev.k.err = (const char *)err_est + (size_t)e0 * stride_err * r;
-        ev.dt_each = dt_steps_dev + (size_t)e0 * T;
-        ev.k.traj = trajectory ? trajectory + (size_t)e0 * 3 * T : nullptr;
-        ev.status_steps = status_steps ? status_steps + (size_t)e0 * T : nullptr;
-        ev.k.status = e0 + n == n_steps ? status : nullptr;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), lds, s, ev);
-        HIPCHK(hipGetLastError());
-        h->stepped = true;
-    }
-    return KFPOS_OK;
-}
-
-int kfpos_run_planar_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds, const double *dt_events,
-                                const kfpos_planar_inputs *in, double *trajectory, uint32_t *status_events,
-                                uint32_t *status, void *stream) {
-    g_err.clear();
-    if (!h || n_events < 0) return KFPOS_ERR_ARG;
-    if (n_events == 0) return KFPOS_OK;
-    if (!kinds || !dt_events || !in) return KFPOS_ERR_ARG;
-    static const char *const names[5] = {"range_mm / err_est", "px4flow", "imu", "mag", "compass"};
-    const bool have[5] = {in->range_mm && in->err_est, in->px4flow != nullptr, in->imu != nullptr, in->mag != nullptr,
-                          in->compass != nullptr};
-    int n_toa = 0, lead = -1; /* lead: ranging events ahead of the call's first sensor event */
-    for (int e = 0; e < n_events; ++e) {
-        const int kind = kinds[e];
-        if (kind > KFPOS_SENSOR_COMPASS) {
-            g_err = "kfpos_run_planar_events_dev: kinds[" + std::to_string(e) + "] = " + std::to_string(kind) + " is no event kind";
-            return KFPOS_ERR_ARG;
-        }
-        if (!have[kind]) {
-            g_err = "kfpos_run_planar_events_dev: kinds[" + std::to_string(e) + "] = " + std::to_string(kind) +
-                    " but kfpos_planar_inputs." + names[kind] + " is NULL";
-            return KFPOS_ERR_ARG;
-        }
-        if (kind == KFPOS_PLANAR_EVENT_TOA) ++n_toa;
-        else if (lead < 0) lead = e;
-    }
-    if (lead < 0) lead = n_events;
-    if (h->cfg.model != KFPOS_MODEL_PLANAR) return KFPOS_ERR_MODEL;
-    if (n_toa && !h->have_anchors) {
-        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
-        return KFPOS_ERR_STATE;
-    }
-    DevScope dev_(h->cfg.device);
-    const size_t T = h->cfg.n_tags, r = h->msz;
-    const hipStream_t s = (hipStream_t)stream;
-    /* Ranging events ahead of the first sensor event: the multi-epoch ranging path of kfpos_run_trace_dev -- on a handle
-     * that never had a sensor sample that is the closed-form ranging-only kernel, which single calls would run as well.
-     * It reports the last status word of a launch only, so with status_events every one of these events is a launch of
-     * its own (kfpos_run_events_dev does the same). */
-    if (lead > 0) {
-        KArgs a;
-        fill_args(h, a);
-        a.mode = MODE_TOA;
-        a.stride_ranges = in->stride_ranges;
-        a.stride_err = in->stride_err;
-        const int chunk = status_events ? 1 : h->trace_chunk;
-        for (int s0 = 0; s0 < lead; s0 += chunk) {
-            const int n = lead - s0 < chunk ? lead - s0 : chunk;
-            a.n_steps = n;
-            a.ranges = in->range_mm + (size_t)s0 * in->stride_ranges;
-            a.err = (const char *)in->err_est + (size_t)s0 * in->stride_err * r;
-            for (int k = 0; k < n; ++k) a.dt_steps[k] = dt_events[s0 + k];
-            a.dt_shared = dt_events[s0];
-            a.traj = trajectory ? trajectory + (size_t)s0 * 3 * T : nullptr;
-            a.status = status_events ? status_events + (size_t)s0 * T : (s0 + n == n_events ? status : nullptr);
-            const int rc = launch_step(h, a, s);
-            if (rc != KFPOS_OK) return rc;
-        }
-        if (lead == n_events && status_events && status)
-            HIPCHK(hipMemcpyAsync(status, status_events + (size_t)(n_events - 1) * T, sizeof(uint32_t) * T,
-                                  hipMemcpyDeviceToDevice, s));
-    }
-    if (lead == n_events) return KFPOS_OK;
-    /* From the first sensor event on: k_events_planar, up to trace_chunk events per launch. Every launch leaves the
-     * samples it latched in HBM, so the next one (and whoever calls next) finds them where single calls leave them. */
-    const int as = (!h->force_generic && static_anchors(h) == 8) ? -8 : 0;
-    const kfpos_k::planar_events_kernel_t kern = kfpos_k::planar_events_kernel(h->cfg.storage, as);
-    const size_t lds = park_bytes() + (as == 0 ? lds_bytes(h) : (size_t)3 * 8 * WAVE * sizeof(double));
-    if (lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kfpos_k::PevArgs ev;
-    fill_args(h, ev.k);
-    ev.k.stride_ranges = in->stride_ranges;
-    ev.k.stride_err = in->stride_err;
-    const double *const base[4] = {in->px4flow, in->imu, in->mag, in->compass};
-    const int64_t stride[4] = {in->stride_px4flow, in->stride_imu, in->stride_mag, in->stride_compass};
-    for (int c = 0; c < 4; ++c) ev.stride_sens[c] = stride[c];
-    const int blocks = (int)((T + WAVE - 1) / WAVE);
-    size_t ord[5] = {(size_t)lead, 0, 0, 0, 0}; /* events of each kind consumed so far: they carry across launches */
-    for (int e0 = lead; e0 < n_events; e0 += h->trace_chunk) {
-        const int n = n_events - e0 < h->trace_chunk ? n_events - e0 : h->trace_chunk;
-        ev.k.n_steps = n;
-        ev.k.ranges = in->range_mm ? in->range_mm + ord[0] * in->stride_ranges : nullptr;
-        ev.k.err = in->err_est ? (const char *)in->err_est + ord[0] * in->stride_err * r : nullptr;
-        for (int c = 0; c < 4; ++c) ev.sens[c] = base[c] ? base[c] + ord[c + 1] * stride[c] : nullptr;
-        std::memset(ev.kinds, 0, sizeof(ev.kinds));
-        for (int k = 0; k < n; ++k) {
-            ev.k.dt_steps[k] = dt_events[e0 + k];
-            ev.kinds[k >> 3] |= (uint32_t)kinds[e0 + k] << ((k & 7) * 4);
-            ++ord[kinds[e0 + k]];
-        }
-        ev.k.dt_shared = dt_events[e0];
-        ev.k.traj = trajectory ? trajectory + (size_t)e0 * 3 * T : nullptr;
-        ev.status_events = status_events ? status_events + (size_t)e0 * T : nullptr;
-        ev.k.status = e0 + n == n_events ? status : nullptr;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), lds, s, ev);
-        HIPCHK(hipGetLastError());
-        h->stepped = true;
-        h->planar_sensors = true; /* ranging epochs now carry the latched samples (kfpos_step_sensor_dev) */
-    }
-    return KFPOS_OK;
-}
-
-int kfpos_run_planar_events_each_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds,
-                                     const double *dt_events_dev, const kfpos_planar_inputs *in, double *trajectory,
-                                     uint32_t *status_events, uint32_t *status, void *stream) {
-    g_err.clear();
-    if (!h || n_events < 0) return KFPOS_ERR_ARG;
-    if (n_events == 0) return KFPOS_OK;
-    if (!kinds || !dt_events_dev || !in) return KFPOS_ERR_ARG;
-    static const char *const names[5] = {"range_mm / err_est", "px4flow", "imu", "mag", "compass"};
-    const bool have[5] = {in->range_mm && in->err_est, in->px4flow != nullptr, in->imu != nullptr, in->mag != nullptr,
-                          in->compass != nullptr};
-    int n_toa = 0, first_sensor = -1;
-    for (int e = 0; e < n_events; ++e) {
-        const int kind = kinds[e];
-        if (kind > KFPOS_SENSOR_COMPASS) {
-            g_err = "kfpos_run_planar_events_each_dev: kinds[" + std::to_string(e) + "] = " + std::to_string(kind) + " is no event kind";
-            return KFPOS_ERR_ARG;
-        }
-        if (!have[kind]) {
-            g_err = "kfpos_run_planar_events_each_dev: kinds[" + std::to_string(e) + "] = " + std::to_string(kind) +
-                    " but kfpos_planar_inputs." + names[kind] + " is NULL";
-            return KFPOS_ERR_ARG;
-        }
-        if (kind == KFPOS_PLANAR_EVENT_TOA) ++n_toa;
-        else if (first_sensor < 0) first_sensor = e;
-    }
-    if (first_sensor < 0) first_sensor = n_events;
-    if (h->cfg.model != KFPOS_MODEL_PLANAR) return KFPOS_ERR_MODEL;
-    if (n_toa && !h->have_anchors) {
-        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
-        return KFPOS_ERR_STATE;
-    }
-    DevScope dev_(h->cfg.device);
-    const size_t T = h->cfg.n_tags, r = h->msz;
-    const hipStream_t s = (hipStream_t)stream;
-    /* WHICH ranging kernel runs is a property of the handle: on one that never had a sensor sample a single
-     * kfpos_step_toa_dev runs the closed-form ranging-only kernel for every tag, so the ranging slots ahead of the call's
-     * first sensor slot go down launch_step there -- one slot per launch, KArgs carries a per-tag dt with n_steps == 1
-     * only. On a handle that has planar_sensors set the single call is k_step_planar<true>, whose text
-     * k_events_planar_each runs: there the new kernel takes the call from its first slot (lead = 0), one launch
-     * instead of one per leading slot. */
-    const int lead = h->planar_sensors ? 0 : first_sensor;
-    for (int e = 0; e < lead; ++e) {
-        KArgs a;
-        fill_args(h, a);
-        a.mode = MODE_TOA;
-        a.ranges = in->range_mm + (size_t)e * in->stride_ranges;
-        a.err = (const char *)in->err_est + (size_t)e * in->stride_err * r;
-        a.dt = dt_events_dev + (size_t)e * T;
-        a.traj = trajectory ? trajectory + (size_t)e * 3 * T : nullptr;
-        a.status = status_events ? status_events + (size_t)e * T : (e + 1 == n_events ? status : nullptr);
-        const int rc = launch_step(h, a, s);
-        if (rc != KFPOS_OK) return rc;
-    }
-    if (lead == n_events) {
-        if (lead > 0 && status_events && status)
-            HIPCHK(hipMemcpyAsync(status, status_events + (size_t)(n_events - 1) * T, sizeof(uint32_t) * T,
-                                  hipMemcpyDeviceToDevice, s));
-        return KFPOS_OK;
-    }
-    /* From there on: k_events_planar_each, up to trace_chunk slots per launch. Every launch leaves the samples its lanes
-     * latched in HBM, so the next one (and whoever calls next) finds them where single calls leave them. LDS as
-     * k_events_planar: the epoch scratch and CovSpill8 behind it. */
-    const int as = (!h->force_generic && static_anchors(h) == 8) ? -8 : 0;
-    const kfpos_k::planar_events_each_kernel_t kern = kfpos_k::planar_events_each_kernel(h->cfg.storage, as);
-    const size_t lds = park_bytes() + (as == 0 ? lds_bytes(h) : (size_t)3 * 8 * WAVE * sizeof(double));
-    if (lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kfpos_k::PevEachArgs ev;
-    fill_args(h, ev.k);
-    ev.k.stride_ranges = in->stride_ranges;
-    ev.k.stride_err = in->stride_err;
-    for (double &d : ev.k.dt_steps) d = 0.0; /* unused by this kernel */
-    const double *const base[4] = {in->px4flow, in->imu, in->mag, in->compass};
-    const int64_t stride[4] = {in->stride_px4flow, in->stride_imu, in->stride_mag, in->stride_compass};
-    for (int c = 0; c < 4; ++c) ev.stride_sens[c] = stride[c];
-    const int blocks = (int)((T + WAVE - 1) / WAVE);
-    size_t ord[5] = {(size_t)lead, 0, 0, 0, 0}; /* slots of each kind consumed so far: they carry across launches */
-    for (int e0 = lead; e0 < n_events; e0 += h->trace_chunk) {
-        const int n = n_events - e0 < h->trace_chunk ? n_events - e0 : h->trace_chunk;
-        ev.k.n_steps = n;
-        ev.k.ranges = in->range_mm ? in->range_mm + ord[0] * in->stride_ranges : nullptr;
-        ev.k.err = in->err_est ? (const char *)in->err_est + ord[0] * in->stride_err * r : nullptr;
-        for (int c = 0; c < 4; ++c) ev.sens[c] = base[c] ? base[c] + ord[c + 1] * stride[c] : nullptr;
-        std::memset(ev.kinds, 0, sizeof(ev.kinds));
-        for (int k = 0; k < n; ++k) {
-            ev.kinds[k >> 3] |= (uint32_t)kinds[e0 + k] << ((k & 7) * 4);
-            ++ord[kinds[e0 + k]];
-        }
-        ev.dt_each = dt_events_dev + (size_t)e0 * T;
-        ev.k.traj = trajectory ? trajectory + (size_t)e0 * 3 * T : nullptr;
-        ev.status_events = status_events ? status_events + (size_t)e0 * T : nullptr;
-        ev.k.status = e0 + n == n_events ? status : nullptr;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), lds, s, ev);
-        HIPCHK(hipGetLastError());
-        h->stepped = true;
-        h->planar_sensors = true; /* ranging epochs now carry the latched samples (kfpos_step_sensor_dev) */
-    }
-    return KFPOS_OK;
 }
 
 /* the bank as the pose kernels read it; outputs and extrapolation times: null / 0 until the caller sets them */

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9_each(const kfpos_k::EvEach
     const int n = a.n_steps;
     /* the kind is wave-uniform and kept as an integer the optimiser cannot see through: carried round the loop as a
      * boolean it becomes a lane mask, and the ordinals selected by it vector registers (k_events_imu9) */
-    auto is_toa = [&](int e) -> int { return opaque_uniform((int)((ev.kinds[(e >> 6) & 1] >> (e & 63)) & 1ull)); };
+    auto is_toa = [&](int e) -> int { return opaque_uniform(kfpos_kinds1_at(ev.kinds, e)); };
     auto load_dt = [&](int e) -> double { return (ev.dt_each + (size_t)e * T)[(uint32_t)opaque_lane(t)]; };
 
     /* load order = order of first use, as in k_step_imu9 */

@@ -27,7 +27,7 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9(const kfpos_k::EvArgs ev) 
     const int n = a.n_steps;
     /* wave-uniform, and kept as an integer the optimiser cannot see through: carried round the loop as a boolean it
      * becomes a lane mask, and the ordinals selected by it vector registers */
-    auto is_toa = [&](int e) -> int { return opaque_uniform((int)((ev.kinds[(e >> 6) & 1] >> (e & 63)) & 1ull)); };
+    auto is_toa = [&](int e) -> int { return opaque_uniform(kfpos_kinds1_at(ev.kinds, e)); };
 
     /* load order = order of first use, as in k_step_imu9 */
     uint32_t fl = a.flags[t32];

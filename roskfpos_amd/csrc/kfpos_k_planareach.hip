@@ -36,7 +36,7 @@ __global__ __launch_bounds__(WAVE) void k_events_planar_each(const kfpos_k::PevE
     const int n = a.n_steps;
     /* wave-uniform, and kept as an integer the optimiser cannot see through (k_events_planar): the branches on it are
      * scalar branches, the ordinals selected by it scalar registers */
-    auto kind_of = [&](int e) -> int { return opaque_uniform((int)((ev.kinds[e >> 3] >> ((e & 7) * 4)) & 7u)); };
+    auto kind_of = [&](int e) -> int { return opaque_uniform(kfpos_kinds4_at(ev.kinds, e)); };
     auto load_dt = [&](int e) -> double { return (ev.dt_each + (size_t)e * T)[(uint32_t)opaque_lane(t)]; };
 
     constexpr bool DT_AHEAD = KFPOS_PLANAREACH_DT_AHEAD != 0;

@@ -27,7 +27,7 @@ __global__ __launch_bounds__(WAVE) void k_events_planar(const kfpos_k::PevArgs e
     const int n = a.n_steps;
     /* wave-uniform, and kept as an integer the optimiser cannot see through (k_events_imu9): the branches on it are
      * scalar branches, the ordinals selected by it scalar registers */
-    auto kind_of = [&](int e) -> int { return opaque_uniform((int)((ev.kinds[e >> 3] >> ((e & 7) * 4)) & 7u)); };
+    auto kind_of = [&](int e) -> int { return opaque_uniform(kfpos_kinds4_at(ev.kinds, e)); };
 
     Tag8 tg;
     tg.xy[0] = (a.pos + 0 * T)[t32];

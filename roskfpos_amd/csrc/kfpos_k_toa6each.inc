@@ -77,7 +77,7 @@ __global__ __launch_bounds__(WAVE) void k_trace_toa6_each(const kfpos_k::TraceEa
 #pragma unroll
             for (int k = 0; k < 3; ++k) (a.traj + ((size_t)opaque_uniform(e) * 3 + k) * T)[tl] = tg.pos[k];
         }
-        if (ev.status_steps || last_status) { /* the status word a single call would have returned for this slot */
+        if (ev.status_events || last_status) { /* the status word a single call would have returned for this slot */
             if (any) {
                 bool fin = true;
 #pragma unroll
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(WAVE) void k_trace_toa6_each(const kfpos_k::TraceEa
                 const bool waiting = !a.use_init_pos && isnan(tg.pos[0]); /* still waiting for its ML initialisation */
                 if (run && !fin && !waiting) s |= ST_NONFINITE;
             }
-            if (ev.status_steps) (ev.status_steps + (size_t)opaque_uniform(e) * T)[tl] = s;
+            if (ev.status_events) (ev.status_events + (size_t)opaque_uniform(e) * T)[tl] = s;
             if (last_status) a.status[tl] = s;
         }
         if constexpr (cov_is_rounded<REAL>()) { /* what the single launch of this slot would have kept in HBM */

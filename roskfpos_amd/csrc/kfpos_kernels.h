@@ -1,7 +1,8 @@
 /*
  * kfpos_kernels.h -- what the kernel translation units of libkfpos_hip.so share: the kernel-argument blocks, the
  * device-side helpers that stage an epoch (component-major HBM -> registers / LDS), and the selector functions through
- * which the host side (kfpos_hip.hip) obtains a kernel without seeing its template.
+ * which the host side (kfpos_hip.hip, kfpos_hip_replay.hip) obtains a kernel without seeing its template, and what those
+ * two host units share among themselves (at the end of namespace kfpos_k's declarations).
  *
  * Execution model: ONE FILTER PER LANE, 64 filters per wavefront, one wavefront per workgroup.
  *  - The whole per-tag state (position, velocity, packed covariance: 21 / 36 / 45 doubles) lives in
@@ -25,7 +26,7 @@
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
  * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
- * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_comm (RCCL gather).
+ * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
 #define KFPOS_KERNELS_H
@@ -40,6 +41,7 @@
 #include "kfpos_core.h"
 #include "kfpos_internal.h"
 #include "kfpos_p48.h"
+#include "kfpos_replay_plan.h"
 
 namespace kfpos_k {
 
@@ -119,6 +121,7 @@ struct EvArgs {
     uint32_t *status_events; /* [n_steps][T] or null */
 };
 static_assert(KFPOS_TRACE_CHUNK == 128, "EvArgs::kinds is indexed as two 64-bit words");
+static_assert(KFPOS_TRACE_CHUNK == KFPOS_PLAN_MAX_EVENTS, "kfpos_replay_plan.h packs and decodes `kinds` for this many events");
 static_assert(sizeof(EvArgs) <= 4096, "kernel arguments are limited to 4 KB");
 typedef void (*events_kernel_t)(const EvArgs);
 
@@ -139,11 +142,11 @@ typedef void (*events_each_kernel_t)(const EvEachArgs);
 /* kfpos_run_trace_each_dev (kfpos_k_toa6eachs.hip / kfpos_k_toa6eachf.hip): ranging slots of the 6-state filter with a
  * timeline per tag, a block of its own around an unchanged KArgs as well. Every slot is a ranging epoch, so there are no
  * kinds: slot e of the launch reads k.ranges / k.err + e * stride, dt_each[e * T + t] is tag t's timeLag in it, < 0 =
- * the tag sits the slot out (k.dt_steps is unused). k.traj / status_steps start at the launch's first slot; k.status:
+ * the tag sits the slot out (k.dt_steps is unused). k.traj / status_events start at the launch's first slot; k.status:
  * the last slot's words, or null. */
 struct TraceEachArgs {
     KArgs k;
-    uint32_t *status_steps;  /* [n_steps][T] or null */
+    uint32_t *status_events; /* [n_steps][T] or null */
     const double *dt_each;   /* DEVICE, [n_steps][T], at the launch's first slot */
 };
 static_assert(sizeof(TraceEachArgs) <= 4096, "kernel arguments are limited to 4 KB");
@@ -239,6 +242,26 @@ constexpr int PLANAR_HAS_SHIFT = 4;              /* planar flags word: bits 5..7
 constexpr int LATCH_ROWS = 15;
 
 } // namespace kfpos_k
+
+/* ---- what the two host units share: defined in kfpos_hip.hip, used by kfpos_hip_replay.hip as well ---- */
+#define KFPOS_HIDDEN __attribute__((visibility("hidden")))
+KFPOS_HIDDEN void fill_args(const kfpos_handle *h, kfpos_k::KArgs &a);           /* the handle's part of every argument block */
+KFPOS_HIDDEN int launch_step(kfpos_handle *h, const kfpos_k::KArgs &a, hipStream_t s); /* the step kernel of the handle, a.T tags */
+KFPOS_HIDDEN int static_anchors(const kfpos_handle *h);                          /* anchor-count specialisation: 8, -16 or 0 */
+KFPOS_HIDDEN size_t lds_bytes(const kfpos_handle *h);                            /* an LDS-resident epoch of max_anchors */
+KFPOS_HIDDEN size_t park_bytes();
+KFPOS_HIDDEN size_t park9_bytes();
+
+#define g_err (kfpos_error_text())
+#define HIPCHK(expr)                                                                              \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) {                                                                   \
+            g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                            \
+            return KFPOS_ERR_HIP;                                                                 \
+        }                                                                                         \
+    } while (0)
+using DevScope = KfposDevScope; /* kfpos_internal.h */
 
 namespace {
 

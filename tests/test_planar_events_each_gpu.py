@@ -192,6 +192,32 @@ def test_one_call_equals_the_single_calls_for_a_single_tag(storage, A):
     _bit_identity(A, storage, [("fixed", True, False), ("ml2d", False, True)], tags=[1])   # tag 1 skips slots
 
 
+def test_a_schedule_that_crosses_the_launch_boundary():
+    """the schedule four times over, 160 slots: behind the leading ranging slot of a fresh handle a launch of 128 slots
+    -- all 16 words of its `kinds` in use, slots of every kind at 64 or later in it -- and a second one for the rest"""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    from roskfpos_amd import capi
+    reps = 4
+    inp = Inputs(8, capi.STORE_F64, "fixed")
+    inp.kinds, inp.ran = np.tile(inp.kinds, reps), np.tile(inp.ran, (reps, 1))
+    inp.d_r, inp.d_dt = inp.d_r.repeat(reps, 1, 1), inp.d_dt.repeat(reps, 1)
+    inp.d_s = {kind: s.repeat(reps, 1, 1) for kind, s in inp.d_s.items()}
+    lead = pe.launch_starts(inp.kinds, 128)[0]
+    assert inp.kinds.size >= 130 and lead == 1 and len(pe.launch_starts(inp.kinds, 128)) == 2
+    assert set(inp.kinds[lead + 64:lead + 128].tolist()) == {0, 1, 2, 3, 4}
+    b = inp.bank()
+    ref = _single_calls(b, inp)
+    b.close()
+    assert np.array_equal(ref[1] == ST_SKIPPED, ~inp.ran)
+    low = ref[1][inp.ran] & 0xFF
+    assert (low == 0).mean() > 0.5 and (low != 0).any() and np.isfinite(ref[0][-1]).all()
+    b = inp.bank()
+    got = _one_call(b, inp)
+    b.close()
+    _same_bytes(got, ref, "four times the schedule")
+
+
 @pytest.mark.parametrize("start,waiting,storage,A", [("fixed", False, 2, 5), ("fixed_free", False, 3, 8),
                                                      ("ml3d", True, 1, 8), ("ml2d", True, 0, 5),
                                                      ("ml3d", False, 3, 5), ("ml2d", False, 2, 8)])

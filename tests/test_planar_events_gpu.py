@@ -189,6 +189,31 @@ def test_one_call_equals_the_single_calls_for_a_single_tag(storage, A):
     _bit_identity(1, A, storage, [("fixed", True, False), ("ml2d", False, True)])
 
 
+def test_a_schedule_that_crosses_the_launch_boundary():
+    """the schedule four times over, 160 events: behind the leading ranging event a launch of 128 events -- all 16 words
+    of its `kinds` in use, events of every kind at 64 or later in it -- and a second one for the rest"""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    from roskfpos_amd import capi
+    reps = 4
+    inp = Inputs(130, 8, capi.STORE_F64, "fixed")
+    kinds, dts = np.tile(inp.kinds, reps), np.tile(inp.dts, reps)
+    inp.d_r = inp.d_r.repeat(reps, 1, 1)
+    inp.d_s = {kind: s.repeat(reps, 1, 1) for kind, s in inp.d_s.items()}
+    lead = pe.launch_starts(kinds, 128)[0]
+    assert kinds.size >= 130 and lead == 1 and len(pe.launch_starts(kinds, 128)) == 2
+    assert set(kinds[lead + 64:lead + 128].tolist()) == {0, 1, 2, 3, 4}
+    b = inp.bank()
+    ref = _single_calls(b, inp, kinds, dts)
+    b.close()
+    low = ref[1] & 0xFF
+    assert (low == 0).mean() > 0.5 and (low != 0).any() and np.isfinite(ref[0][-1]).all()
+    b = inp.bank()
+    got = _one_call(b, inp, kinds, dts)
+    b.close()
+    _same_bytes(got, ref, "four times the schedule")
+
+
 @pytest.mark.parametrize("storage,A", [(0, 8), (2, 5), (3, 8)])
 def test_a_handle_that_already_holds_latched_samples(storage, A):
     """earlier single calls left all three latches behind: the leading ranging event carries them, and kinds the call

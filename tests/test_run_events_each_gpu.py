@@ -242,6 +242,30 @@ def test_one_call_equals_the_single_calls_for_a_single_tag(storage, A):
     _bit_identity(A, storage, [(True, False), (False, True)], tags=[1])   # tag 1 skips slots (asserted above)
 
 
+def test_a_schedule_that_crosses_the_launch_boundary():
+    """the schedule four times over, 156 slots: a launch of 128 slots -- both words of its `kinds` in use, slots of
+    either kind at 64 or later in it -- and a second one for the rest"""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    from roskfpos_amd import capi
+    reps = 4
+    inp = Inputs(8, capi.STORE_MIXED, True, False)                  # the register-resident kernel
+    inp.kinds, inp.mask = np.tile(inp.kinds, reps), np.tile(inp.mask, (reps, 1))
+    inp.d_r, inp.d_a, inp.d_dt = inp.d_r.repeat(reps, 1, 1), inp.d_a.repeat(reps, 1, 1), inp.d_dt.repeat(reps, 1)
+    assert inp.kinds.size >= 130 and inp.kinds.size > 128
+    assert set(inp.kinds[64:128].tolist()) == {IMU, TOA}
+    b = inp.bank()
+    ref = _single_calls(b, inp)
+    b.close()
+    assert ((ref[1] == ST_SKIPPED) == ~inp.mask).all()
+    low = ref[1][inp.mask] & 0xFF
+    assert (low == 0).mean() > 0.5 and (low != 0).any() and np.isfinite(ref[0][-1]).all()
+    b = inp.bank()
+    got = _one_call(b, inp)
+    b.close()
+    _same_bytes(got, ref, "four times the schedule")
+
+
 @pytest.mark.parametrize("storage,A", [(0, 8), (1, 5), (2, 8), (3, 5), (2, 5)])
 def test_slots_ahead_of_a_tags_first_sample_fuse_its_earlier_latch_with_its_own_covariance(storage, A):
     """On a bank that has run the schedule once (from a fixed start with P = 0 the sample's covariance leaves no trace in

@@ -193,6 +193,30 @@ def test_one_call_equals_the_single_calls_for_a_single_tag(storage, A):
     _bit_identity(1, A, storage, [(True, False, True), (False, True, False)])
 
 
+def test_a_schedule_that_crosses_the_launch_boundary():
+    """the schedule four times over, 156 events: behind the leading ranging event a launch of 128 events -- both words
+    of its `kinds` in use, events of either kind at 64 or later in it -- and a second one for the rest"""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    from roskfpos_amd import capi
+    reps = 4
+    inp = Inputs(130, 8, capi.STORE_MIXED, True, False, True)       # the register-resident kernel
+    kinds, dts = np.tile(inp.kinds, reps), np.tile(inp.dts, reps)
+    inp.d_r, inp.d_a = inp.d_r.repeat(reps, 1, 1), inp.d_a.repeat(reps, 1, 1)
+    lead = int(np.flatnonzero(kinds == IMU)[0])
+    assert kinds.size >= 130 and lead == 1 and kinds.size - lead > 128
+    assert set(kinds[lead + 64:lead + 128].tolist()) == {IMU, TOA}
+    b = inp.bank()
+    ref = _single_calls(b, inp, kinds, dts)
+    b.close()
+    low = ref[1] & 0xFF
+    assert (low == 0).mean() > 0.5 and (low != 0).any() and np.isfinite(ref[0][-1]).all()
+    b = inp.bank()
+    got = _one_call(b, inp, kinds, dts)
+    b.close()
+    _same_bytes(got, ref, "four times the schedule")
+
+
 @pytest.mark.parametrize("storage,A", [(0, 8), (1, 5), (2, 8), (3, 5), (2, 5)])
 def test_leading_ranging_events_fuse_the_previously_latched_sample_with_its_covariance(storage, A):
     if not has_gpu():
