@@ -1,7 +1,7 @@
 /*
- * kfpos_hip.hip -- host side of libkfpos_hip.so: the handle, launch selection, the three ways in (synchronous
- * host-buffer API, streaming slots, device-buffer API) and the C ABI of include/kfpos.h. The kernels live in
- * kfpos_k_*.hip (kfpos_kernels.h says which is where); the replay entry points (kfpos_run_*_dev: whole schedules in few
+ * kfpos_hip.hip -- host side of libkfpos_hip.so: the handle, launch selection, two of the three ways in
+ * (synchronous host-buffer API, device-buffer API) and the C ABI of include/kfpos.h. The kernels live in
+ * kfpos_k_*.hip (kfpos_kernels.h says which is where); the streaming slots in kfpos_hip_slots.hip; the replay entry points (kfpos_run_*_dev: whole schedules in few
  * launches) in kfpos_hip_replay.hip; the RCCL pose gather in kfpos_comm.hip.
  */
 #include <algorithm>
@@ -173,106 +173,140 @@ int stage_region(kfpos_handle *h, size_t bytes, void **out) {
 }
 void stage_reset(kfpos_handle *h) { h->stage_used = 0; }
 
-/* host row-major [T][C] -> component-major [C][T] of `esz`-byte elements: one copy + a device-side turn */
-int stage_in(kfpos_handle *h, void *dst, const void *src, int C, size_t esz) {
-    const size_t T = h->cfg.n_tags;
+/* host row-major [n][C] -> component-major [C][n] of `esz`-byte elements: one copy (into `landing`, or a region of the
+ * staging area) + a device-side turn */
+int stage_in(kfpos_handle *h, void *dst, const void *src, size_t n, int C, size_t esz, void *landing = nullptr) {
     if (C == 1) {
-        HIPCHK(hipMemcpy(dst, src, T * esz, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dst, src, n * esz, hipMemcpyHostToDevice));
         return KFPOS_OK;
     }
-    void *rows = nullptr;
-    const int rc = stage_region(h, T * C * esz, &rows);
+    const int rc = landing ? KFPOS_OK : stage_region(h, n * C * esz, &landing);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(rows, src, T * C * esz, hipMemcpyHostToDevice));
-    kfpos_k::launch_rows_to_cols(esz, nullptr, rows, dst, (int)T, C);
+    HIPCHK(hipMemcpy(landing, src, n * C * esz, hipMemcpyHostToDevice));
+    kfpos_k::launch_rows_to_cols(esz, nullptr, landing, dst, (int)n, C);
     HIPCHK(hipGetLastError());
     return KFPOS_OK;
 }
-/* device [C][T] doubles -> host row-major [T][C] */
-int stage_out(kfpos_handle *h, double *dst, const double *dsrc, int C) {
-    const size_t T = h->cfg.n_tags;
+/* device [C][n] doubles -> host row-major [n][C] */
+int stage_out(kfpos_handle *h, double *dst, const double *dsrc, size_t n, int C) {
     if (C == 1) {
-        HIPCHK(hipMemcpy(dst, dsrc, T * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dst, dsrc, n * sizeof(double), hipMemcpyDeviceToHost));
         return KFPOS_OK;
     }
     void *rows = nullptr;
-    const int rc = stage_region(h, T * C * sizeof(double), &rows);
+    const int rc = stage_region(h, n * C * sizeof(double), &rows);
     if (rc) return rc;
-    kfpos_k::launch_cols_to_rows(nullptr, dsrc, (double *)rows, (int)T, C);
+    kfpos_k::launch_cols_to_rows(nullptr, dsrc, (double *)rows, (int)n, C);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(dst, rows, T * C * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dst, rows, n * C * sizeof(double), hipMemcpyDeviceToHost));
     return KFPOS_OK;
 }
 
-int stage_dt(kfpos_handle *h, const double *dt, int32_t dt_len, const double **d_dt, double *shared) {
-    if (!dt || (dt_len != 1 && dt_len != h->cfg.n_tags)) return KFPOS_ERR_ARG;
-    if (dt_len == 1 && h->cfg.n_tags != 1) {
-        *d_dt = nullptr;
-        *shared = dt[0];
-        return KFPOS_OK;
-    }
-    HIPCHK(hipMemcpy(h->d_dt, dt, sizeof(double) * h->cfg.n_tags, hipMemcpyHostToDevice));
-    *d_dt = h->d_dt;
-    *shared = dt[0];
-    return KFPOS_OK;
-}
-
-int fetch_status(kfpos_handle *h, uint32_t *status) {
-    HIPCHK(hipDeviceSynchronize());
-    if (status) HIPCHK(hipMemcpy(status, h->d_status, sizeof(uint32_t) * h->cfg.n_tags, hipMemcpyDeviceToHost));
-    return KFPOS_OK;
-}
-
-
-/* ---- small banks: inputs and outputs in one host-pinned, device-mapped block (kfpos_handle::sm_*) ---- */
 size_t small_bank_limit() { /* elements of the range matrix (n_tags x max_anchors) up to which a bank is "small" */
     const char *e = getenv("KFPOS_SMALL_BANK_ELEMS");
     return e ? (size_t)atol(e) : 4096;
 }
 template <typename E>
-void rows_to_cols_host(void *dst, const void *src, size_t T, int C) {
+void rows_to_cols_host(void *dst, const void *src, size_t n, int C) {
     const E *s = (const E *)src;
     E *d = (E *)dst;
-    for (size_t t = 0; t < T; ++t)
-        for (int c = 0; c < C; ++c) d[(size_t)c * T + t] = s[t * C + c];
-}
-/* host row-major [T][C] -> component-major [C][T] inside the mapped block */
-void small_in_n(kfpos_handle *h, size_t off, const void *src, size_t T, int C, size_t esz) {
-    if (esz == 4) rows_to_cols_host<uint32_t>(h->sm_h + off, src, T, C);
-    else rows_to_cols_host<uint64_t>(h->sm_h + off, src, T, C);
-}
-void small_in(kfpos_handle *h, size_t off, const void *src, int C, size_t esz) { small_in_n(h, off, src, h->cfg.n_tags, C, esz); }
-/* component-major [C][T] doubles in the mapped block -> host row-major [T][C] */
-void small_out(const kfpos_handle *h, double *dst, size_t off_doubles, int C) {
-    const size_t T = h->cfg.n_tags;
-    const double *s = (const double *)(h->sm_h + h->sm_out) + off_doubles;
-    for (size_t t = 0; t < T; ++t)
-        for (int c = 0; c < C; ++c) dst[t * C + c] = s[(size_t)c * T + t];
-}
-int small_dt(kfpos_handle *h, const double *dt, int32_t dt_len, const double **d_dt, double *shared) {
-    if (!dt || (dt_len != 1 && dt_len != h->cfg.n_tags)) return KFPOS_ERR_ARG;
-    *shared = dt[0];
-    *d_dt = nullptr;
-    if (dt_len != 1) {
-        std::memcpy(h->sm_h + h->sm_dt, dt, sizeof(double) * h->cfg.n_tags);
-        *d_dt = (const double *)(h->sm_d + h->sm_dt);
-    }
-    return KFPOS_OK;
-}
-int small_finish(kfpos_handle *h, uint32_t *status) {
-    HIPCHK(hipStreamSynchronize(nullptr)); /* the kernel's writes into the mapped block are visible now */
-    if (status) std::memcpy(status, h->sm_h + h->sm_status, sizeof(uint32_t) * h->cfg.n_tags);
-    return KFPOS_OK;
+    for (size_t t = 0; t < n; ++t)
+        for (int c = 0; c < C; ++c) d[(size_t)c * n + t] = s[t * C + c];
 }
 
-/* ---- streaming host API: wait for whatever the slots still have in flight ---- */
-int drain_slots(kfpos_handle *h) {
-    for (auto &sl : h->slot)
-        if (sl.busy) {
-            HIPCHK(hipEventSynchronize(sl.done));
-            sl.busy = false;
+/* ---- the route a host-buffer call takes to the device, chosen once per call ----
+ * mapped (small banks, kfpos_handle::sm): inputs and outputs live in one host-pinned, device-mapped block; the CPU turns
+ * the layout in place, the kernels read and write host memory over the bus, and the call ends with a synchronisation of
+ * the null stream. staged: plain copies into device buffers and a layout kernel per array, ended by a device
+ * synchronisation. A call names, per array, where it lives on either route (Place) and uses the operations below; it
+ * never asks which route it is on. */
+struct Place {
+    size_t mapped; /* offset in the mapped block */
+    void *dst;     /* staged: the component-major device array ... */
+    void *landing; /* ... and where the row-major copy lands before its turn (null: a region of the staging area) */
+};
+constexpr size_t TAGS_STAGE_MAX = (size_t)16 << 20;
+struct Route {
+    kfpos_handle *h;
+    unsigned char *host, *dev; /* the mapped block (host == null: staged; dev is then the region block() reserved) */
+    size_t chunk;              /* block(): records it holds */
+
+    void *at(const Place &p) const { return host ? dev + p.mapped : p.dst; }
+    /* row-major host array [n][C] of esz-byte elements in, component-major at(p) */
+    int in(const void *src, size_t n, int C, size_t esz, const Place &p) {
+        if (!host) return stage_in(h, p.dst, src, n, C, esz, p.landing);
+        if (esz == 4) rows_to_cols_host<uint32_t>(host + p.mapped, src, n, C);
+        else rows_to_cols_host<uint64_t>(host + p.mapped, src, n, C);
+        return KFPOS_OK;
+    }
+    /* dt of a call, validated: one value (dt_len == 1) travels in the arguments, an array goes up. null = shared */
+    int dt_in(const double *dt, int32_t dt_len, size_t n, const Place &p, const double **d_dt) {
+        *d_dt = dt_len == 1 ? nullptr : (const double *)at(p);
+        return dt_len == 1 ? KFPOS_OK : in(dt, n, 1, sizeof(double), p);
+    }
+    /* component-major doubles [C][n] at device address d (inside a Place of this call) out to row-major host */
+    int out(double *dst, const double *d, size_t n, int C) {
+        if (!host) return stage_out(h, dst, d, n, C);
+        const double *s = (const double *)(host + ((const unsigned char *)d - dev));
+        for (size_t t = 0; t < n; ++t)
+            for (int c = 0; c < C; ++c) dst[t * C + c] = s[(size_t)c * n + t];
+        return KFPOS_OK;
+    }
+    /* the call's launches have completed (a mapped block's results are visible) */
+    int sync() {
+        HIPCHK(host ? hipStreamSynchronize(nullptr) : hipDeviceSynchronize());
+        return KFPOS_OK;
+    }
+    /* n status words delivered, after sync() */
+    int words(uint32_t *status, const Place &p, size_t n) {
+        if (status && host) std::memcpy(status, host + p.mapped, sizeof(uint32_t) * n);
+        else if (status) HIPCHK(hipMemcpy(status, p.dst, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+        return KFPOS_OK;
+    }
+    int finish(uint32_t *status, const Place &p, size_t n) {
+        const int rc = sync();
+        return rc ? rc : words(status, p, n);
+    }
+    /* staged: p.dst = `bytes` of the staging area (reserve() first where several are held at once, so that none moves
+     * while another is in use); mapped: the block has its places already */
+    int reserve(size_t bytes) {
+        void *probe = nullptr;
+        const int rc = host ? KFPOS_OK : stage_region(h, bytes, &probe);
+        if (!host) stage_reset(h);
+        return rc;
+    }
+    int region(size_t bytes, Place &p) { return host ? KFPOS_OK : stage_region(h, bytes, &p.dst); }
+    /* The per-tag calls stage records: the whole mapped block, or one region of the staging area filled and emptied
+     * with plain copies, addressed as dev + offset. Sized for n records of `rec` bytes, at most TAGS_STAGE_MAX: longer
+     * lists go through it in chunks of `chunk` (>= 1) records. */
+    int block(size_t rec, size_t n) {
+        size_t cap = h->sm.bytes;
+        if (!host) {
+            cap = rec * n < TAGS_STAGE_MAX ? rec * n : TAGS_STAGE_MAX;
+            const int rc = stage_region(h, cap, (void **)&dev);
+            if (rc) return rc;
         }
-    return KFPOS_OK;
+        chunk = cap / rec;
+        if (chunk == 0) { /* (a loop over chunks of nothing would never end) */
+            g_err = "per-tag staging holds less than one tag";
+            return KFPOS_ERR_STATE;
+        }
+        return KFPOS_OK;
+    }
+    hipError_t up(size_t off, const void *src, size_t bytes) const {
+        if (!host) return hipMemcpy(dev + off, src, bytes, hipMemcpyHostToDevice);
+        std::memcpy(host + off, src, bytes);
+        return hipSuccess;
+    }
+    hipError_t down(void *dst, size_t off, size_t bytes) const {
+        if (!host) return hipMemcpy(dst, dev + off, bytes, hipMemcpyDeviceToHost);
+        std::memcpy(dst, host + off, bytes);
+        return hipSuccess;
+    }
+};
+Route route_of(kfpos_handle *h) {
+    if (!h->sm_h) stage_reset(h);
+    return Route{h, h->sm_h, h->sm_h ? h->sm_d : nullptr, 0};
 }
 
 /* packed index of the stored covariance entry (i, j) */
@@ -416,16 +450,8 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
         return KFPOS_ERR_HIP;
     }
     if (T * A <= small_bank_limit()) { /* small bank: one mapped block instead of staging copies (kfpos_handle::sm_*) */
-        size_t off = 0;
-        auto region = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-        h->sm_ranges = region(A * T * sizeof(int32_t));
-        h->sm_err = region(A * T * m);
-        h->sm_accel = region(3 * T * m);
-        h->sm_cov = region(9 * T * m);
-        h->sm_dt = region(T * sizeof(double));
-        h->sm_sensor = region(24 * T * sizeof(double));
-        h->sm_status = region(T * sizeof(uint32_t));
-        h->sm_out = region((size_t)(15 + h->n + h->n * h->n) * T * sizeof(double));
+        h->sm = kfpos_layout::mapped_layout(handle_sizes(h));
+        const size_t off = h->sm.bytes;
         void *hp = nullptr, *dp = nullptr;
         if (hipHostMalloc(&hp, off, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
             g_err = "hipHostMalloc(mapped block of a small bank) failed";
@@ -435,7 +461,6 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
         }
         std::memset(hp, 0, off);
         h->sm_h = (unsigned char *)hp;
-        h->sm_bytes = off;
         h->sm_d = (unsigned char *)dp;
     }
     const bool parks = cfg->model == KFPOS_MODEL_PLANAR || (cfg->model == KFPOS_MODEL_TOA && h->full);
@@ -539,10 +564,10 @@ int kfpos_set_init_positions(kfpos_handle *h, const double *xyz) {
     if (!h->cfg.use_init_pos || h->stepped) return KFPOS_ERR_STATE;
     stage_reset(h);
     if (h->n == 3) { /* ALGORITHM_ML: the seed of every solve */
-        const int rc = stage_in(h, h->d_vel, xyz, 3, sizeof(double));
+        const int rc = stage_in(h, h->d_vel, xyz, h->cfg.n_tags, 3, sizeof(double));
         if (rc) return rc;
     }
-    const int rc = stage_in(h, h->d_pos, xyz, 3, sizeof(double));
+    const int rc = stage_in(h, h->d_pos, xyz, h->cfg.n_tags, 3, sizeof(double));
     if (rc == KFPOS_OK && h->n == 8) { /* the filter works at mUWBtagZ, whatever initialPosition.z says */
         std::vector<double> z(h->cfg.n_tags, h->planar.fixed_height);
         HIPCHK(hipMemcpy(h->d_pos + 2 * (size_t)h->cfg.n_tags, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -569,74 +594,84 @@ int kfpos_set_planar(kfpos_handle *h, const kfpos_planar_config *cfg) {
 int kfpos_real_size(const kfpos_handle *h) { return h ? h->msz : 0; }
 int kfpos_state_dim(const kfpos_handle *h) { return h ? h->n : 0; }
 
-/* ---- device-buffer API ---- */
+/* ---- rounds: what a call feeds, and whether this handle takes it (kfpos_kernels.h: Round) ---- */
+static_assert(ROUND_TOA == MODE_TOA && ROUND_IMU == MODE_IMU_ONLY && ROUND_FUSED == MODE_FUSED, "Round::mode = the kind");
+static_assert(ROUND_TOA == KFPOS_SLOT_TOA && ROUND_IMU == KFPOS_SLOT_IMU && ROUND_FUSED == KFPOS_SLOT_TOA_IMU, "a slot's kind is a round kind");
+extern "C++" Round round_check(const kfpos_handle *h, int kind, int32_t sensor_kind, bool slot) {
+    static const int width[5] = {0, 5, 24, 3, 1}; /* KFPOS_SENSOR_PX4FLOW, _IMU, _MAG, _COMPASS */
+    const bool sensor = kind == ROUND_SENSOR && !slot && sensor_kind >= 1 && sensor_kind <= 4;
+    const bool imu9 = h->cfg.model == KFPOS_MODEL_TOA_IMU, planar = h->cfg.model == KFPOS_MODEL_PLANAR;
+    Round r = {KFPOS_OK, kind == ROUND_TOA || kind == ROUND_FUSED, kind == ROUND_IMU || kind == ROUND_FUSED,
+               sensor ? width[sensor_kind] : 0, sensor ? sensor_kind : kind};
+    if (!sensor && kind != ROUND_TOA && kind != ROUND_IMU && kind != ROUND_FUSED) r.answer = KFPOS_ERR_ARG;
+    else if (slot && planar && kind != ROUND_TOA) r.answer = KFPOS_ERR_MODEL; /* its sensors: kfpos_step_sensor / _rows */
+    else if (kind == ROUND_FUSED && !imu9) r.answer = KFPOS_ERR_MODEL;
+    /* the empty virtuals: KalmanFilterTOA::newIMUMeasurement, PositionEstimationAlgorithm.h:26-35 */
+    else if ((kind == ROUND_IMU && !imu9) || (sensor && !planar)) r.answer = ROUND_EMPTY;
+    else if (r.has_rng && !h->have_anchors) r.answer = KFPOS_ERR_STATE;
+    return r;
+}
+extern "C++" int round_refusal(int answer) {
+    if (answer == KFPOS_ERR_STATE)
+        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
+    return answer;
+}
+extern "C++" void round_args(const kfpos_handle *h, const Round &r, const RoundIn &in, const double *dt, double dt_shared,
+                             uint32_t *status, double *traj, KArgs &a) {
+    fill_args(h, a);
+    if (r.has_rng) {
+        a.ranges = in.ranges;
+        a.err = in.err;
+    }
+    if (r.has_imu) {
+        a.accel = in.accel;
+        a.cov = in.cov;
+    }
+    if (r.width) a.sensor = in.sensor;
+    a.mode = r.mode;
+    a.dt = dt;
+    a.dt_shared = dt_shared;
+    a.status = status;
+    a.traj = traj;
+}
+
+/* ---- device-buffer API: the caller has checked h and the pointers its kind carries ---- */
+static int round_dev(kfpos_handle *h, int kind, int32_t sensor_kind, const RoundIn &in, int32_t latch, const double *dt,
+                     double dt_shared, uint32_t *status, void *stream) {
+    DevScope dev_(h->cfg.device);
+    const Round r = round_check(h, kind, sensor_kind, false);
+    if (r.answer == ROUND_EMPTY) { /* (an IMU sample leaves the caller's status words as they are) */
+        if (status && r.width) HIPCHK(hipMemsetAsync(status, 0, sizeof(uint32_t) * h->cfg.n_tags, (hipStream_t)stream));
+        return KFPOS_OK;
+    }
+    if (r.answer) return round_refusal(r.answer);
+    KArgs a;
+    round_args(h, r, in, dt, dt_shared, status, nullptr, a);
+    a.latch = latch ? 1 : 0;
+    const int rc = launch_step(h, a, (hipStream_t)stream);
+    if (r.width) h->planar_sensors = true; /* ranging epochs now carry the latched samples */
+    return rc;
+}
+
 int kfpos_step_toa_dev(kfpos_handle *h, const int32_t *range_mm, const void *err_est, const double *dt,
                        double dt_shared, uint32_t *status, void *stream) {
     g_err.clear();
     if (!h || !range_mm || !err_est) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (!h->have_anchors) {
-        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
-        return KFPOS_ERR_STATE;
-    }
-    KArgs a;
-    fill_args(h, a);
-    a.ranges = range_mm;
-    a.err = err_est;
-    a.dt = dt;
-    a.dt_shared = dt_shared;
-    a.status = status;
-    a.mode = MODE_TOA;
-    return launch_step(h, a, (hipStream_t)stream);
+    return round_dev(h, ROUND_TOA, 0, {range_mm, err_est, nullptr, nullptr, nullptr}, 1, dt, dt_shared, status, stream);
 }
 
 int kfpos_step_imu_dev(kfpos_handle *h, const void *accel, const void *cov, const double *dt,
                        double dt_shared, uint32_t *status, void *stream) {
     g_err.clear();
     if (!h || !accel || !cov) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (h->cfg.model != KFPOS_MODEL_TOA_IMU) return KFPOS_OK; /* KalmanFilterTOA::newIMUMeasurement is empty */
-    KArgs a;
-    fill_args(h, a);
-    a.accel = accel;
-    a.cov = cov;
-    a.dt = dt;
-    a.dt_shared = dt_shared;
-    a.status = status;
-    a.mode = MODE_IMU_ONLY;
-    a.latch = 1;
-    return launch_step(h, a, (hipStream_t)stream);
-}
-
-static int sensor_width(int32_t kind) {
-    switch (kind) {
-    case KFPOS_SENSOR_PX4FLOW: return 5;
-    case KFPOS_SENSOR_IMU: return 24;
-    case KFPOS_SENSOR_MAG: return 3;
-    case KFPOS_SENSOR_COMPASS: return 1;
-    default: return 0;
-    }
+    return round_dev(h, ROUND_IMU, 0, {nullptr, nullptr, accel, cov, nullptr}, 1, dt, dt_shared, status, stream);
 }
 
 int kfpos_step_sensor_dev(kfpos_handle *h, int32_t kind, const double *data, const double *dt, double dt_shared,
                           uint32_t *status, void *stream) {
     g_err.clear();
-    if (!h || !data || sensor_width(kind) == 0) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (h->cfg.model != KFPOS_MODEL_PLANAR) { /* the empty virtuals of PositionEstimationAlgorithm.h:26-35 */
-        if (status) HIPCHK(hipMemsetAsync(status, 0, sizeof(uint32_t) * h->cfg.n_tags, (hipStream_t)stream));
-        return KFPOS_OK;
-    }
-    KArgs a;
-    fill_args(h, a);
-    a.sensor = data;
-    a.dt = dt;
-    a.dt_shared = dt_shared;
-    a.status = status;
-    a.mode = kind;
-    const int rc = launch_step(h, a, (hipStream_t)stream);
-    h->planar_sensors = true; /* ranging epochs now carry the latched samples */
-    return rc;
+    if (!h || !data) return KFPOS_ERR_ARG;
+    return round_dev(h, ROUND_SENSOR, kind, {nullptr, nullptr, nullptr, nullptr, data}, 1, dt, dt_shared, status, stream);
 }
 
 int kfpos_step_toa_imu_dev(kfpos_handle *h, const int32_t *range_mm, const void *err_est, const void *accel,
@@ -644,25 +679,11 @@ int kfpos_step_toa_imu_dev(kfpos_handle *h, const int32_t *range_mm, const void 
                            uint32_t *status, void *stream) {
     g_err.clear();
     if (!h || !range_mm || !err_est || !accel || !cov) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (h->cfg.model != KFPOS_MODEL_TOA_IMU) return KFPOS_ERR_MODEL;
-    if (!h->have_anchors) return KFPOS_ERR_STATE;
-    KArgs a;
-    fill_args(h, a);
-    a.ranges = range_mm;
-    a.err = err_est;
-    a.accel = accel;
-    a.cov = cov;
-    a.dt = dt;
-    a.dt_shared = dt_shared;
-    a.status = status;
-    a.mode = MODE_FUSED;
-    a.latch = latch ? 1 : 0;
-    return launch_step(h, a, (hipStream_t)stream);
+    return round_dev(h, ROUND_FUSED, 0, {range_mm, err_est, accel, cov, nullptr}, latch, dt, dt_shared, status, stream);
 }
 
 /* the bank as the pose kernels read it; outputs and extrapolation times: null / 0 until the caller sets them */
-static void pose_bank_args(const kfpos_handle *h, PoseArgs &a) {
+extern "C++" void pose_bank_args(const kfpos_handle *h, PoseArgs &a) {
     std::memset(&a, 0, sizeof(a));
     a.T = h->cfg.n_tags;
     a.model = h->cfg.model;
@@ -702,268 +723,71 @@ int kfpos_get_pose_dev(kfpos_handle *h, double dt_ahead, double *pos, double *co
 }
 
 /* ---- host-buffer API ---- */
+/* Every synchronous step call, whole-bank (listed = false: n_tags tags) or for a row list: what the round may feed, the
+ * inputs through the call's route to where the step reads them -- the bank's staging arrays, or the work block's input
+ * area 0 and work bank (the slots have been drained) --, the step, the status words back. */
+static int round_host(kfpos_handle *h, const char *who, int kind, int32_t sensor_kind, bool listed, const int32_t *rows,
+                      int32_t n, const RoundIn &src, const double *dt, int32_t dt_len, uint32_t *status) {
+    g_err.clear();
+    if (!h) return KFPOS_ERR_ARG;
+    const Round r = round_check(h, kind, sensor_kind, false);
+    if (r.answer == KFPOS_ERR_ARG) return KFPOS_ERR_ARG;
+    int rc = listed ? rows_check(h, who, rows, n) : KFPOS_OK;
+    if (rc) return rc;
+    if (!listed) n = h->cfg.n_tags;
+    if (n == 0) return KFPOS_OK;
+    if ((r.has_rng && (!src.ranges || !src.err)) || (r.has_imu && (!src.accel || !src.cov)) || (r.width && !src.sensor)) return KFPOS_ERR_ARG;
+    if (r.answer == ROUND_EMPTY) {
+        if (status) std::memset(status, 0, sizeof(uint32_t) * n);
+        return KFPOS_OK;
+    }
+    if (r.answer) return round_refusal(r.answer);
+    DevScope dev_(h->cfg.device);
+    if ((rc = drain_slots(h))) return rc;
+    if (!dt || (dt_len != 1 && dt_len != n)) return KFPOS_ERR_ARG;
+    if (listed && (rc = rows_reserve(h, (size_t)n))) return rc;
+    const kfpos_layout::Rows L = listed ? rows_layout(h, (size_t)n) : kfpos_layout::Rows{};
+    auto place = [&](size_t mapped, void *bank, size_t w_off, size_t i_off) {
+        return listed ? Place{mapped, h->d_work + w_off, h->d_work + i_off} : Place{mapped, bank, nullptr};
+    };
+    const size_t N = (size_t)n, m = h->msz;
+    const int A = h->cfg.max_anchors;
+    const Place p_rows = {h->sm.out, h->d_work + L.i_rows, nullptr}; /* mapped: the pose-output region, free during a step */
+    const Place p_dt = place(h->sm.dt, h->d_dt, L.i_dt, 0), p_status = place(h->sm.status, h->d_status, L.i_status, 0);
+    const Place p_ranges = place(h->sm.ranges, h->d_ranges, L.w_ranges, L.i_ranges), p_err = place(h->sm.err, h->d_err, L.w_err, L.i_err);
+    const Place p_accel = place(h->sm.accel, h->d_accel, L.w_accel, L.i_accel), p_cov = place(h->sm.cov, h->d_cov, L.w_cov, L.i_cov);
+    const Place p_sensor = place(h->sm.sensor, h->d_sensor, L.w_sensor, L.i_sensor);
+    Route rt = route_of(h);
+    const double *d_dt;
+    if (listed && (rc = rt.in(rows, N, 1, sizeof(int32_t), p_rows))) return rc;
+    if ((rc = rt.dt_in(dt, dt_len, N, p_dt, &d_dt))) return rc;
+    if (r.has_rng && ((rc = rt.in(src.ranges, N, A, sizeof(int32_t), p_ranges)) || (rc = rt.in(src.err, N, A, m, p_err)))) return rc;
+    if (r.has_imu && ((rc = rt.in(src.accel, N, 3, m, p_accel)) || (rc = rt.in(src.cov, N, 9, m, p_cov)))) return rc;
+    if (r.width && (rc = rt.in(src.sensor, N, r.width, sizeof(double), p_sensor))) return rc;
+    const RoundIn in = {(const int32_t *)rt.at(p_ranges), rt.at(p_err), rt.at(p_accel), rt.at(p_cov), (const double *)rt.at(p_sensor)};
+    KArgs a;
+    round_args(h, r, in, d_dt, dt[0], (uint32_t *)rt.at(p_status), nullptr, a);
+    rc = listed ? rows_step(h, nullptr, L, (const int32_t *)rt.at(p_rows), n, a) : launch_step(h, a, nullptr);
+    if (r.width) h->planar_sensors = true; /* ranging epochs now carry the latched samples */
+    if (rc) return rc;
+    return rt.finish(status, p_status, N);
+}
+
 int kfpos_step_toa(kfpos_handle *h, const int32_t *range_mm, const void *err_est, const double *dt,
                    int32_t dt_len, uint32_t *status) {
-    g_err.clear();
-    if (!h || !range_mm || !err_est) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (!h->have_anchors) {
-        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
-        return KFPOS_ERR_STATE;
-    }
-    int rc = drain_slots(h);
-    if (rc) return rc;
-    const double *d_dt;
-    double shared;
-    if (h->sm_h) {
-        if ((rc = small_dt(h, dt, dt_len, &d_dt, &shared))) return rc;
-        small_in(h, h->sm_ranges, range_mm, h->cfg.max_anchors, sizeof(int32_t));
-        small_in(h, h->sm_err, err_est, h->cfg.max_anchors, h->msz);
-        if ((rc = kfpos_step_toa_dev(h, (const int32_t *)(h->sm_d + h->sm_ranges), h->sm_d + h->sm_err, d_dt, shared,
-                                     (uint32_t *)(h->sm_d + h->sm_status), nullptr)))
-            return rc;
-        return small_finish(h, status);
-    }
-    stage_reset(h);
-    if ((rc = stage_dt(h, dt, dt_len, &d_dt, &shared))) return rc;
-    if ((rc = stage_in(h, h->d_ranges, range_mm, h->cfg.max_anchors, sizeof(int32_t)))) return rc;
-    if ((rc = stage_in(h, h->d_err, err_est, h->cfg.max_anchors, h->msz))) return rc;
-    if ((rc = kfpos_step_toa_dev(h, h->d_ranges, h->d_err, d_dt, shared, h->d_status, nullptr))) return rc;
-    return fetch_status(h, status);
+    return round_host(h, "kfpos_step_toa", ROUND_TOA, 0, false, nullptr, 0, {range_mm, err_est, nullptr, nullptr, nullptr}, dt, dt_len, status);
 }
-
 int kfpos_step_imu(kfpos_handle *h, const void *accel, const void *cov, const double *dt, int32_t dt_len,
                    uint32_t *status) {
-    g_err.clear();
-    if (!h || !accel || !cov) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (h->cfg.model != KFPOS_MODEL_TOA_IMU) {
-        if (status) std::memset(status, 0, sizeof(uint32_t) * h->cfg.n_tags);
-        return KFPOS_OK;
-    }
-    const double *d_dt;
-    double shared;
-    int rc = drain_slots(h);
-    if (rc) return rc;
-    if (h->sm_h) {
-        if ((rc = small_dt(h, dt, dt_len, &d_dt, &shared))) return rc;
-        small_in(h, h->sm_accel, accel, 3, h->msz);
-        small_in(h, h->sm_cov, cov, 9, h->msz);
-        if ((rc = kfpos_step_imu_dev(h, h->sm_d + h->sm_accel, h->sm_d + h->sm_cov, d_dt, shared,
-                                     (uint32_t *)(h->sm_d + h->sm_status), nullptr)))
-            return rc;
-        return small_finish(h, status);
-    }
-    stage_reset(h);
-    if ((rc = stage_dt(h, dt, dt_len, &d_dt, &shared))) return rc;
-    if ((rc = stage_in(h, h->d_accel, accel, 3, h->msz))) return rc;
-    if ((rc = stage_in(h, h->d_cov, cov, 9, h->msz))) return rc;
-    if ((rc = kfpos_step_imu_dev(h, h->d_accel, h->d_cov, d_dt, shared, h->d_status, nullptr))) return rc;
-    return fetch_status(h, status);
+    return round_host(h, "kfpos_step_imu", ROUND_IMU, 0, false, nullptr, 0, {nullptr, nullptr, accel, cov, nullptr}, dt, dt_len, status);
 }
-
 int kfpos_step_sensor(kfpos_handle *h, int32_t kind, const double *data, const double *dt, int32_t dt_len,
                       uint32_t *status) {
-    g_err.clear();
-    const int C = sensor_width(kind);
-    if (!h || !data || C == 0) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (h->cfg.model != KFPOS_MODEL_PLANAR) {
-        if (status) std::memset(status, 0, sizeof(uint32_t) * h->cfg.n_tags);
-        return KFPOS_OK;
-    }
-    const double *d_dt;
-    double shared;
-    int rc = drain_slots(h);
-    if (rc) return rc;
-    if (h->sm_h) {
-        if ((rc = small_dt(h, dt, dt_len, &d_dt, &shared))) return rc;
-        small_in(h, h->sm_sensor, data, C, sizeof(double));
-        if ((rc = kfpos_step_sensor_dev(h, kind, (const double *)(h->sm_d + h->sm_sensor), d_dt, shared,
-                                        (uint32_t *)(h->sm_d + h->sm_status), nullptr)))
-            return rc;
-        return small_finish(h, status);
-    }
-    stage_reset(h);
-    if ((rc = stage_dt(h, dt, dt_len, &d_dt, &shared))) return rc;
-    if ((rc = stage_in(h, h->d_sensor, data, C, sizeof(double)))) return rc;
-    if ((rc = kfpos_step_sensor_dev(h, kind, h->d_sensor, d_dt, shared, h->d_status, nullptr))) return rc;
-    return fetch_status(h, status);
+    return round_host(h, "kfpos_step_sensor", ROUND_SENSOR, kind, false, nullptr, 0, {nullptr, nullptr, nullptr, nullptr, data}, dt, dt_len, status);
 }
-
-
-/* ---- streaming host API (kfpos.h: kfpos_slot_*) ---- */
-static int slots_init(kfpos_handle *h) {
-    if (h->s_copy) return KFPOS_OK;
-    {
-        const char *e = getenv("KFPOS_SLOT_SPLIT_BYTES");
-        h->split_bytes = e ? (size_t)atol(e) : 0; /* off: measured slower inside the pipeline (profiles/r02i_*) */
-    }
-    const size_t T = h->cfg.n_tags, A = h->cfg.max_anchors, m = h->msz;
-    size_t off = 0;
-    auto region = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    h->so_ranges = region(A * T * sizeof(int32_t));
-    h->so_err = region(A * T * m);
-    h->so_accel = region(3 * T * m);
-    h->so_cov = region(9 * T * m);
-    h->so_dt = region(T * sizeof(double));
-    h->so_status = region(T * sizeof(uint32_t));
-    h->so_pos = region(3 * T * sizeof(double));
-    h->so_bytes = off;
-    HIPCHK(hipStreamCreateWithFlags(&h->s_copy, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&h->s_copy2, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&h->s_comp, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&h->s_back, hipStreamNonBlocking));
-    for (auto &sl : h->slot) {
-        HIPCHK(hipHostMalloc((void **)&sl.host, off, hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&sl.dev, off));
-        std::memset(sl.host, 0, off);
-        HIPCHK(hipMemset(sl.dev, 0, off));
-        HIPCHK(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&sl.copied2, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&sl.computed, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    }
-    HIPCHK(hipDeviceSynchronize()); /* whatever the other entry points queued on the default stream comes first */
-    return KFPOS_OK;
-}
-
-int kfpos_slot_count(const kfpos_handle *h) { return h ? KFPOS_N_SLOTS : 0; }
-
-int kfpos_slot_acquire(kfpos_handle *h, int32_t slot, kfpos_epoch_slot *out) {
-    g_err.clear();
-    if (!h || !out || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    const int rc = slots_init(h);
-    if (rc) return rc;
-    auto &sl = h->slot[slot];
-    if (sl.busy) { /* its last submission: inputs consumed, outputs delivered */
-        HIPCHK(hipEventSynchronize(sl.done));
-        sl.busy = false;
-    }
-    out->range_mm = (int32_t *)(sl.host + h->so_ranges);
-    out->err_est = sl.host + h->so_err;
-    out->accel = sl.host + h->so_accel;
-    out->cov = sl.host + h->so_cov;
-    out->dt = (double *)(sl.host + h->so_dt);
-    out->status = (uint32_t *)(sl.host + h->so_status);
-    out->pos = (double *)(sl.host + h->so_pos);
-    return KFPOS_OK;
-}
-
-int kfpos_slot_submit(kfpos_handle *h, int32_t slot, int32_t flags, double dt_shared) {
-    g_err.clear();
-    if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (!h->s_copy || h->slot[slot].busy) {
-        g_err = "kfpos_slot_submit: acquire the slot first (kfpos_slot_acquire)";
-        return KFPOS_ERR_STATE;
-    }
-    const int kind = flags & 0xff;
-    if (kind != KFPOS_SLOT_TOA && kind != KFPOS_SLOT_IMU && kind != KFPOS_SLOT_TOA_IMU) return KFPOS_ERR_ARG;
-    if (h->cfg.model == KFPOS_MODEL_PLANAR && kind != KFPOS_SLOT_TOA) return KFPOS_ERR_MODEL; /* its sensors: kfpos_step_sensor */
-    const bool imu9 = h->cfg.model == KFPOS_MODEL_TOA_IMU;
-    if (kind == KFPOS_SLOT_TOA_IMU && !imu9) return KFPOS_ERR_MODEL;
-    const bool has_rng = kind != KFPOS_SLOT_IMU, has_imu = imu9 && kind != KFPOS_SLOT_TOA;
-    if (kind == KFPOS_SLOT_IMU && !imu9) { /* KalmanFilterTOA::newIMUMeasurement is empty */
-        std::memset(h->slot[slot].host + h->so_status, 0, sizeof(uint32_t) * h->cfg.n_tags);
-        return KFPOS_OK;
-    }
-    if (has_rng && !h->have_anchors) {
-        g_err = "kfpos_set_anchors has not been called";
-        return KFPOS_ERR_STATE;
-    }
-    auto &sl = h->slot[slot];
-    const size_t T = h->cfg.n_tags, A = h->cfg.max_anchors, m = h->msz;
-    /* 1. inputs: pinned host -> device on the copy stream. A complete fused epoch is one contiguous block of the slot
-     * (ranges | err | accel | cov | dt): one DMA instead of five. Measured on this platform (tools/exp/h2d_probe.hip,
-     * profiles/r02g_*): a lone 7.3 MB copy moves at 27-35 GB/s while the GPU is otherwise idle and at 53 GB/s while a
-     * kernel is running; two halves on two streams reach 55 GB/s when ALONE but were slower inside this pipeline
-     * (KFPOS_SLOT_SPLIT_BYTES=n turns that on for copies of n bytes and more; default off). */
-    bool second = false;
-    auto h2d = [&](size_t off, size_t bytes) -> hipError_t {
-        if (h->split_bytes == 0 || bytes < h->split_bytes) return hipMemcpyAsync(sl.dev + off, sl.host + off, bytes, hipMemcpyHostToDevice, h->s_copy);
-        const size_t half = (bytes / 2 + 255) & ~(size_t)255;
-        hipError_t e = hipMemcpyAsync(sl.dev + off, sl.host + off, half, hipMemcpyHostToDevice, h->s_copy);
-        if (e != hipSuccess) return e;
-        second = true;
-        return hipMemcpyAsync(sl.dev + off + half, sl.host + off + half, bytes - half, hipMemcpyHostToDevice, h->s_copy2);
-    };
-    /* a slot's device copy of err / cov may still be read by a later submission of another slot that reused it
-     * (KFPOS_SLOT_REUSE_*) -- also after a third slot has uploaded newer ones in between */
-    auto guard = [&](hipEvent_t last_use) -> hipError_t {
-        hipError_t e = hipStreamWaitEvent(h->s_copy, last_use, 0);
-        return e != hipSuccess ? e : hipStreamWaitEvent(h->s_copy2, last_use, 0);
-    };
-    const bool up_err = has_rng && !(flags & KFPOS_SLOT_REUSE_ERR), up_cov = has_imu && !(flags & KFPOS_SLOT_REUSE_COV);
-    if (has_rng && !up_err && h->err_slot < 0) {
-        g_err = "KFPOS_SLOT_REUSE_ERR before any errorEstimation was submitted";
-        return KFPOS_ERR_STATE;
-    }
-    if (has_imu && !up_cov && h->cov_slot < 0) {
-        g_err = "KFPOS_SLOT_REUSE_COV before any covariance was submitted";
-        return KFPOS_ERR_STATE;
-    }
-    if (up_err && sl.err_reader) HIPCHK(guard(sl.err_reader));
-    if (up_cov && sl.cov_reader) HIPCHK(guard(sl.cov_reader));
-    if (up_err && up_cov) { /* the whole block in one go */
-        const size_t end = (flags & KFPOS_SLOT_DT_PER_TAG) ? h->so_dt + T * sizeof(double) : h->so_cov + 9 * T * m;
-        HIPCHK(h2d(h->so_ranges, end - h->so_ranges));
-    } else {
-        if (has_rng) HIPCHK(h2d(h->so_ranges, up_err ? h->so_err + A * T * m - h->so_ranges : A * T * sizeof(int32_t)));
-        if (has_imu) HIPCHK(h2d(h->so_accel, up_cov ? h->so_cov + 9 * T * m - h->so_accel : 3 * T * m));
-        if (flags & KFPOS_SLOT_DT_PER_TAG) HIPCHK(h2d(h->so_dt, T * sizeof(double)));
-    }
-    if (up_err) h->err_slot = slot;
-    if (up_cov) h->cov_slot = slot;
-    HIPCHK(hipEventRecord(sl.copied, h->s_copy));
-    if (second) HIPCHK(hipEventRecord(sl.copied2, h->s_copy2));
-    /* 2. the step, on the compute stream (submissions run in order: the filter state is sequential) */
-    HIPCHK(hipStreamWaitEvent(h->s_comp, sl.copied, 0));
-    if (second) HIPCHK(hipStreamWaitEvent(h->s_comp, sl.copied2, 0));
-    KArgs a;
-    fill_args(h, a);
-    a.mode = kind == KFPOS_SLOT_TOA ? MODE_TOA : (kind == KFPOS_SLOT_IMU ? MODE_IMU_ONLY : MODE_FUSED);
-    a.latch = 1;
-    if (has_rng) {
-        a.ranges = (const int32_t *)(sl.dev + h->so_ranges);
-        a.err = h->slot[h->err_slot].dev + h->so_err;
-    }
-    if (has_imu) {
-        a.accel = sl.dev + h->so_accel;
-        a.cov = h->slot[h->cov_slot].dev + h->so_cov;
-    }
-    a.dt = (flags & KFPOS_SLOT_DT_PER_TAG) ? (const double *)(sl.dev + h->so_dt) : nullptr;
-    a.dt_shared = dt_shared;
-    a.status = (uint32_t *)(sl.dev + h->so_status);
-    const bool want_pose = !(flags & KFPOS_SLOT_NO_POSE);
-    a.traj = want_pose ? (double *)(sl.dev + h->so_pos) : nullptr;
-    const int rc = launch_step(h, a, h->s_comp);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(sl.computed, h->s_comp));
-    if (has_rng) h->slot[h->err_slot].err_reader = sl.computed;
-    if (has_imu) h->slot[h->cov_slot].cov_reader = sl.computed;
-    /* 3. outputs: device -> pinned host, on the return stream */
-    HIPCHK(hipStreamWaitEvent(h->s_back, sl.computed, 0));
-    /* status words and poses sit side by side in the slot: one copy */
-    HIPCHK(hipMemcpyAsync(sl.host + h->so_status, sl.dev + h->so_status,
-                          want_pose ? h->so_pos + 3 * T * sizeof(double) - h->so_status : T * sizeof(uint32_t),
-                          hipMemcpyDeviceToHost, h->s_back));
-    HIPCHK(hipEventRecord(sl.done, h->s_back));
-    sl.busy = true;
-    return KFPOS_OK;
-}
-
-int kfpos_slot_wait(kfpos_handle *h, int32_t slot) {
-    g_err.clear();
-    if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    auto &sl = h->slot[slot];
-    if (sl.busy) {
-        HIPCHK(hipEventSynchronize(sl.done));
-        sl.busy = false;
-    }
-    return KFPOS_OK;
+int kfpos_step_toa_imu(kfpos_handle *h, const int32_t *range_mm, const void *err_est, const void *accel,
+                       const void *cov, const double *dt, int32_t dt_len, uint32_t *status) {
+    return round_host(h, "kfpos_step_toa_imu", ROUND_FUSED, 0, false, nullptr, 0, {range_mm, err_est, accel, cov, nullptr}, dt, dt_len, status);
 }
 
 int kfpos_get_height(kfpos_handle *h, double *z) {
@@ -986,138 +810,59 @@ int kfpos_set_height(kfpos_handle *h, const double *z) {
     return KFPOS_OK;
 }
 
-int kfpos_step_toa_imu(kfpos_handle *h, const int32_t *range_mm, const void *err_est, const void *accel,
-                       const void *cov, const double *dt, int32_t dt_len, uint32_t *status) {
-    g_err.clear();
-    if (!h || !range_mm || !err_est || !accel || !cov) return KFPOS_ERR_ARG;
+/* getPose (pos, cov3x3, vel) or the predicted state (x, P) of the whole bank: out[k] = the caller's k-th array (null = not
+ * wanted), dt validated by the caller. The results sit behind one another in the mapped block's output region, getPose's
+ * 15 rows first; staged, getPose's in d_out and the predicted state in the staging area -- reserved together with their
+ * row-major turns, so that no region moves while another is in use. */
+static int pose_host(kfpos_handle *h, const double *dt, int32_t dt_len, bool predicted, double *const out[3],
+                     uint32_t *status) {
     DevScope dev_(h->cfg.device);
-    if (h->cfg.model != KFPOS_MODEL_TOA_IMU) return KFPOS_ERR_MODEL;
-    if (!h->have_anchors) return KFPOS_ERR_STATE;
-    const double *d_dt;
-    double shared;
+    const size_t T = h->cfg.n_tags, n = h->n;
+    const size_t w[3] = {predicted ? n : 3, predicted ? n * n : 9, predicted ? 0 : (size_t)3};
     int rc = drain_slots(h);
     if (rc) return rc;
-    if (h->sm_h) {
-        if ((rc = small_dt(h, dt, dt_len, &d_dt, &shared))) return rc;
-        small_in(h, h->sm_ranges, range_mm, h->cfg.max_anchors, sizeof(int32_t));
-        small_in(h, h->sm_err, err_est, h->cfg.max_anchors, h->msz);
-        small_in(h, h->sm_accel, accel, 3, h->msz);
-        small_in(h, h->sm_cov, cov, 9, h->msz);
-        if ((rc = kfpos_step_toa_imu_dev(h, (const int32_t *)(h->sm_d + h->sm_ranges), h->sm_d + h->sm_err,
-                                         h->sm_d + h->sm_accel, h->sm_d + h->sm_cov, 1, d_dt, shared,
-                                         (uint32_t *)(h->sm_d + h->sm_status), nullptr)))
-            return rc;
-        return small_finish(h, status);
+    Route rt = route_of(h);
+    const Place p_dt = {h->sm.dt, h->d_dt, nullptr}, p_status = {h->sm.status, h->d_status, nullptr};
+    if (predicted && (rc = rt.reserve(2 * (n + n * n) * T * sizeof(double) + 1024))) return rc;
+    double *d[3];
+    for (size_t k = 0, off = predicted ? 15 * T : 0; k < 3; off += w[k++] * T) {
+        Place p = {h->sm.out + off * sizeof(double), h->d_out + off, nullptr};
+        if (predicted && (rc = rt.region(w[k] * T * sizeof(double), p))) return rc;
+        d[k] = (double *)rt.at(p);
     }
-    stage_reset(h);
-    if ((rc = stage_dt(h, dt, dt_len, &d_dt, &shared))) return rc;
-    if ((rc = stage_in(h, h->d_ranges, range_mm, h->cfg.max_anchors, sizeof(int32_t)))) return rc;
-    if ((rc = stage_in(h, h->d_err, err_est, h->cfg.max_anchors, h->msz))) return rc;
-    if ((rc = stage_in(h, h->d_accel, accel, 3, h->msz))) return rc;
-    if ((rc = stage_in(h, h->d_cov, cov, 9, h->msz))) return rc;
-    if ((rc = kfpos_step_toa_imu_dev(h, h->d_ranges, h->d_err, h->d_accel, h->d_cov, 1, d_dt, shared,
-                                     h->d_status, nullptr)))
-        return rc;
-    return fetch_status(h, status);
-}
-
-static int get_pose_host(kfpos_handle *h, double dt_ahead, const double *dt_each, double *pos, double *cov3x3,
-                         double *vel, uint32_t *status) {
-    if (!h) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    const size_t T = h->cfg.n_tags;
-    int rc0 = drain_slots(h);
-    if (rc0) return rc0;
-    if (h->sm_h) {
-        const double *d_each = nullptr;
-        if (dt_each) {
-            std::memcpy(h->sm_h + h->sm_dt, dt_each, sizeof(double) * T);
-            d_each = (const double *)(h->sm_d + h->sm_dt);
-        }
-        double *o = (double *)(h->sm_d + h->sm_out);
-        const int rc = launch_pose(h, dt_ahead, d_each, o, o + 3 * T, o + 12 * T, (uint32_t *)(h->sm_d + h->sm_status), nullptr);
-        if (rc) return rc;
-        if ((rc0 = small_finish(h, status))) return rc0;
-        if (pos) small_out(h, pos, 0, 3);
-        if (cov3x3) small_out(h, cov3x3, 3 * T, 9);
-        if (vel) small_out(h, vel, 12 * T, 3);
-        return KFPOS_OK;
-    }
-    stage_reset(h);
-    double *dp = h->d_out, *dc = h->d_out + 3 * T, *dv = h->d_out + 12 * T;
-    const double *d_each = nullptr;
-    if (dt_each) {
-        HIPCHK(hipMemcpy(h->d_dt, dt_each, sizeof(double) * T, hipMemcpyHostToDevice));
-        d_each = h->d_dt;
-    }
-    int rc = launch_pose(h, dt_ahead, d_each, dp, dc, dv, h->d_status, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    if (pos && (rc = stage_out(h, pos, dp, 3))) return rc;
-    if (cov3x3 && (rc = stage_out(h, cov3x3, dc, 9))) return rc;
-    if (vel && (rc = stage_out(h, vel, dv, 3))) return rc;
-    if (status) HIPCHK(hipMemcpy(status, h->d_status, sizeof(uint32_t) * T, hipMemcpyDeviceToHost));
-    return KFPOS_OK;
+    const double *d_each;
+    if ((rc = rt.dt_in(dt, dt_len, T, p_dt, &d_each))) return rc;
+    uint32_t *d_status = (uint32_t *)rt.at(p_status);
+    rc = predicted ? launch_pose(h, dt[0], d_each, nullptr, nullptr, nullptr, d_status, nullptr, d[0], d[1])
+                   : launch_pose(h, dt[0], d_each, d[0], d[1], d[2], d_status, nullptr);
+    if (rc || (rc = rt.sync())) return rc;
+    for (int k = 0; k < 3; ++k)
+        if (out[k] && (rc = rt.out(out[k], d[k], T, (int)w[k]))) return rc;
+    return rt.words(status, p_status, T);
 }
 
 int kfpos_get_pose(kfpos_handle *h, double dt_ahead, double *pos, double *cov3x3, double *vel,
                    uint32_t *status) {
     g_err.clear();
-    return get_pose_host(h, dt_ahead, nullptr, pos, cov3x3, vel, status);
+    if (!h) return KFPOS_ERR_ARG;
+    double *const out[3] = {pos, cov3x3, vel};
+    return pose_host(h, &dt_ahead, 1, false, out, status);
 }
 
 int kfpos_get_pose_each(kfpos_handle *h, const double *dt_ahead, double *pos, double *cov3x3, double *vel,
                         uint32_t *status) {
     g_err.clear();
-    if (!dt_ahead) return KFPOS_ERR_ARG;
-    return get_pose_host(h, 0.0, dt_ahead, pos, cov3x3, vel, status);
+    if (!dt_ahead || !h) return KFPOS_ERR_ARG;
+    double *const out[3] = {pos, cov3x3, vel};
+    return pose_host(h, dt_ahead, h->cfg.n_tags, false, out, status);
 }
 
 int kfpos_get_predicted(kfpos_handle *h, const double *dt_ahead, int32_t dt_len, double *x, double *P,
                         uint32_t *status) {
     g_err.clear();
     if (!h || !dt_ahead || !x || !P || (dt_len != 1 && dt_len != h->cfg.n_tags)) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    const size_t T = h->cfg.n_tags, n = h->n;
-    int rc0 = drain_slots(h);
-    if (rc0) return rc0;
-    if (h->sm_h) {
-        const double *d_each = nullptr;
-        if (dt_len > 1) {
-            std::memcpy(h->sm_h + h->sm_dt, dt_ahead, sizeof(double) * T);
-            d_each = (const double *)(h->sm_d + h->sm_dt);
-        }
-        double *o = (double *)(h->sm_d + h->sm_out) + 15 * T;
-        if ((rc0 = launch_pose(h, dt_ahead[0], d_each, nullptr, nullptr, nullptr, (uint32_t *)(h->sm_d + h->sm_status),
-                               nullptr, o, o + n * T)))
-            return rc0;
-        if ((rc0 = small_finish(h, status))) return rc0;
-        small_out(h, x, 15 * T, (int)n);
-        small_out(h, P, 15 * T + n * T, (int)(n * n));
-        return KFPOS_OK;
-    }
-    stage_reset(h);
-    /* component-major results + their row-major turn, all from the staging area: reserve the lot first so that no
-     * region moves while another is in use */
-    const size_t bx = n * T * sizeof(double), bP = n * n * T * sizeof(double);
-    void *probe = nullptr;
-    int rc = stage_region(h, 2 * (bx + bP) + 1024, &probe);
-    if (rc) return rc;
-    stage_reset(h);
-    void *vx = nullptr, *vP = nullptr;
-    if ((rc = stage_region(h, bx, &vx)) || (rc = stage_region(h, bP, &vP))) return rc;
-    double *dx = (double *)vx, *dP = (double *)vP;
-    const double *d_each = nullptr;
-    if (dt_len > 1 || T == 1) {
-        HIPCHK(hipMemcpy(h->d_dt, dt_ahead, sizeof(double) * T, hipMemcpyHostToDevice));
-        d_each = h->d_dt;
-    }
-    if ((rc = launch_pose(h, dt_ahead[0], d_each, nullptr, nullptr, nullptr, h->d_status, nullptr, dx, dP))) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    if ((rc = stage_out(h, x, dx, (int)n))) return rc;
-    if ((rc = stage_out(h, P, dP, (int)(n * n)))) return rc;
-    if (status) HIPCHK(hipMemcpy(status, h->d_status, sizeof(uint32_t) * T, hipMemcpyDeviceToHost));
-    return KFPOS_OK;
+    double *const out[3] = {x, P, nullptr};
+    return pose_host(h, dt_ahead, dt_len, true, out, status);
 }
 
 int kfpos_get_state(kfpos_handle *h, double *x, double *P, uint32_t *flags) {
@@ -1242,8 +987,8 @@ int kfpos_get_latch(kfpos_handle *h, double *latch) {
     HIPCHK(hipDeviceSynchronize());
     stage_reset(h);
     const size_t T = h->cfg.n_tags;
-    if (L == LATCH_ROWS) return stage_out(h, latch, h->d_latch, LATCH_ROWS);
-    if (L == 3) return stage_out(h, latch, h->d_vel, 3); /* ALGORITHM_ML: _previousEstimation, the seed of every solve */
+    if (L == LATCH_ROWS) return stage_out(h, latch, h->d_latch, T, LATCH_ROWS);
+    if (L == 3) return stage_out(h, latch, h->d_vel, T, 3); /* ALGORITHM_ML: _previousEstimation, the seed of every solve */
     /* 9-state: acceleration [3][T] and the lower triangle {00,10,11,20,21,22} [6][T], kfpos_real */
     std::vector<unsigned char> a(3 * T * h->msz), c(6 * T * h->msz);
     HIPCHK(hipMemcpy(a.data(), h->d_imu_acc, a.size(), hipMemcpyDeviceToHost));
@@ -1270,8 +1015,8 @@ int kfpos_set_latch(kfpos_handle *h, const double *latch) {
     HIPCHK(hipDeviceSynchronize());
     stage_reset(h);
     const size_t T = h->cfg.n_tags;
-    if (L == LATCH_ROWS) return stage_in(h, h->d_latch, latch, LATCH_ROWS, sizeof(double));
-    if (L == 3) return stage_in(h, h->d_vel, latch, 3, sizeof(double));
+    if (L == LATCH_ROWS) return stage_in(h, h->d_latch, latch, T, LATCH_ROWS, sizeof(double));
+    if (L == 3) return stage_in(h, h->d_vel, latch, T, 3, sizeof(double));
     std::vector<unsigned char> a(3 * T * h->msz), c(6 * T * h->msz);
     auto wr = [&](std::vector<unsigned char> &b, size_t k, double v) {
         if (h->msz == 4) ((float *)b.data())[k] = (float)v;
@@ -1406,49 +1151,6 @@ static void tag_fresh(const kfpos_handle *h, kfpos_k::TagArgs &a) {
     a.n_comp = c;
 }
 
-/* Staging of the per-tag calls: the small bank's mapped block (the kernel reads and writes host memory in place), or
- * one region of the device staging area filled and emptied with plain copies. Sized for n records of `rec` bytes, at most
- * TAGS_STAGE_MAX: longer lists go through it in chunks of `chunk` (>= 1) records. */
-struct TagStage {
-    unsigned char *dev = nullptr, *host = nullptr; /* host != null: mapped */
-    size_t chunk = 0; /* records it holds */
-};
-static constexpr size_t TAGS_STAGE_MAX = (size_t)16 << 20;
-static int tag_stage(kfpos_handle *h, size_t rec, size_t n, TagStage &st) {
-    size_t cap = h->sm_bytes;
-    if (h->sm_h) {
-        st.dev = h->sm_d;
-        st.host = h->sm_h;
-    } else {
-        stage_reset(h);
-        cap = rec * n < TAGS_STAGE_MAX ? rec * n : TAGS_STAGE_MAX;
-        void *p = nullptr;
-        const int rc = stage_region(h, cap, &p);
-        if (rc) return rc;
-        st.dev = (unsigned char *)p;
-    }
-    st.chunk = cap / rec;
-    if (st.chunk == 0) { /* (a loop over chunks of nothing would never end) */
-        g_err = "per-tag staging holds less than one tag";
-        return KFPOS_ERR_STATE;
-    }
-    return KFPOS_OK;
-}
-static hipError_t tag_up(const TagStage &st, size_t off, const void *src, size_t bytes) {
-    if (st.host) {
-        std::memcpy(st.host + off, src, bytes);
-        return hipSuccess;
-    }
-    return hipMemcpy(st.dev + off, src, bytes, hipMemcpyHostToDevice);
-}
-static hipError_t tag_down(const TagStage &st, void *dst, size_t off, size_t bytes) {
-    if (st.host) {
-        std::memcpy(dst, st.host + off, bytes);
-        return hipSuccess;
-    }
-    return hipMemcpy(dst, st.dev + off, bytes, hipMemcpyDeviceToHost);
-}
-
 /* get (STORE = false) / set (STORE = true) of the listed tags; the host pointers of absent parts are null, and a
  * store only ever reads the caller's arrays */
 extern "C++" template <bool STORE>
@@ -1469,22 +1171,22 @@ static int tags_transfer(kfpos_handle *h, const int32_t *rows, int32_t n,
     if (wsum == 0 && !flags) return KFPOS_OK;
     /* per listed tag: its values (doubles), its flags word, its row index */
     const size_t rec = wsum * sizeof(double) + sizeof(uint32_t) + sizeof(int32_t);
-    TagStage st;
-    const int rc = tag_stage(h, rec, (size_t)n, st);
+    Route st = route_of(h);
+    const int rc = st.block(rec, (size_t)n);
     if (rc) return rc;
     const size_t chunk = st.chunk;
     for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
         const size_t m = (size_t)n - c0 < chunk ? (size_t)n - c0 : chunk;
         const size_t off_fl = m * wsum * sizeof(double), off_rows = off_fl + m * sizeof(uint32_t);
-        HIPCHK(tag_up(st, off_rows, rows + c0, m * sizeof(int32_t)));
+        HIPCHK(st.up(off_rows, rows + c0, m * sizeof(int32_t)));
         if constexpr (store) {
             size_t off = 0;
             for (int s = 0; s < kfpos_k::TAG_SECTIONS; ++s) {
                 if (!a.w[s]) continue;
-                HIPCHK(tag_up(st, off, part[s] + c0 * width[s], m * width[s] * sizeof(double)));
+                HIPCHK(st.up(off, part[s] + c0 * width[s], m * width[s] * sizeof(double)));
                 off += m * width[s] * sizeof(double);
             }
-            if (flags) HIPCHK(tag_up(st, off_fl, flags + c0, m * sizeof(uint32_t)));
+            if (flags) HIPCHK(st.up(off_fl, flags + c0, m * sizeof(uint32_t)));
         }
         a.n = (int)m;
         a.val = (double *)st.dev;
@@ -1497,10 +1199,10 @@ static int tags_transfer(kfpos_handle *h, const int32_t *rows, int32_t n,
             size_t off = 0;
             for (int s = 0; s < kfpos_k::TAG_SECTIONS; ++s) {
                 if (!a.w[s]) continue;
-                HIPCHK(tag_down(st, part[s] + c0 * width[s], off, m * width[s] * sizeof(double)));
+                HIPCHK(st.down(part[s] + c0 * width[s], off, m * width[s] * sizeof(double)));
                 off += m * width[s] * sizeof(double);
             }
-            if (flags) HIPCHK(tag_down(st, flags + c0, off_fl, m * sizeof(uint32_t)));
+            if (flags) HIPCHK(st.down(flags + c0, off_fl, m * sizeof(uint32_t)));
         }
     }
     return KFPOS_OK;
@@ -1565,14 +1267,14 @@ int kfpos_reset_tags(kfpos_handle *h, const int32_t *rows, int32_t n, const doub
     a.cst[4] = h->planar.init_angle;
     /* per listed tag: its start position (if given), its row index */
     const size_t rec = (init_xyz ? 3 * sizeof(double) : 0) + sizeof(int32_t);
-    TagStage st;
-    if ((rc = tag_stage(h, rec, (size_t)n, st))) return rc;
+    Route st = route_of(h);
+    if ((rc = st.block(rec, (size_t)n))) return rc;
     const size_t chunk = st.chunk;
     for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
         const size_t m = (size_t)n - c0 < chunk ? (size_t)n - c0 : chunk;
         const size_t off_rows = init_xyz ? m * 3 * sizeof(double) : 0;
-        HIPCHK(tag_up(st, off_rows, rows + c0, m * sizeof(int32_t)));
-        if (init_xyz) HIPCHK(tag_up(st, 0, init_xyz + c0 * 3, m * 3 * sizeof(double)));
+        HIPCHK(st.up(off_rows, rows + c0, m * sizeof(int32_t)));
+        if (init_xyz) HIPCHK(st.up(0, init_xyz + c0 * 3, m * 3 * sizeof(double)));
         a.n = (int)m;
         a.init = init_xyz ? (const double *)st.dev : nullptr;
         a.rows = (const int32_t *)(st.dev + off_rows);
@@ -1610,8 +1312,8 @@ static int pose_rows_host(kfpos_handle *h, const char *who, const int32_t *rows,
     if (wsum == 0 && !status) return KFPOS_OK;
     /* per entry: its results and its dt (doubles), its status word, its row index */
     const size_t rec = (wsum + (each ? 1 : 0)) * sizeof(double) + sizeof(uint32_t) + sizeof(int32_t);
-    TagStage st;
-    if ((rc = tag_stage(h, rec, (size_t)n, st))) return rc;
+    Route st = route_of(h);
+    if ((rc = st.block(rec, (size_t)n))) return rc;
     kfpos_k::PoseRowsArgs a = {};
     pose_bank_args(h, a.p);
     a.p.dt_ahead = dt_ahead[0];
@@ -1624,8 +1326,8 @@ static int pose_rows_host(kfpos_handle *h, const char *who, const int32_t *rows,
             o += out[k] ? m * w[k] * sizeof(double) : 0;
         }
         const size_t off_dt = o, off_st = off_dt + (each ? m * sizeof(double) : 0), off_rows = off_st + m * sizeof(uint32_t);
-        HIPCHK(tag_up(st, off_rows, rows + c0, m * sizeof(int32_t)));
-        if (each) HIPCHK(tag_up(st, off_dt, dt_ahead + c0, m * sizeof(double)));
+        HIPCHK(st.up(off_rows, rows + c0, m * sizeof(int32_t)));
+        if (each) HIPCHK(st.up(off_dt, dt_ahead + c0, m * sizeof(double)));
         double *d[3];
         for (int k = 0; k < 3; ++k) d[k] = out[k] ? (double *)(st.dev + off[k]) : nullptr;
         if (predicted) {
@@ -1644,8 +1346,8 @@ static int pose_rows_host(kfpos_handle *h, const char *who, const int32_t *rows,
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(nullptr)); /* the staging is free again; a mapped block's results are visible */
         for (int k = 0; k < 3; ++k)
-            if (out[k]) HIPCHK(tag_down(st, out[k] + c0 * w[k], off[k], m * w[k] * sizeof(double)));
-        if (status) HIPCHK(tag_down(st, status + c0, off_st, m * sizeof(uint32_t)));
+            if (out[k]) HIPCHK(st.down(out[k] + c0 * w[k], off[k], m * w[k] * sizeof(double)));
+        if (status) HIPCHK(st.down(status + c0, off_st, m * sizeof(uint32_t)));
     }
     return KFPOS_OK;
 }
@@ -1671,46 +1373,8 @@ int kfpos_get_predicted_rows(kfpos_handle *h, const int32_t *rows, int32_t n, co
  * bank (kfpos_k_tags.hip: k_rows_work), the kernel this handle runs anyway steps that bank with KArgs::T = n, and the
  * result is scattered back. Launches per round: gather + one layout turn per input array (2 for a ranging round, 4 for a
  * fused one, 1 for a sensor sample; none on a small bank's mapped block) + step + scatter. */
-struct RowsLayout {
-    size_t in_bytes; /* one input area (for work_cap tags) and the places inside it */
-    size_t i_rows, i_ranges, i_err, i_accel, i_cov, i_sensor, i_dt, i_status, i_pos;
-    size_t w[kfpos_k::TB_N], w_flags, w_ranges, w_err, w_accel, w_cov, w_sensor; /* the work bank at stride n */
-    size_t total;
-};
-static RowsLayout rows_layout(const kfpos_handle *h, size_t cap, size_t n) {
-    using namespace kfpos_k;
-    RowsLayout L{};
-    const size_t A = h->cfg.max_anchors, m = h->msz, imu = h->n == 9 ? 1 : 0, pl = h->n == 8 ? 1 : 0;
-    size_t off = 0;
-    auto region = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    L.i_rows = region(cap * sizeof(int32_t));
-    L.i_ranges = region(cap * A * sizeof(int32_t));
-    L.i_err = region(cap * A * m);
-    L.i_accel = region(imu * cap * 3 * m);
-    L.i_cov = region(imu * cap * 9 * m);
-    L.i_sensor = region(pl * cap * 24 * sizeof(double));
-    L.i_dt = region(cap * sizeof(double));
-    L.i_status = region(cap * sizeof(uint32_t));
-    L.i_pos = region(cap * 3 * sizeof(double));
-    L.in_bytes = off;
-    off = KFPOS_N_SLOTS * L.in_bytes;
-    L.w[TB_POS] = region(3 * n * sizeof(double));
-    L.w[TB_VEL] = region((h->n == 8 ? 4 : (h->n == 6 ? 0 : 3)) * n * sizeof(double));
-    L.w[TB_P] = region((size_t)h->psz * n * h->rsz);
-    L.w[TB_IMU_ACC] = region(imu * 3 * n * m);
-    L.w[TB_IMU_COV] = region(imu * 6 * n * m);
-    L.w[TB_LATCH] = region(pl * LATCH_ROWS * n * sizeof(double));
-    L.w_flags = region(n * sizeof(uint32_t));
-    L.w_ranges = region(n * A * sizeof(int32_t));
-    L.w_err = region(n * A * m);
-    L.w_accel = region(imu * n * 3 * m);
-    L.w_cov = region(imu * n * 9 * m);
-    L.w_sensor = region(pl * n * 24 * sizeof(double));
-    L.total = off;
-    return L;
-}
 /* room for n listed tags; growing frees the old block, so everything in flight completes first */
-static int rows_reserve(kfpos_handle *h, size_t n) {
+extern "C++" int rows_reserve(kfpos_handle *h, size_t n) {
     if (n <= h->work_cap) return KFPOS_OK;
     size_t cap = n > 2 * h->work_cap ? n : 2 * h->work_cap;
     if (cap > (size_t)h->cfg.n_tags) cap = h->cfg.n_tags;
@@ -1718,13 +1382,13 @@ static int rows_reserve(kfpos_handle *h, size_t n) {
     if (h->d_work) (void)hipFree(h->d_work);
     h->d_work = nullptr;
     h->work_cap = 0;
-    HIPCHK(hipMalloc((void **)&h->d_work, rows_layout(h, cap, cap).total));
+    HIPCHK(hipMalloc((void **)&h->d_work, kfpos_layout::rows_layout(handle_sizes(h), KFPOS_N_SLOTS, cap, cap).total));
     h->work_cap = cap;
     return KFPOS_OK;
 }
 /* tags_check(unique) in O(n) -- a round of the streaming path validates its list on every submission: each row carries
  * the number of the call that last listed it. Same answers, same texts: the first offending entry of the list. */
-static int rows_check(kfpos_handle *h, const char *who, const int32_t *rows, int32_t n) {
+extern "C++" int rows_check(kfpos_handle *h, const char *who, const int32_t *rows, int32_t n) {
     if (n < 0 || (n > 0 && !rows)) return tags_check(h, who, rows, n, true);
     if (h->row_stamp.empty()) h->row_stamp.assign((size_t)h->cfg.n_tags, 0u);
     if (++h->stamp == 0) { /* wrapped: forget every earlier call */
@@ -1739,7 +1403,7 @@ static int rows_check(kfpos_handle *h, const char *who, const int32_t *rows, int
     return KFPOS_OK;
 }
 /* gather -> step -> scatter on stream s. a: fill_args + the inputs of the call at [.][n], status [n], traj [3][n] */
-static int rows_step(kfpos_handle *h, hipStream_t s, const RowsLayout &L, const int32_t *d_rows, int n, KArgs &a) {
+extern "C++" int rows_step(kfpos_handle *h, hipStream_t s, const kfpos_layout::Rows &L, const int32_t *d_rows, int n, KArgs &a) {
     using namespace kfpos_k;
     TagArgs g;
     tag_args(h, g);
@@ -1765,262 +1429,21 @@ static int rows_step(kfpos_handle *h, hipStream_t s, const RowsLayout &L, const 
     return KFPOS_OK;
 }
 
-enum { ROWS_TOA = 0, ROWS_IMU = 1, ROWS_TOA_IMU = 2, ROWS_SENSOR = 3 };
-/* the synchronous row-list calls: what the whole-bank call of the same name does, for the listed tags only */
-static int step_rows_host(kfpos_handle *h, const char *who, int call, const int32_t *rows, int32_t n,
-                          const int32_t *range_mm, const void *err_est, const void *accel, const void *cov,
-                          int32_t sensor_kind, const double *data, const double *dt, int32_t dt_len, uint32_t *status) {
-    g_err.clear();
-    if (!h) return KFPOS_ERR_ARG;
-    const bool rng = call == ROWS_TOA || call == ROWS_TOA_IMU, imu = call == ROWS_IMU || call == ROWS_TOA_IMU;
-    const int C = call == ROWS_SENSOR ? sensor_width(sensor_kind) : 0;
-    if (call == ROWS_SENSOR && C == 0) return KFPOS_ERR_ARG;
-    int rc = rows_check(h, who, rows, n);
-    if (rc) return rc;
-    if (n == 0) return KFPOS_OK;
-    if ((rng && (!range_mm || !err_est)) || (imu && (!accel || !cov)) || (call == ROWS_SENSOR && !data)) return KFPOS_ERR_ARG;
-    if (call == ROWS_TOA_IMU && h->cfg.model != KFPOS_MODEL_TOA_IMU) return KFPOS_ERR_MODEL;
-    if ((call == ROWS_IMU && h->cfg.model != KFPOS_MODEL_TOA_IMU) || (call == ROWS_SENSOR && h->cfg.model != KFPOS_MODEL_PLANAR)) {
-        if (status) std::memset(status, 0, sizeof(uint32_t) * n); /* the reference's empty virtuals */
-        return KFPOS_OK;
-    }
-    if (rng && !h->have_anchors) {
-        g_err = "kfpos_set_anchors has not been called (the node drops ranges until the anchors are known, Posgenerator.cpp:92-96)";
-        return KFPOS_ERR_STATE;
-    }
-    if (!dt || (dt_len != 1 && dt_len != n)) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if ((rc = drain_slots(h))) return rc;
-    if ((rc = rows_reserve(h, (size_t)n))) return rc;
-    const RowsLayout L = rows_layout(h, h->work_cap, (size_t)n);
-    const bool small = h->sm_h != nullptr; /* inputs and status through the mapped block, turned on the CPU */
-    unsigned char *in = h->d_work;         /* input area 0: the slots have been drained */
-    const size_t A = h->cfg.max_anchors, m = h->msz;
-    /* host row-major [n][C] -> device component-major [C][n]; the first HIP error is kept in `he` */
-    hipError_t he = hipSuccess;
-    auto stage = [&](const void *src, int Cc, size_t esz, size_t sm_off, size_t i_off, size_t w_off) -> const void * {
-        if (small) {
-            small_in_n(h, sm_off, src, (size_t)n, Cc, esz);
-            return h->sm_d + sm_off;
-        }
-        if (he == hipSuccess) he = hipMemcpy(in + i_off, src, (size_t)n * Cc * esz, hipMemcpyHostToDevice);
-        kfpos_k::launch_rows_to_cols(esz, nullptr, in + i_off, h->d_work + w_off, n, Cc);
-        if (he == hipSuccess) he = hipGetLastError();
-        return h->d_work + w_off;
-    };
-    KArgs a;
-    fill_args(h, a);
-    const int32_t *d_rows;
-    if (small) {
-        std::memcpy(h->sm_h + h->sm_out, rows, sizeof(int32_t) * n); /* the pose-output region: free during a step */
-        d_rows = (const int32_t *)(h->sm_d + h->sm_out);
-    } else {
-        HIPCHK(hipMemcpy(in + L.i_rows, rows, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-        d_rows = (const int32_t *)(in + L.i_rows);
-    }
-    if (rng) {
-        a.ranges = (const int32_t *)stage(range_mm, (int)A, sizeof(int32_t), h->sm_ranges, L.i_ranges, L.w_ranges);
-        a.err = stage(err_est, (int)A, m, h->sm_err, L.i_err, L.w_err);
-    }
-    if (imu) {
-        a.accel = stage(accel, 3, m, h->sm_accel, L.i_accel, L.w_accel);
-        a.cov = stage(cov, 9, m, h->sm_cov, L.i_cov, L.w_cov);
-    }
-    if (call == ROWS_SENSOR) a.sensor = (const double *)stage(data, C, sizeof(double), h->sm_sensor, L.i_sensor, L.w_sensor);
-    HIPCHK(he);
-    a.dt_shared = dt[0];
-    if (dt_len != 1 || n == 1) {
-        if (small) {
-            std::memcpy(h->sm_h + h->sm_dt, dt, sizeof(double) * n);
-            a.dt = (const double *)(h->sm_d + h->sm_dt);
-        } else {
-            HIPCHK(hipMemcpy(in + L.i_dt, dt, sizeof(double) * n, hipMemcpyHostToDevice));
-            a.dt = (const double *)(in + L.i_dt);
-        }
-    }
-    a.status = small ? (uint32_t *)(h->sm_d + h->sm_status) : (uint32_t *)(in + L.i_status);
-    a.mode = call == ROWS_SENSOR ? sensor_kind : (call == ROWS_TOA ? MODE_TOA : (call == ROWS_IMU ? MODE_IMU_ONLY : MODE_FUSED));
-    a.latch = 1;
-    rc = rows_step(h, nullptr, L, d_rows, n, a);
-    if (call == ROWS_SENSOR) h->planar_sensors = true; /* ranging epochs now carry the latched samples */
-    if (rc) return rc;
-    if (small) {
-        HIPCHK(hipStreamSynchronize(nullptr));
-        if (status) std::memcpy(status, h->sm_h + h->sm_status, sizeof(uint32_t) * n);
-        return KFPOS_OK;
-    }
-    HIPCHK(hipDeviceSynchronize());
-    if (status) HIPCHK(hipMemcpy(status, in + L.i_status, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-    return KFPOS_OK;
-}
-
 int kfpos_step_toa_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const int32_t *range_mm, const void *err_est,
                         const double *dt, int32_t dt_len, uint32_t *status) {
-    return step_rows_host(h, "kfpos_step_toa_rows", ROWS_TOA, rows, n, range_mm, err_est, nullptr, nullptr, 0, nullptr, dt, dt_len, status);
+    return round_host(h, "kfpos_step_toa_rows", ROUND_TOA, 0, true, rows, n, {range_mm, err_est, nullptr, nullptr, nullptr}, dt, dt_len, status);
 }
 int kfpos_step_imu_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const void *accel, const void *cov,
                         const double *dt, int32_t dt_len, uint32_t *status) {
-    return step_rows_host(h, "kfpos_step_imu_rows", ROWS_IMU, rows, n, nullptr, nullptr, accel, cov, 0, nullptr, dt, dt_len, status);
+    return round_host(h, "kfpos_step_imu_rows", ROUND_IMU, 0, true, rows, n, {nullptr, nullptr, accel, cov, nullptr}, dt, dt_len, status);
 }
 int kfpos_step_toa_imu_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const int32_t *range_mm, const void *err_est,
                             const void *accel, const void *cov, const double *dt, int32_t dt_len, uint32_t *status) {
-    return step_rows_host(h, "kfpos_step_toa_imu_rows", ROWS_TOA_IMU, rows, n, range_mm, err_est, accel, cov, 0, nullptr, dt, dt_len, status);
+    return round_host(h, "kfpos_step_toa_imu_rows", ROUND_FUSED, 0, true, rows, n, {range_mm, err_est, accel, cov, nullptr}, dt, dt_len, status);
 }
 int kfpos_step_sensor_rows(kfpos_handle *h, const int32_t *rows, int32_t n, int32_t kind, const double *data,
                            const double *dt, int32_t dt_len, uint32_t *status) {
-    return step_rows_host(h, "kfpos_step_sensor_rows", ROWS_SENSOR, rows, n, nullptr, nullptr, nullptr, nullptr, kind, data, dt, dt_len, status);
-}
-
-int kfpos_slot_acquire_rows(kfpos_handle *h, int32_t slot, kfpos_rows_slot *out) {
-    g_err.clear();
-    if (!h || !out || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    const int rc = slots_init(h);
-    if (rc) return rc;
-    auto &sl = h->slot[slot];
-    if (!sl.rows) HIPCHK(hipHostMalloc((void **)&sl.rows, sizeof(int32_t) * h->cfg.n_tags, hipHostMallocDefault));
-    if (sl.busy) {
-        HIPCHK(hipEventSynchronize(sl.done));
-        sl.busy = false;
-    }
-    out->rows = sl.rows;
-    out->range_mm = (int32_t *)(sl.host + h->so_ranges);
-    out->err_est = sl.host + h->so_err;
-    out->accel = sl.host + h->so_accel;
-    out->cov = sl.host + h->so_cov;
-    out->dt = (double *)(sl.host + h->so_dt);
-    out->status = (uint32_t *)(sl.host + h->so_status);
-    out->pos = (double *)(sl.host + h->so_pos);
-    out->capacity = h->cfg.n_tags;
-    return KFPOS_OK;
-}
-
-int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t n, double dt_shared) {
-    g_err.clear();
-    if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    auto &sl = h->slot[slot];
-    if (!h->s_copy || sl.busy || !sl.rows) {
-        g_err = "kfpos_slot_submit_rows: acquire the slot first (kfpos_slot_acquire_rows)";
-        return KFPOS_ERR_STATE;
-    }
-    const int kind = flags & 0xff;
-    if (kind != KFPOS_SLOT_TOA && kind != KFPOS_SLOT_IMU && kind != KFPOS_SLOT_TOA_IMU) return KFPOS_ERR_ARG;
-    if (flags & (KFPOS_SLOT_REUSE_ERR | KFPOS_SLOT_REUSE_COV)) {
-        g_err = "kfpos_slot_submit_rows: KFPOS_SLOT_REUSE_* belongs to whole-bank rounds (a row-list round brings the listed tags' own values)";
-        return KFPOS_ERR_ARG;
-    }
-    const bool pose_cov = (flags & KFPOS_SLOT_POSE_COV) != 0;
-    if (pose_cov && (flags & KFPOS_SLOT_NO_POSE)) {
-        g_err = "kfpos_slot_submit_rows: KFPOS_SLOT_POSE_COV with KFPOS_SLOT_NO_POSE (a round that returns what is published returns pos)";
-        return KFPOS_ERR_ARG;
-    }
-    if (n > h->cfg.n_tags) {
-        g_err = "kfpos_slot_submit_rows: n exceeds the slot's capacity (n_tags)";
-        return KFPOS_ERR_ARG;
-    }
-    int rc = rows_check(h, "kfpos_slot_submit_rows", sl.rows, n);
-    if (rc) return rc;
-    sl.pose_round = false; /* until this round has enqueued its own (a round that enqueues nothing publishes nothing) */
-    if (n == 0) return KFPOS_OK;
-    if (h->cfg.model == KFPOS_MODEL_PLANAR && kind != KFPOS_SLOT_TOA) return KFPOS_ERR_MODEL; /* its sensors: kfpos_step_sensor_rows */
-    const bool imu9 = h->cfg.model == KFPOS_MODEL_TOA_IMU;
-    if (kind == KFPOS_SLOT_TOA_IMU && !imu9) return KFPOS_ERR_MODEL;
-    const bool has_rng = kind != KFPOS_SLOT_IMU, has_imu = imu9 && kind != KFPOS_SLOT_TOA;
-    if (kind == KFPOS_SLOT_IMU && !imu9) { /* KalmanFilterTOA::newIMUMeasurement is empty */
-        std::memset(sl.host + h->so_status, 0, sizeof(uint32_t) * n);
-        return KFPOS_OK;
-    }
-    if (has_rng && !h->have_anchors) {
-        g_err = "kfpos_set_anchors has not been called";
-        return KFPOS_ERR_STATE;
-    }
-    const size_t cap = h->cfg.n_tags;
-    if (pose_cov && !sl.pose_host) { /* first use of the flag in this slot */
-        HIPCHK(hipHostMalloc((void **)&sl.pose_host, cap * 12 * sizeof(double), hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&sl.pose_dev, cap * 12 * sizeof(double)));
-    }
-    if ((rc = rows_reserve(h, (size_t)n))) return rc;
-    const RowsLayout L = rows_layout(h, h->work_cap, (size_t)n);
-    unsigned char *in = h->d_work + (size_t)slot * L.in_bytes; /* this slot's input area: its last round has completed */
-    const size_t N = (size_t)n, A = h->cfg.max_anchors, m = h->msz;
-    /* 1. the listed tags' records, pinned host -> device on the copy stream: bytes proportional to n. The slot's device
-     * block is not touched: it may hold the errorEstimations / covariance a later whole-bank round reuses */
-    auto up = [&](size_t i_off, const void *src, size_t bytes) {
-        return hipMemcpyAsync(in + i_off, src, bytes, hipMemcpyHostToDevice, h->s_copy);
-    };
-    HIPCHK(up(L.i_rows, sl.rows, N * sizeof(int32_t)));
-    if (has_rng) {
-        HIPCHK(up(L.i_ranges, sl.host + h->so_ranges, N * A * sizeof(int32_t)));
-        HIPCHK(up(L.i_err, sl.host + h->so_err, N * A * m));
-    }
-    if (has_imu) {
-        HIPCHK(up(L.i_accel, sl.host + h->so_accel, N * 3 * m));
-        HIPCHK(up(L.i_cov, sl.host + h->so_cov, N * 9 * m));
-    }
-    if (flags & KFPOS_SLOT_DT_PER_TAG) HIPCHK(up(L.i_dt, sl.host + h->so_dt, N * sizeof(double)));
-    HIPCHK(hipEventRecord(sl.copied, h->s_copy));
-    /* 2. turn, gather, step, scatter on the compute stream, in submission order with the whole-bank rounds */
-    HIPCHK(hipStreamWaitEvent(h->s_comp, sl.copied, 0));
-    KArgs a;
-    fill_args(h, a);
-    auto turn = [&](size_t i_off, size_t w_off, int Cc, size_t esz) -> const void * {
-        kfpos_k::launch_rows_to_cols(esz, h->s_comp, in + i_off, h->d_work + w_off, n, Cc);
-        return h->d_work + w_off;
-    };
-    if (has_rng) {
-        a.ranges = (const int32_t *)turn(L.i_ranges, L.w_ranges, (int)A, sizeof(int32_t));
-        a.err = turn(L.i_err, L.w_err, (int)A, m);
-    }
-    if (has_imu) {
-        a.accel = turn(L.i_accel, L.w_accel, 3, m);
-        a.cov = turn(L.i_cov, L.w_cov, 9, m);
-    }
-    HIPCHK(hipGetLastError());
-    a.mode = kind == KFPOS_SLOT_TOA ? MODE_TOA : (kind == KFPOS_SLOT_IMU ? MODE_IMU_ONLY : MODE_FUSED);
-    a.latch = 1;
-    a.dt = (flags & KFPOS_SLOT_DT_PER_TAG) ? (const double *)(in + L.i_dt) : nullptr;
-    a.dt_shared = dt_shared;
-    a.status = (uint32_t *)(in + L.i_status);
-    const bool want_pose = !(flags & KFPOS_SLOT_NO_POSE);
-    a.traj = want_pose ? (double *)(in + L.i_pos) : nullptr;
-    if ((rc = rows_step(h, h->s_comp, L, (const int32_t *)(in + L.i_rows), n, a))) return rc;
-    if (pose_cov) { /* what is published for the round's tags: getPose at timeLag 0 of the bank the scatter just wrote */
-        kfpos_k::PoseRowsArgs g = {};
-        pose_bank_args(h, g.p);
-        g.p.cov = sl.pose_dev;
-        g.p.vel = sl.pose_dev + cap * 9;
-        g.rows = (const int32_t *)(in + L.i_rows);
-        g.n = n;
-        kfpos_k::launch_get_pose_rows(h->cfg.model, h->full != 0, h->cfg.storage, h->s_comp, g);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(sl.computed, h->s_comp));
-    /* 3. status [n] and pos [3][n] back */
-    HIPCHK(hipStreamWaitEvent(h->s_back, sl.computed, 0));
-    HIPCHK(hipMemcpyAsync(sl.host + h->so_status, in + L.i_status, N * sizeof(uint32_t), hipMemcpyDeviceToHost, h->s_back));
-    if (want_pose) HIPCHK(hipMemcpyAsync(sl.host + h->so_pos, in + L.i_pos, N * 3 * sizeof(double), hipMemcpyDeviceToHost, h->s_back));
-    if (pose_cov) { /* cov3x3 [n][9], vel [n][3] behind them */
-        HIPCHK(hipMemcpyAsync(sl.pose_host, sl.pose_dev, N * 9 * sizeof(double), hipMemcpyDeviceToHost, h->s_back));
-        HIPCHK(hipMemcpyAsync(sl.pose_host + cap * 9, sl.pose_dev + cap * 9, N * 3 * sizeof(double), hipMemcpyDeviceToHost, h->s_back));
-    }
-    HIPCHK(hipEventRecord(sl.done, h->s_back));
-    sl.busy = true;
-    sl.pose_round = pose_cov;
-    return KFPOS_OK;
-}
-
-int kfpos_slot_pose_rows(kfpos_handle *h, int32_t slot, double **cov3x3, double **vel) {
-    g_err.clear();
-    if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
-    const auto &sl = h->slot[slot];
-    if (!sl.pose_round) {
-        g_err = "kfpos_slot_pose_rows: the slot's last row-list round did not carry KFPOS_SLOT_POSE_COV";
-        return KFPOS_ERR_STATE;
-    }
-    if (cov3x3) *cov3x3 = sl.pose_host;
-    if (vel) *vel = sl.pose_host + (size_t)h->cfg.n_tags * 9;
-    return KFPOS_OK;
+    return round_host(h, "kfpos_step_sensor_rows", ROUND_SENSOR, kind, true, rows, n, {nullptr, nullptr, nullptr, nullptr, data}, dt, dt_len, status);
 }
 
 int kfpos_timing_begin(kfpos_handle *h, void *stream) {

@@ -1,7 +1,7 @@
 /*
  * kfpos_internal.h -- what the translation units of libkfpos_hip.so share and the ABI does not show: the handle.
- * (kfpos_k_*.hip: the kernels; kfpos_hip.hip: host side and filter entry points; kfpos_hip_replay.hip: the replay entry
- * points, kfpos_run_*_dev; kfpos_comm.hip: the RCCL pose gather.)
+ * (kfpos_k_*.hip: the kernels; kfpos_hip.hip: host side and filter entry points; kfpos_hip_slots.hip: the streaming
+ * slots, kfpos_slot_*; kfpos_hip_replay.hip: the replay entry points, kfpos_run_*_dev; kfpos_comm.hip: the RCCL pose gather.)
  */
 #ifndef KFPOS_INTERNAL_H
 #define KFPOS_INTERNAL_H
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/kfpos.h"
+#include "kfpos_host_layout.h"
 
 #define KFPOS_TRACE_CHUNK 128 /* epochs per multi-epoch launch (their dt values travel in the kernel arguments) */
 #define KFPOS_N_SLOTS 3       /* streaming host API: one slot being filled, one on the bus, one computing / returning */
@@ -73,8 +74,7 @@ struct kfpos_handle {
      * input and output of a host-API call in component-major form; the kernels read and write it in place over the
      * bus, so a call is "turn the layout on the CPU, launch, synchronise" -- no hipMemcpy, no layout kernels */
     unsigned char *sm_h = nullptr, *sm_d = nullptr;
-    size_t sm_ranges = 0, sm_err = 0, sm_accel = 0, sm_cov = 0, sm_dt = 0, sm_sensor = 0, sm_status = 0, sm_out = 0;
-    size_t sm_bytes = 0; /* the whole block: nothing in it outlives a call, so the per-tag accessors stage through all of it */
+    kfpos_layout::Mapped sm = {}; /* sm.bytes, the whole block: nothing in it outlives a call, so the per-tag accessors stage through all of it */
     /* streaming host API: KFPOS_N_SLOTS slots of pinned host + device buffers, three streams (kfpos_slot_*) */
     struct Slot {
         unsigned char *host = nullptr; /* pinned block: ranges | err | accel | cov | dt | status | pos */
@@ -90,7 +90,7 @@ struct kfpos_handle {
         double *pose_host = nullptr, *pose_dev = nullptr;
         bool pose_round = false;
     } slot[KFPOS_N_SLOTS];
-    size_t so_ranges = 0, so_err = 0, so_accel = 0, so_cov = 0, so_dt = 0, so_status = 0, so_pos = 0, so_bytes = 0;
+    kfpos_layout::Slot so = {};
     hipStream_t s_copy = nullptr, s_copy2 = nullptr, s_comp = nullptr, s_back = nullptr;
     size_t split_bytes = 0;                            /* H2D copies from this size on travel as two halves on two streams */
     int err_slot = -1, cov_slot = -1;                  /* which slot's device block holds the current err / cov */

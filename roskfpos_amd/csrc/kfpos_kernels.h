@@ -1,8 +1,8 @@
 /*
  * kfpos_kernels.h -- what the kernel translation units of libkfpos_hip.so share: the kernel-argument blocks, the
  * device-side helpers that stage an epoch (component-major HBM -> registers / LDS), and the selector functions through
- * which the host side (kfpos_hip.hip, kfpos_hip_replay.hip) obtains a kernel without seeing its template, and what those
- * two host units share among themselves (at the end of namespace kfpos_k's declarations).
+ * which the host side (kfpos_hip.hip, kfpos_hip_slots.hip, kfpos_hip_replay.hip) obtains a kernel without seeing its template, and what those
+ * host units share among themselves (at the end of namespace kfpos_k's declarations).
  *
  * Execution model: ONE FILTER PER LANE, 64 filters per wavefront, one wavefront per workgroup.
  *  - The whole per-tag state (position, velocity, packed covariance: 21 / 36 / 45 doubles) lives in
@@ -26,7 +26,7 @@
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
  * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
- * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
+ * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_hip_slots (the streaming slots of the C ABI, kfpos_slot_*), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
 #define KFPOS_KERNELS_H
@@ -211,7 +211,7 @@ struct TagComp {
     uint8_t kind, buf, row, aux;
 };
 enum : int { TC_NONE = 0, TC_F64 = 1, TC_COV = 2, TC_REAL = 3 };                 /* double / stored covariance entry / kfpos_real */
-enum : int { TB_POS = 0, TB_VEL, TB_P, TB_IMU_ACC, TB_IMU_COV, TB_LATCH, TB_N }; /* TagArgs::buf */
+/* TB_* (TB_POS ... TB_LATCH, TB_N), the indices into TagArgs::buf: kfpos_host_layout.h */
 enum : int { TAGS_GATHER = 0, TAGS_SCATTER = 1, TAGS_RESET = 2, TAGS_WORK_IN = 3, TAGS_WORK_OUT = 4 };
 constexpr int TAG_SECTIONS = 4;            /* x | P | latch | height */
 constexpr int TAG_COMPS = 9 + 81 + 15 + 1; /* the longest record: no model has all of them at once */
@@ -239,12 +239,46 @@ void launch_tags(int op, int st, hipStream_t s, const TagArgs &a);          /* k
 constexpr int COOP_LANES = 8;                   /* kfpos_k_coop.hip: one tag per group of 8 lanes */
 constexpr int COOP_TAGS_PER_WAVE = 64 / COOP_LANES;
 constexpr int PLANAR_HAS_SHIFT = 4;              /* planar flags word: bits 5..7 = latched PX4Flow / IMU / magnetometer */
-constexpr int LATCH_ROWS = 15;
+/* LATCH_ROWS: kfpos_host_layout.h */
 
 } // namespace kfpos_k
 
-/* ---- what the two host units share: defined in kfpos_hip.hip, used by kfpos_hip_replay.hip as well ---- */
+/* ---- what the host units share: defined in kfpos_hip.hip unless noted, used by kfpos_hip_replay.hip and
+ * kfpos_hip_slots.hip as well ---- */
 #define KFPOS_HIDDEN __attribute__((visibility("hidden")))
+/* A round: what one call feeds the bank. ROUND_TOA / _IMU / _FUSED are KFPOS_SLOT_TOA / _IMU / _TOA_IMU and the
+ * MODE_* of the step kernels; ROUND_SENSOR carries a KFPOS_SENSOR_* kind beside it. */
+enum : int { ROUND_TOA = 0, ROUND_IMU = 1, ROUND_FUSED = 2, ROUND_SENSOR = 3 };
+constexpr int ROUND_EMPTY = -1; /* Round::answer (no KFPOS_* code): one of the reference's empty virtuals -- n zero status words, KFPOS_OK */
+struct Round {
+    int answer;            /* KFPOS_OK: proceed; ROUND_EMPTY; KFPOS_ERR_ARG (no such kind), _MODEL, _STATE (anchors) */
+    bool has_rng, has_imu; /* the inputs the kind carries, whatever the answer */
+    int width, mode;       /* values per tag of a sensor sample (0: not a sensor round); KArgs::mode */
+};
+struct RoundIn { /* the inputs of a round, component-major device pointers */
+    const int32_t *ranges;
+    const void *err, *accel, *cov;
+    const double *sensor;
+};
+/* may this handle take this kind of round? slot: a streaming round (no sensor kinds; a planar bank takes ranging only) */
+KFPOS_HIDDEN Round round_check(const kfpos_handle *h, int kind, int32_t sensor_kind, bool slot);
+KFPOS_HIDDEN int round_refusal(int answer); /* KFPOS_ERR_MODEL / _STATE as the call's return value, with the anchors text */
+/* fill_args + the round's part of the argument block (latch = 1) */
+KFPOS_HIDDEN void round_args(const kfpos_handle *h, const Round &r, const RoundIn &in, const double *dt, double dt_shared,
+                             uint32_t *status, double *traj, kfpos_k::KArgs &a);
+KFPOS_HIDDEN int drain_slots(kfpos_handle *h); /* kfpos_hip_slots.hip: wait for whatever the slots still have in flight */
+/* row-list rounds, synchronous and streaming: the list's check (rows inside the bank, none twice), room for n listed tags
+ * in the work block, and gather -> step -> scatter on stream s (a: round_args with the inputs at [.][n]) */
+KFPOS_HIDDEN int rows_check(kfpos_handle *h, const char *who, const int32_t *rows, int32_t n);
+KFPOS_HIDDEN int rows_reserve(kfpos_handle *h, size_t n);
+KFPOS_HIDDEN int rows_step(kfpos_handle *h, hipStream_t s, const kfpos_layout::Rows &L, const int32_t *d_rows, int n, kfpos_k::KArgs &a);
+KFPOS_HIDDEN void pose_bank_args(const kfpos_handle *h, kfpos_k::PoseArgs &a); /* the bank as the pose kernels read it */
+inline kfpos_layout::Sizes handle_sizes(const kfpos_handle *h) {
+    return {(size_t)h->cfg.n_tags, (size_t)h->cfg.max_anchors, (size_t)h->msz, h->n, h->psz, h->rsz};
+}
+inline kfpos_layout::Rows rows_layout(const kfpos_handle *h, size_t n) { /* the work block as it is, n tags listed */
+    return kfpos_layout::rows_layout(handle_sizes(h), KFPOS_N_SLOTS, h->work_cap, n);
+}
 KFPOS_HIDDEN void fill_args(const kfpos_handle *h, kfpos_k::KArgs &a);           /* the handle's part of every argument block */
 KFPOS_HIDDEN int launch_step(kfpos_handle *h, const kfpos_k::KArgs &a, hipStream_t s); /* the step kernel of the handle, a.T tags */
 KFPOS_HIDDEN int static_anchors(const kfpos_handle *h);                          /* anchor-count specialisation: 8, -16 or 0 */
