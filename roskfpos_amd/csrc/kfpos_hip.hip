@@ -1,8 +1,9 @@
 /*
  * kfpos_hip.hip -- host side of libkfpos_hip.so: the handle, launch selection, two of the three ways in
  * (synchronous host-buffer API, device-buffer API) and the C ABI of include/kfpos.h. The kernels live in
- * kfpos_k_*.hip (kfpos_kernels.h says which is where); the streaming slots in kfpos_hip_slots.hip; the replay entry points (kfpos_run_*_dev: whole schedules in few
- * launches) in kfpos_hip_replay.hip; the RCCL pose gather in kfpos_comm.hip.
+ * kfpos_k_*.hip (kfpos_kernels.h says which is where); the state side of the ABI (whole-bank accessors, per-tag lifecycle,
+ * pose for a row list) in kfpos_hip_state.hip; the streaming slots in kfpos_hip_slots.hip; the replay entry points
+ * (kfpos_run_*_dev: whole schedules in few launches) in kfpos_hip_replay.hip; the RCCL pose gather in kfpos_comm.hip.
  */
 #include <algorithm>
 #include <cmath>
@@ -151,9 +152,7 @@ int launch_step(kfpos_handle *h, const KArgs &a, hipStream_t s) {
     return KFPOS_OK;
 }
 
-namespace {
-
-/* a region of the row-major staging area; regions live until the next stage_reset() (start of an API call) */
+/* ---- staging and the route of a host-buffer call: Route, kfpos_kernels.h says what each does ---- */
 int stage_region(kfpos_handle *h, size_t bytes, void **out) {
     bytes = (bytes + 255) & ~(size_t)255;
     if (h->stage_used + bytes > h->stage_cap) {
@@ -171,11 +170,7 @@ int stage_region(kfpos_handle *h, size_t bytes, void **out) {
     h->stage_used += bytes;
     return KFPOS_OK;
 }
-void stage_reset(kfpos_handle *h) { h->stage_used = 0; }
-
-/* host row-major [n][C] -> component-major [C][n] of `esz`-byte elements: one copy (into `landing`, or a region of the
- * staging area) + a device-side turn */
-int stage_in(kfpos_handle *h, void *dst, const void *src, size_t n, int C, size_t esz, void *landing = nullptr) {
+int stage_in(kfpos_handle *h, void *dst, const void *src, size_t n, int C, size_t esz, void *landing) {
     if (C == 1) {
         HIPCHK(hipMemcpy(dst, src, n * esz, hipMemcpyHostToDevice));
         return KFPOS_OK;
@@ -187,7 +182,6 @@ int stage_in(kfpos_handle *h, void *dst, const void *src, size_t n, int C, size_
     HIPCHK(hipGetLastError());
     return KFPOS_OK;
 }
-/* device [C][n] doubles -> host row-major [n][C] */
 int stage_out(kfpos_handle *h, double *dst, const double *dsrc, size_t n, int C) {
     if (C == 1) {
         HIPCHK(hipMemcpy(dst, dsrc, n * sizeof(double), hipMemcpyDeviceToHost));
@@ -201,122 +195,17 @@ int stage_out(kfpos_handle *h, double *dst, const double *dsrc, size_t n, int C)
     HIPCHK(hipMemcpy(dst, rows, n * C * sizeof(double), hipMemcpyDeviceToHost));
     return KFPOS_OK;
 }
-
-size_t small_bank_limit() { /* elements of the range matrix (n_tags x max_anchors) up to which a bank is "small" */
-    const char *e = getenv("KFPOS_SMALL_BANK_ELEMS");
-    return e ? (size_t)atol(e) : 4096;
-}
-template <typename E>
-void rows_to_cols_host(void *dst, const void *src, size_t n, int C) {
-    const E *s = (const E *)src;
-    E *d = (E *)dst;
-    for (size_t t = 0; t < n; ++t)
-        for (int c = 0; c < C; ++c) d[(size_t)c * n + t] = s[t * C + c];
-}
-
-/* ---- the route a host-buffer call takes to the device, chosen once per call ----
- * mapped (small banks, kfpos_handle::sm): inputs and outputs live in one host-pinned, device-mapped block; the CPU turns
- * the layout in place, the kernels read and write host memory over the bus, and the call ends with a synchronisation of
- * the null stream. staged: plain copies into device buffers and a layout kernel per array, ended by a device
- * synchronisation. A call names, per array, where it lives on either route (Place) and uses the operations below; it
- * never asks which route it is on. */
-struct Place {
-    size_t mapped; /* offset in the mapped block */
-    void *dst;     /* staged: the component-major device array ... */
-    void *landing; /* ... and where the row-major copy lands before its turn (null: a region of the staging area) */
-};
-constexpr size_t TAGS_STAGE_MAX = (size_t)16 << 20;
-struct Route {
-    kfpos_handle *h;
-    unsigned char *host, *dev; /* the mapped block (host == null: staged; dev is then the region block() reserved) */
-    size_t chunk;              /* block(): records it holds */
-
-    void *at(const Place &p) const { return host ? dev + p.mapped : p.dst; }
-    /* row-major host array [n][C] of esz-byte elements in, component-major at(p) */
-    int in(const void *src, size_t n, int C, size_t esz, const Place &p) {
-        if (!host) return stage_in(h, p.dst, src, n, C, esz, p.landing);
-        if (esz == 4) rows_to_cols_host<uint32_t>(host + p.mapped, src, n, C);
-        else rows_to_cols_host<uint64_t>(host + p.mapped, src, n, C);
-        return KFPOS_OK;
-    }
-    /* dt of a call, validated: one value (dt_len == 1) travels in the arguments, an array goes up. null = shared */
-    int dt_in(const double *dt, int32_t dt_len, size_t n, const Place &p, const double **d_dt) {
-        *d_dt = dt_len == 1 ? nullptr : (const double *)at(p);
-        return dt_len == 1 ? KFPOS_OK : in(dt, n, 1, sizeof(double), p);
-    }
-    /* component-major doubles [C][n] at device address d (inside a Place of this call) out to row-major host */
-    int out(double *dst, const double *d, size_t n, int C) {
-        if (!host) return stage_out(h, dst, d, n, C);
-        const double *s = (const double *)(host + ((const unsigned char *)d - dev));
-        for (size_t t = 0; t < n; ++t)
-            for (int c = 0; c < C; ++c) dst[t * C + c] = s[(size_t)c * n + t];
-        return KFPOS_OK;
-    }
-    /* the call's launches have completed (a mapped block's results are visible) */
-    int sync() {
-        HIPCHK(host ? hipStreamSynchronize(nullptr) : hipDeviceSynchronize());
-        return KFPOS_OK;
-    }
-    /* n status words delivered, after sync() */
-    int words(uint32_t *status, const Place &p, size_t n) {
-        if (status && host) std::memcpy(status, host + p.mapped, sizeof(uint32_t) * n);
-        else if (status) HIPCHK(hipMemcpy(status, p.dst, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-        return KFPOS_OK;
-    }
-    int finish(uint32_t *status, const Place &p, size_t n) {
-        const int rc = sync();
-        return rc ? rc : words(status, p, n);
-    }
-    /* staged: p.dst = `bytes` of the staging area (reserve() first where several are held at once, so that none moves
-     * while another is in use); mapped: the block has its places already */
-    int reserve(size_t bytes) {
-        void *probe = nullptr;
-        const int rc = host ? KFPOS_OK : stage_region(h, bytes, &probe);
-        if (!host) stage_reset(h);
-        return rc;
-    }
-    int region(size_t bytes, Place &p) { return host ? KFPOS_OK : stage_region(h, bytes, &p.dst); }
-    /* The per-tag calls stage records: the whole mapped block, or one region of the staging area filled and emptied
-     * with plain copies, addressed as dev + offset. Sized for n records of `rec` bytes, at most TAGS_STAGE_MAX: longer
-     * lists go through it in chunks of `chunk` (>= 1) records. */
-    int block(size_t rec, size_t n) {
-        size_t cap = h->sm.bytes;
-        if (!host) {
-            cap = rec * n < TAGS_STAGE_MAX ? rec * n : TAGS_STAGE_MAX;
-            const int rc = stage_region(h, cap, (void **)&dev);
-            if (rc) return rc;
-        }
-        chunk = cap / rec;
-        if (chunk == 0) { /* (a loop over chunks of nothing would never end) */
-            g_err = "per-tag staging holds less than one tag";
-            return KFPOS_ERR_STATE;
-        }
-        return KFPOS_OK;
-    }
-    hipError_t up(size_t off, const void *src, size_t bytes) const {
-        if (!host) return hipMemcpy(dev + off, src, bytes, hipMemcpyHostToDevice);
-        std::memcpy(host + off, src, bytes);
-        return hipSuccess;
-    }
-    hipError_t down(void *dst, size_t off, size_t bytes) const {
-        if (!host) return hipMemcpy(dst, dev + off, bytes, hipMemcpyDeviceToHost);
-        std::memcpy(dst, host + off, bytes);
-        return hipSuccess;
-    }
-};
 Route route_of(kfpos_handle *h) {
     if (!h->sm_h) stage_reset(h);
     return Route{h, h->sm_h, h->sm_h ? h->sm_d : nullptr, 0};
 }
 
-/* packed index of the stored covariance entry (i, j) */
-inline int pidx(const kfpos_handle *h, int i, int j) {
-    if (h->full) return i * h->n + j;
-    const int N = h->n;
-    if (i > j) { const int tt = i; i = j; j = tt; }
-    return i * N - i * (i - 1) / 2 + (j - i);
-}
+namespace {
 
+size_t small_bank_limit() { /* elements of the range matrix (n_tags x max_anchors) up to which a bank is "small" */
+    const char *e = getenv("KFPOS_SMALL_BANK_ELEMS");
+    return e ? (size_t)atol(e) : 4096;
+}
 } // namespace
 
 extern "C" {
@@ -790,26 +679,6 @@ int kfpos_step_toa_imu(kfpos_handle *h, const int32_t *range_mm, const void *err
     return round_host(h, "kfpos_step_toa_imu", ROUND_FUSED, 0, false, nullptr, 0, {range_mm, err_est, accel, cov, nullptr}, dt, dt_len, status);
 }
 
-int kfpos_get_height(kfpos_handle *h, double *z) {
-    g_err.clear();
-    if (!h || !z) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (h->cfg.model != KFPOS_MODEL_PLANAR) return KFPOS_ERR_MODEL;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(z, h->d_pos + 2 * (size_t)h->cfg.n_tags, sizeof(double) * h->cfg.n_tags, hipMemcpyDeviceToHost));
-    return KFPOS_OK;
-}
-
-int kfpos_set_height(kfpos_handle *h, const double *z) {
-    g_err.clear();
-    if (!h || !z) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    if (h->cfg.model != KFPOS_MODEL_PLANAR) return KFPOS_ERR_MODEL;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(h->d_pos + 2 * (size_t)h->cfg.n_tags, z, sizeof(double) * h->cfg.n_tags, hipMemcpyHostToDevice));
-    return KFPOS_OK;
-}
-
 /* getPose (pos, cov3x3, vel) or the predicted state (x, P) of the whole bank: out[k] = the caller's k-th array (null = not
  * wanted), dt validated by the caller. The results sit behind one another in the mapped block's output region, getPose's
  * 15 rows first; staged, getPose's in d_out and the predicted state in the staging area -- reserved together with their
@@ -865,509 +734,6 @@ int kfpos_get_predicted(kfpos_handle *h, const double *dt_ahead, int32_t dt_len,
     return pose_host(h, dt_ahead, dt_len, true, out, status);
 }
 
-int kfpos_get_state(kfpos_handle *h, double *x, double *P, uint32_t *flags) {
-    g_err.clear();
-    if (!h) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    HIPCHK(hipDeviceSynchronize());
-    const size_t T = h->cfg.n_tags;
-    const int n = h->n;
-    if (x) {
-        std::vector<double> pos(3 * T);
-        HIPCHK(hipMemcpy(pos.data(), h->d_pos, pos.size() * sizeof(double), hipMemcpyDeviceToHost));
-        std::vector<double> vel;
-        if (n == 9 || n == 8) {
-            vel.resize((n == 8 ? 4 : 3) * T);
-            HIPCHK(hipMemcpy(vel.data(), h->d_vel, vel.size() * sizeof(double), hipMemcpyDeviceToHost));
-        }
-        for (size_t t = 0; t < T; ++t) {
-            for (int k = 0; k < n; ++k) x[t * n + k] = 0.0;
-            if (n == 8) { /* [x y vx vy 0 0 theta omega]; the height: kfpos_get_height */
-                x[t * 8 + 0] = pos[t];
-                x[t * 8 + 1] = pos[T + t];
-                x[t * 8 + 2] = vel[t];
-                x[t * 8 + 3] = vel[T + t];
-                x[t * 8 + 6] = vel[2 * T + t];
-                x[t * 8 + 7] = vel[3 * T + t];
-                continue;
-            }
-            for (int k = 0; k < 3; ++k) {
-                x[t * n + k] = pos[(size_t)k * T + t];
-                if (n == 9) x[t * n + 3 + k] = vel[(size_t)k * T + t];
-            }
-        }
-    }
-    if (P) {
-        std::vector<unsigned char> buf((size_t)h->psz * T * h->rsz);
-        HIPCHK(hipMemcpy(buf.data(), h->d_P, buf.size(), hipMemcpyDeviceToHost));
-        for (size_t t = 0; t < T; ++t)
-            for (int i = 0; i < n; ++i)
-                for (int j = 0; j < n; ++j) {
-                    const size_t k = (size_t)pidx(h, i, j) * T + t;
-                    if (h->rsz == 6) { /* KFPOS_STORE_P48 (kfpos_p48.h): [psz][T] uint32 | [psz][T] uint16 */
-                        P[(t * n + i) * n + j] = kfpos_p48_decode(((const uint32_t *)buf.data())[k],
-                                                                  ((const uint16_t *)(buf.data() + (size_t)h->psz * T * 4))[k]);
-                        continue;
-                    }
-                    P[(t * n + i) * n + j] = h->rsz == 4 ? (double)((const float *)buf.data())[k]
-                                                          : ((const double *)buf.data())[k];
-                }
-    }
-    if (flags) HIPCHK(hipMemcpy(flags, h->d_flags, sizeof(uint32_t) * T, hipMemcpyDeviceToHost));
-    return KFPOS_OK;
-}
-
-int kfpos_set_state(kfpos_handle *h, const double *x, const double *P, const uint32_t *flags) {
-    g_err.clear();
-    if (!h) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    HIPCHK(hipDeviceSynchronize());
-    const size_t T = h->cfg.n_tags;
-    const int n = h->n;
-    if (x && n == 8) { /* the height row of d_pos is kept */
-        std::vector<double> xy(2 * T), vel(4 * T);
-        for (size_t t = 0; t < T; ++t) {
-            xy[t] = x[t * 8 + 0];
-            xy[T + t] = x[t * 8 + 1];
-            vel[t] = x[t * 8 + 2];
-            vel[T + t] = x[t * 8 + 3];
-            vel[2 * T + t] = x[t * 8 + 6];
-            vel[3 * T + t] = x[t * 8 + 7];
-        }
-        HIPCHK(hipMemcpy(h->d_pos, xy.data(), xy.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_vel, vel.data(), vel.size() * sizeof(double), hipMemcpyHostToDevice));
-    } else if (x) {
-        std::vector<double> pos(3 * T);
-        std::vector<double> vel(n == 9 ? 3 * T : 0);
-        for (size_t t = 0; t < T; ++t)
-            for (int k = 0; k < 3; ++k) {
-                pos[(size_t)k * T + t] = x[t * n + k];
-                if (n == 9) vel[(size_t)k * T + t] = x[t * n + 3 + k];
-            }
-        HIPCHK(hipMemcpy(h->d_pos, pos.data(), pos.size() * sizeof(double), hipMemcpyHostToDevice));
-        if (n == 9) HIPCHK(hipMemcpy(h->d_vel, vel.data(), vel.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (P) {
-        std::vector<unsigned char> buf((size_t)h->psz * T * h->rsz);
-        for (size_t t = 0; t < T; ++t)
-            for (int i = 0; i < n; ++i)
-                for (int j = h->full ? 0 : i; j < n; ++j) {
-                    const size_t k = (size_t)pidx(h, i, j) * T + t;
-                    const double v = P[(t * n + i) * n + j];
-                    if (h->rsz == 6) { /* rounded and encoded exactly as the kernels do (kfpos_p48.h) */
-                        kfpos_p48_encode(kfpos_p48_round(v), &((uint32_t *)buf.data())[k],
-                                         &((uint16_t *)(buf.data() + (size_t)h->psz * T * 4))[k]);
-                    } else if (h->rsz == 4) ((float *)buf.data())[k] = (float)v;
-                    else ((double *)buf.data())[k] = v;
-                }
-        HIPCHK(hipMemcpy(h->d_P, buf.data(), buf.size(), hipMemcpyHostToDevice));
-    }
-    if (flags) {
-        HIPCHK(hipMemcpy(h->d_flags, flags, sizeof(uint32_t) * T, hipMemcpyHostToDevice));
-        if (n == 8) /* restored latch bits: ranging epochs must run the instantiation that honours them */
-            for (size_t t = 0; t < T; ++t) h->planar_sensors = h->planar_sensors || ((flags[t] >> PLANAR_HAS_SHIFT) != 0);
-    }
-    h->stepped = true;
-    return KFPOS_OK;
-}
-
-int kfpos_latch_dim(const kfpos_handle *h) {
-    g_err.clear();
-    if (!h) return 0;
-    return h->cfg.model == KFPOS_MODEL_TOA_IMU ? 12 : (h->cfg.model == KFPOS_MODEL_PLANAR ? LATCH_ROWS : (h->cfg.model == KFPOS_MODEL_ML ? 3 : 0));
-}
-
-int kfpos_get_latch(kfpos_handle *h, double *latch) {
-    g_err.clear();
-    if (!h) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    const int L = kfpos_latch_dim(h);
-    if (L == 0) return KFPOS_OK;
-    if (!latch) return KFPOS_ERR_ARG;
-    HIPCHK(hipDeviceSynchronize());
-    stage_reset(h);
-    const size_t T = h->cfg.n_tags;
-    if (L == LATCH_ROWS) return stage_out(h, latch, h->d_latch, T, LATCH_ROWS);
-    if (L == 3) return stage_out(h, latch, h->d_vel, T, 3); /* ALGORITHM_ML: _previousEstimation, the seed of every solve */
-    /* 9-state: acceleration [3][T] and the lower triangle {00,10,11,20,21,22} [6][T], kfpos_real */
-    std::vector<unsigned char> a(3 * T * h->msz), c(6 * T * h->msz);
-    HIPCHK(hipMemcpy(a.data(), h->d_imu_acc, a.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(c.data(), h->d_imu_cov, c.size(), hipMemcpyDeviceToHost));
-    auto rd = [&](const std::vector<unsigned char> &b, size_t k) {
-        return h->msz == 4 ? (double)((const float *)b.data())[k] : ((const double *)b.data())[k];
-    };
-    static const int tri[3][3] = {{0, 1, 3}, {1, 2, 4}, {3, 4, 5}};
-    for (size_t t = 0; t < T; ++t) {
-        for (int k = 0; k < 3; ++k) latch[t * 12 + k] = rd(a, (size_t)k * T + t);
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) latch[t * 12 + 3 + 3 * i + j] = rd(c, (size_t)tri[i][j] * T + t);
-    }
-    return KFPOS_OK;
-}
-
-int kfpos_set_latch(kfpos_handle *h, const double *latch) {
-    g_err.clear();
-    if (!h) return KFPOS_ERR_ARG;
-    DevScope dev_(h->cfg.device);
-    const int L = kfpos_latch_dim(h);
-    if (L == 0) return KFPOS_OK;
-    if (!latch) return KFPOS_ERR_ARG;
-    HIPCHK(hipDeviceSynchronize());
-    stage_reset(h);
-    const size_t T = h->cfg.n_tags;
-    if (L == LATCH_ROWS) return stage_in(h, h->d_latch, latch, T, LATCH_ROWS, sizeof(double));
-    if (L == 3) return stage_in(h, h->d_vel, latch, T, 3, sizeof(double));
-    std::vector<unsigned char> a(3 * T * h->msz), c(6 * T * h->msz);
-    auto wr = [&](std::vector<unsigned char> &b, size_t k, double v) {
-        if (h->msz == 4) ((float *)b.data())[k] = (float)v;
-        else ((double *)b.data())[k] = v;
-    };
-    static const int li[6] = {0, 1, 1, 2, 2, 2}, lj[6] = {0, 0, 1, 0, 1, 2};
-    for (size_t t = 0; t < T; ++t) {
-        for (int k = 0; k < 3; ++k) wr(a, (size_t)k * T + t, latch[t * 12 + k]);
-        for (int k = 0; k < 6; ++k) wr(c, (size_t)k * T + t, latch[t * 12 + 3 + 3 * li[k] + lj[k]]);
-    }
-    HIPCHK(hipMemcpy(h->d_imu_acc, a.data(), a.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_imu_cov, c.data(), c.size(), hipMemcpyHostToDevice));
-    return KFPOS_OK;
-}
-
-/* ---- per-tag lifecycle: kfpos_reset_tags / kfpos_get_tags / kfpos_set_tags (kernels: kfpos_k_tags.hip) ---- */
-static int latch_dim(const kfpos_handle *h) {
-    return h->cfg.model == KFPOS_MODEL_TOA_IMU ? 12 : (h->cfg.model == KFPOS_MODEL_PLANAR ? LATCH_ROWS : (h->cfg.model == KFPOS_MODEL_ML ? 3 : 0));
-}
-
-/* The bounds check of the per-tag kernels: every row inside [0, n_tags), and (unique) no row twice. Nothing has been
- * written when this fails; the text names the first offending entry of the list, whichever rule it breaks. */
-static int tags_check(const kfpos_handle *h, const char *who, const int32_t *rows, int32_t n, bool unique) {
-    if (n < 0 || (n > 0 && !rows)) {
-        g_err = std::string(who) + (n < 0 ? ": n < 0" : ": rows == NULL");
-        return KFPOS_ERR_ARG;
-    }
-    int32_t bad = 0; /* the first entry out of range, n if none */
-    while (bad < n && rows[bad] >= 0 && rows[bad] < h->cfg.n_tags) ++bad;
-    int32_t twice = bad; /* the first entry in front of it that repeats an earlier one */
-    if (unique && bad > 1) {
-        /* one sort of (row, position) keys: inside a run of equal rows positions ascend, so the second key of a run is
-         * that row's first repeat */
-        std::vector<uint64_t> key((size_t)bad);
-        for (int32_t i = 0; i < bad; ++i) key[i] = ((uint64_t)(uint32_t)rows[i] << 32) | (uint32_t)i;
-        std::sort(key.begin(), key.end());
-        for (int32_t k = 1; k < bad; ++k) {
-            const bool repeats = (key[k] >> 32) == (key[k - 1] >> 32);
-            const bool second_of_run = repeats && (k == 1 || (key[k - 2] >> 32) != (key[k] >> 32));
-            const int32_t at = (int32_t)(uint32_t)key[k];
-            if (second_of_run && at < twice) twice = at;
-        }
-    }
-    if (twice < bad) {
-        g_err = std::string(who) + ": rows[" + std::to_string(twice) + "] = row " + std::to_string(rows[twice]) +
-                " is listed twice";
-        return KFPOS_ERR_ARG;
-    }
-    if (bad < n) {
-        g_err = std::string(who) + ": rows[" + std::to_string(bad) + "] = row " + std::to_string(rows[bad]) +
-                " is outside [0, " + std::to_string(h->cfg.n_tags) + ")";
-        return KFPOS_ERR_ARG;
-    }
-    return KFPOS_OK;
-}
-
-/* the part of the kernel arguments every per-tag call shares */
-static void tag_args(const kfpos_handle *h, kfpos_k::TagArgs &a) {
-    std::memset(&a, 0, sizeof(a));
-    a.T = h->cfg.n_tags;
-    a.psz = h->psz;
-    a.buf[kfpos_k::TB_POS] = h->d_pos;
-    a.buf[kfpos_k::TB_VEL] = h->d_vel;
-    a.buf[kfpos_k::TB_P] = h->d_P;
-    a.buf[kfpos_k::TB_IMU_ACC] = h->d_imu_acc;
-    a.buf[kfpos_k::TB_IMU_COV] = h->d_imu_cov;
-    a.buf[kfpos_k::TB_LATCH] = h->d_latch;
-    a.flags = h->d_flags;
-}
-
-/* The record of one tag as kfpos_get_state / kfpos_get_latch / kfpos_get_height lay it out -- x (n) | P (n x n) |
- * latch | height -- component by component: where it is stored, and whether kfpos_set_state / kfpos_set_latch /
- * kfpos_set_height store THROUGH it (the mirror half of a packed covariance is read, never written). */
-static void tag_record(const kfpos_handle *h, kfpos_k::TagArgs &a) {
-    using namespace kfpos_k;
-    const int n = h->n, L = latch_dim(h);
-    int c = 0;
-    auto put = [&](int kind, int buf, int row, int stored) {
-        a.comp[c++] = TagComp{(uint8_t)kind, (uint8_t)buf, (uint8_t)row, (uint8_t)stored};
-    };
-    a.cbase[0] = c;
-    for (int k = 0; k < n; ++k) {
-        if (n == 8) { /* [x y vx vy 0 0 theta omega]; the height row of d_pos is its own section */
-            static const int src[8] = {0, 1, 0, 1, -1, -1, 2, 3};
-            if (src[k] < 0) put(TC_NONE, 0, 0, 0);
-            else put(TC_F64, (k < 2) ? TB_POS : TB_VEL, src[k], 1);
-        } else if (k < 3) put(TC_F64, TB_POS, k, 1);
-        else if (n == 9 && k < 6) put(TC_F64, TB_VEL, k - 3, 1);
-        else put(TC_NONE, 0, 0, 0); /* 6-state: the velocity is not a stored member; 9-state: a = 0 */
-    }
-    a.cbase[1] = c;
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) put(TC_COV, TB_P, pidx(h, i, j), (h->full || j >= i) ? 1 : 0);
-    a.cbase[2] = c;
-    if (L == LATCH_ROWS)
-        for (int k = 0; k < L; ++k) put(TC_F64, TB_LATCH, k, 1);
-    else if (L == 3) /* ALGORITHM_ML: _previousEstimation, the seed of every solve */
-        for (int k = 0; k < L; ++k) put(TC_F64, TB_VEL, k, 1);
-    else if (L == 12) { /* acceleration [3] + the lower triangle {00,10,11,20,21,22} of its covariance, kfpos_real */
-        static const int tri[3][3] = {{0, 1, 3}, {1, 2, 4}, {3, 4, 5}};
-        for (int k = 0; k < 3; ++k) put(TC_REAL, TB_IMU_ACC, k, 1);
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) put(TC_REAL, TB_IMU_COV, tri[i][j], i >= j ? 1 : 0);
-    }
-    a.cbase[3] = c;
-    if (n == 8) put(TC_F64, TB_POS, 2, 1);
-}
-
-/* The stored rows of one tag and what kfpos_create (+ kfpos_set_planar) left in them: TagComp::aux = 0 zero, 1..3 the
- * start position, 4 / 5 the planar height / angle. */
-static void tag_fresh(const kfpos_handle *h, kfpos_k::TagArgs &a) {
-    using namespace kfpos_k;
-    const int n = h->n;
-    int c = 0;
-    auto put = [&](int kind, int buf, int row, int what) {
-        a.comp[c++] = TagComp{(uint8_t)kind, (uint8_t)buf, (uint8_t)row, (uint8_t)what};
-    };
-    for (int k = 0; k < 3; ++k) put(TC_F64, TB_POS, k, (n == 8 && k == 2) ? 4 : 1 + k);
-    if (n == 3)
-        for (int k = 0; k < 3; ++k) put(TC_F64, TB_VEL, k, 1 + k); /* the solver's seed */
-    if (n == 8)
-        for (int k = 0; k < 4; ++k) put(TC_F64, TB_VEL, k, k == 2 ? 5 : 0); /* vx vy theta omega */
-    if (n == 9)
-        for (int k = 0; k < 3; ++k) put(TC_F64, TB_VEL, k, 0);
-    for (int k = 0; k < h->psz; ++k) put(TC_COV, TB_P, k, 0);
-    if (n == 9) {
-        for (int k = 0; k < 3; ++k) put(TC_REAL, TB_IMU_ACC, k, 0);
-        for (int k = 0; k < 6; ++k) put(TC_REAL, TB_IMU_COV, k, 0);
-    }
-    if (n == 8)
-        for (int k = 0; k < LATCH_ROWS; ++k) put(TC_F64, TB_LATCH, k, 0);
-    a.n_comp = c;
-}
-
-/* get (STORE = false) / set (STORE = true) of the listed tags; the host pointers of absent parts are null, and a
- * store only ever reads the caller's arrays */
-extern "C++" template <bool STORE>
-static int tags_transfer(kfpos_handle *h, const int32_t *rows, int32_t n,
-                         std::conditional_t<STORE, const double, double> *x,
-                         std::conditional_t<STORE, const double, double> *P,
-                         std::conditional_t<STORE, const uint32_t, uint32_t> *flags,
-                         std::conditional_t<STORE, const double, double> *latch,
-                         std::conditional_t<STORE, const double, double> *height) {
-    constexpr bool store = STORE;
-    kfpos_k::TagArgs a;
-    tag_args(h, a);
-    tag_record(h, a);
-    std::conditional_t<STORE, const double, double> *part[kfpos_k::TAG_SECTIONS] = {x, P, latch_dim(h) ? latch : nullptr, height};
-    const int width[kfpos_k::TAG_SECTIONS] = {h->n, h->n * h->n, latch_dim(h), 1};
-    size_t wsum = 0;
-    for (int s = 0; s < kfpos_k::TAG_SECTIONS; ++s) wsum += (size_t)(a.w[s] = part[s] ? width[s] : 0);
-    if (wsum == 0 && !flags) return KFPOS_OK;
-    /* per listed tag: its values (doubles), its flags word, its row index */
-    const size_t rec = wsum * sizeof(double) + sizeof(uint32_t) + sizeof(int32_t);
-    Route st = route_of(h);
-    const int rc = st.block(rec, (size_t)n);
-    if (rc) return rc;
-    const size_t chunk = st.chunk;
-    for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
-        const size_t m = (size_t)n - c0 < chunk ? (size_t)n - c0 : chunk;
-        const size_t off_fl = m * wsum * sizeof(double), off_rows = off_fl + m * sizeof(uint32_t);
-        HIPCHK(st.up(off_rows, rows + c0, m * sizeof(int32_t)));
-        if constexpr (store) {
-            size_t off = 0;
-            for (int s = 0; s < kfpos_k::TAG_SECTIONS; ++s) {
-                if (!a.w[s]) continue;
-                HIPCHK(st.up(off, part[s] + c0 * width[s], m * width[s] * sizeof(double)));
-                off += m * width[s] * sizeof(double);
-            }
-            if (flags) HIPCHK(st.up(off_fl, flags + c0, m * sizeof(uint32_t)));
-        }
-        a.n = (int)m;
-        a.val = (double *)st.dev;
-        a.fl = flags ? (uint32_t *)(st.dev + off_fl) : nullptr;
-        a.rows = (const int32_t *)(st.dev + off_rows);
-        kfpos_k::launch_tags(store ? kfpos_k::TAGS_SCATTER : kfpos_k::TAGS_GATHER, h->cfg.storage, nullptr, a);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(nullptr)); /* the staging is free again; a mapped block's results are visible */
-        if constexpr (!store) {
-            size_t off = 0;
-            for (int s = 0; s < kfpos_k::TAG_SECTIONS; ++s) {
-                if (!a.w[s]) continue;
-                HIPCHK(st.down(part[s] + c0 * width[s], off, m * width[s] * sizeof(double)));
-                off += m * width[s] * sizeof(double);
-            }
-            if (flags) HIPCHK(st.down(flags + c0, off_fl, m * sizeof(uint32_t)));
-        }
-    }
-    return KFPOS_OK;
-}
-
-int kfpos_get_tags(kfpos_handle *h, const int32_t *rows, int32_t n, double *x, double *P, uint32_t *flags,
-                   double *latch, double *height) {
-    g_err.clear();
-    if (!h) return KFPOS_ERR_ARG;
-    int rc = tags_check(h, "kfpos_get_tags", rows, n, false);
-    if (rc) return rc;
-    if (height && h->cfg.model != KFPOS_MODEL_PLANAR) {
-        g_err = "kfpos_get_tags: height belongs to KFPOS_MODEL_PLANAR";
-        return KFPOS_ERR_MODEL;
-    }
-    if (n == 0) return KFPOS_OK;
-    DevScope dev_(h->cfg.device);
-    if ((rc = drain_slots(h))) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    return tags_transfer<false>(h, rows, n, x, P, flags, latch, height);
-}
-
-int kfpos_set_tags(kfpos_handle *h, const int32_t *rows, int32_t n, const double *x, const double *P,
-                   const uint32_t *flags, const double *latch, const double *height) {
-    g_err.clear();
-    if (!h) return KFPOS_ERR_ARG;
-    int rc = tags_check(h, "kfpos_set_tags", rows, n, true);
-    if (rc) return rc;
-    if (height && h->cfg.model != KFPOS_MODEL_PLANAR) {
-        g_err = "kfpos_set_tags: height belongs to KFPOS_MODEL_PLANAR";
-        return KFPOS_ERR_MODEL;
-    }
-    if (n == 0) return KFPOS_OK;
-    DevScope dev_(h->cfg.device);
-    if ((rc = drain_slots(h))) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    if ((rc = tags_transfer<true>(h, rows, n, x, P, flags, latch, height))) return rc;
-    if (flags && h->n == 8) /* restored latch bits: ranging epochs must run the instantiation that honours them */
-        for (int32_t i = 0; i < n; ++i) h->planar_sensors = h->planar_sensors || ((flags[i] >> PLANAR_HAS_SHIFT) != 0);
-    h->stepped = true;
-    return KFPOS_OK;
-}
-
-int kfpos_reset_tags(kfpos_handle *h, const int32_t *rows, int32_t n, const double *init_xyz) {
-    g_err.clear();
-    if (!h) return KFPOS_ERR_ARG;
-    int rc = tags_check(h, "kfpos_reset_tags", rows, n, true);
-    if (rc) return rc;
-    if (init_xyz && !h->cfg.use_init_pos) {
-        g_err = "kfpos_reset_tags: init_xyz on a handle without a fixed start (use_init_pos = 0): the tag's next epoch is its ML initialisation";
-        return KFPOS_ERR_STATE;
-    }
-    if (n == 0) return KFPOS_OK;
-    DevScope dev_(h->cfg.device);
-    if ((rc = drain_slots(h))) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    kfpos_k::TagArgs a;
-    tag_args(h, a);
-    tag_fresh(h, a);
-    for (int k = 0; k < 3; ++k) a.cst[k] = h->cfg.use_init_pos ? h->cfg.init_pos[k] : NAN;
-    a.cst[3] = h->planar.fixed_height; /* mUWBtagZ / mAngle as kfpos_set_planar wrote them (0 / 0 if it never ran) */
-    a.cst[4] = h->planar.init_angle;
-    /* per listed tag: its start position (if given), its row index */
-    const size_t rec = (init_xyz ? 3 * sizeof(double) : 0) + sizeof(int32_t);
-    Route st = route_of(h);
-    if ((rc = st.block(rec, (size_t)n))) return rc;
-    const size_t chunk = st.chunk;
-    for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
-        const size_t m = (size_t)n - c0 < chunk ? (size_t)n - c0 : chunk;
-        const size_t off_rows = init_xyz ? m * 3 * sizeof(double) : 0;
-        HIPCHK(st.up(off_rows, rows + c0, m * sizeof(int32_t)));
-        if (init_xyz) HIPCHK(st.up(0, init_xyz + c0 * 3, m * 3 * sizeof(double)));
-        a.n = (int)m;
-        a.init = init_xyz ? (const double *)st.dev : nullptr;
-        a.rows = (const int32_t *)(st.dev + off_rows);
-        kfpos_k::launch_tags(kfpos_k::TAGS_RESET, h->cfg.storage, nullptr, a);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(nullptr));
-    }
-    return KFPOS_OK;
-}
-
-/* ---- pose for a row list: kfpos_get_pose_rows / kfpos_get_predicted_rows (kernel: k_get_pose_rows, kfpos_k_misc.hip) ---- */
-/* both calls: out[k] = the caller's k-th array of w[k] doubles per entry (null = not wanted). Staged like the lifecycle
- * calls: per chunk of m entries the list and dt go up, one launch writes the entries' results row-major, and they come
- * down as they are -- nothing here is sized by n_tags. */
-static int pose_rows_host(kfpos_handle *h, const char *who, const int32_t *rows, int32_t n, const double *dt_ahead,
-                          int32_t dt_len, bool predicted, double *const out[3], const int w[3], uint32_t *status) {
-    if (!h) return KFPOS_ERR_ARG;
-    int rc = tags_check(h, who, rows, n, false);
-    if (rc) return rc;
-    if (!dt_ahead || (dt_len != 1 && dt_len != n)) {
-        g_err = std::string(who) + (!dt_ahead ? ": dt_ahead == NULL" : ": dt_len = " + std::to_string(dt_len) + " is neither 1 nor n = " + std::to_string(n));
-        return KFPOS_ERR_ARG;
-    }
-    if (predicted && (!out[0] || !out[1])) {
-        g_err = std::string(who) + (!out[0] ? ": x == NULL" : ": P == NULL");
-        return KFPOS_ERR_ARG;
-    }
-    if (n == 0) return KFPOS_OK;
-    DevScope dev_(h->cfg.device);
-    if ((rc = drain_slots(h))) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    const bool each = dt_len != 1; /* (dt_len == n == 1: the shared value is that entry's) */
-    size_t wsum = 0;
-    for (int k = 0; k < 3; ++k) wsum += out[k] ? (size_t)w[k] : 0;
-    if (wsum == 0 && !status) return KFPOS_OK;
-    /* per entry: its results and its dt (doubles), its status word, its row index */
-    const size_t rec = (wsum + (each ? 1 : 0)) * sizeof(double) + sizeof(uint32_t) + sizeof(int32_t);
-    Route st = route_of(h);
-    if ((rc = st.block(rec, (size_t)n))) return rc;
-    kfpos_k::PoseRowsArgs a = {};
-    pose_bank_args(h, a.p);
-    a.p.dt_ahead = dt_ahead[0];
-    const size_t chunk = st.chunk;
-    for (size_t c0 = 0; c0 < (size_t)n; c0 += chunk) {
-        const size_t m = (size_t)n - c0 < chunk ? (size_t)n - c0 : chunk;
-        size_t off[3], o = 0;
-        for (int k = 0; k < 3; ++k) {
-            off[k] = o;
-            o += out[k] ? m * w[k] * sizeof(double) : 0;
-        }
-        const size_t off_dt = o, off_st = off_dt + (each ? m * sizeof(double) : 0), off_rows = off_st + m * sizeof(uint32_t);
-        HIPCHK(st.up(off_rows, rows + c0, m * sizeof(int32_t)));
-        if (each) HIPCHK(st.up(off_dt, dt_ahead + c0, m * sizeof(double)));
-        double *d[3];
-        for (int k = 0; k < 3; ++k) d[k] = out[k] ? (double *)(st.dev + off[k]) : nullptr;
-        if (predicted) {
-            a.p.full_x = d[0];
-            a.p.full_P = d[1];
-        } else {
-            a.p.pos = d[0];
-            a.p.cov = d[1];
-            a.p.vel = d[2];
-        }
-        a.p.dt_each = each ? (const double *)(st.dev + off_dt) : nullptr;
-        a.p.status = status ? (uint32_t *)(st.dev + off_st) : nullptr;
-        a.rows = (const int32_t *)(st.dev + off_rows);
-        a.n = (int)m;
-        kfpos_k::launch_get_pose_rows(h->cfg.model, h->full != 0, h->cfg.storage, nullptr, a);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(nullptr)); /* the staging is free again; a mapped block's results are visible */
-        for (int k = 0; k < 3; ++k)
-            if (out[k]) HIPCHK(st.down(out[k] + c0 * w[k], off[k], m * w[k] * sizeof(double)));
-        if (status) HIPCHK(st.down(status + c0, off_st, m * sizeof(uint32_t)));
-    }
-    return KFPOS_OK;
-}
-
-int kfpos_get_pose_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const double *dt_ahead, int32_t dt_len,
-                        double *pos, double *cov3x3, double *vel, uint32_t *status) {
-    g_err.clear();
-    double *const out[3] = {pos, cov3x3, vel};
-    const int w[3] = {3, 9, 3};
-    return pose_rows_host(h, "kfpos_get_pose_rows", rows, n, dt_ahead, dt_len, false, out, w, status);
-}
-
-int kfpos_get_predicted_rows(kfpos_handle *h, const int32_t *rows, int32_t n, const double *dt_ahead, int32_t dt_len,
-                             double *x, double *P, uint32_t *status) {
-    g_err.clear();
-    double *const out[3] = {x, P, nullptr};
-    const int w[3] = {h ? h->n : 0, h ? h->n * h->n : 0, 0};
-    return pose_rows_host(h, "kfpos_get_predicted_rows", rows, n, dt_ahead, dt_len, true, out, w, status);
-}
-
 /* ---- row-list steps: kfpos_step_*_rows, kfpos_slot_acquire_rows / kfpos_slot_submit_rows ----
  * The step kernels are not touched and see no row index: the listed tags' stored bits are gathered into a compact work
  * bank (kfpos_k_tags.hip: k_rows_work), the kernel this handle runs anyway steps that bank with KArgs::T = n, and the
@@ -1407,7 +773,7 @@ extern "C++" int rows_step(kfpos_handle *h, hipStream_t s, const kfpos_layout::R
     using namespace kfpos_k;
     TagArgs g;
     tag_args(h, g);
-    tag_fresh(h, g); /* the stored rows of a tag: the list a reset writes */
+    g.n_comp = fresh_table(h->n, h->psz, g.comp); /* the stored rows of a tag: the list a reset writes */
     g.n = n;
     g.rows = d_rows;
     for (int b = 0; b < TB_N; ++b) g.wbuf[b] = g.buf[b] ? h->d_work + L.w[b] : nullptr;

@@ -3,7 +3,8 @@
  * host + device buffers and three streams, so that the upload of one round, the step of the one before and the return of
  * the one before that overlap. Whole-bank rounds and row-list rounds share the acquire, the round's part of the argument
  * block and the third stage; what a round may feed is decided by round_check, the row-list machinery (rows_check,
- * rows_reserve, rows_step) lives in kfpos_hip.hip next to the lifecycle code it is built on (kfpos_kernels.h declares both).
+ * rows_reserve, rows_step) lives in kfpos_hip.hip, the lifecycle code it is built on in kfpos_hip_state.hip (kfpos_kernels.h
+ * declares both).
  */
 #include <cstdlib>
 #include <cstring>

@@ -1,6 +1,7 @@
 /*
  * kfpos_internal.h -- what the translation units of libkfpos_hip.so share and the ABI does not show: the handle.
- * (kfpos_k_*.hip: the kernels; kfpos_hip.hip: host side and filter entry points; kfpos_hip_slots.hip: the streaming
+ * (kfpos_k_*.hip: the kernels; kfpos_hip.hip: host side and filter entry points; kfpos_hip_state.hip: whole-bank
+ * accessors, per-tag lifecycle, pose for a row list; kfpos_hip_slots.hip: the streaming
  * slots, kfpos_slot_*; kfpos_hip_replay.hip: the replay entry points, kfpos_run_*_dev; kfpos_comm.hip: the RCCL pose gather.)
  */
 #ifndef KFPOS_INTERNAL_H

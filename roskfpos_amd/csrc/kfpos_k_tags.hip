@@ -10,8 +10,8 @@
  * stride T, one element per work item -- unavoidable with a component-major bank, and the list is short against T.
  *
  * Where a component lives (which array, which row, which element type) is not written down here: the host hands the
- * kernels a table (TagArgs::comp) built from the same statements the whole-bank accessors use (pidx, the x / latch
- * orders of kfpos_get_state / kfpos_get_latch); elements are decoded and encoded through ldrow / strow / ldcov / stcov.
+ * kernels a table (TagArgs::comp) from kfpos_state_record.h, the very table the whole-bank accessors walk on the CPU
+ * (kfpos_hip_state.hip: bank_transfer); elements are decoded and encoded through ldrow / strow / ldcov / stcov.
  * Row indices are validated on the host before any launch: no kernel sees a row outside [0, T).
  */
 #include "kfpos_kernels.h"

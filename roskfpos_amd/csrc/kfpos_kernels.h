@@ -1,7 +1,7 @@
 /*
  * kfpos_kernels.h -- what the kernel translation units of libkfpos_hip.so share: the kernel-argument blocks, the
  * device-side helpers that stage an epoch (component-major HBM -> registers / LDS), and the selector functions through
- * which the host side (kfpos_hip.hip, kfpos_hip_slots.hip, kfpos_hip_replay.hip) obtains a kernel without seeing its template, and what those
+ * which the host side (kfpos_hip.hip, kfpos_hip_state.hip, kfpos_hip_slots.hip, kfpos_hip_replay.hip) obtains a kernel without seeing its template, and what those
  * host units share among themselves (at the end of namespace kfpos_k's declarations).
  *
  * Execution model: ONE FILTER PER LANE, 64 filters per wavefront, one wavefront per workgroup.
@@ -26,7 +26,7 @@
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
  * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
- * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_hip_slots (the streaming slots of the C ABI, kfpos_slot_*), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
+ * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_hip_state (the state side of the C ABI: whole-bank accessors, per-tag lifecycle, pose for a row list), kfpos_hip_slots (the streaming slots of the C ABI, kfpos_slot_*), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
 #define KFPOS_KERNELS_H
@@ -35,6 +35,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <type_traits>
 
 #define KFPOS_HD __host__ __device__
@@ -42,6 +43,7 @@
 #include "kfpos_internal.h"
 #include "kfpos_p48.h"
 #include "kfpos_replay_plan.h"
+#include "kfpos_state_record.h"
 
 namespace kfpos_k {
 
@@ -203,18 +205,9 @@ void launch_rows_to_cols(size_t esz, hipStream_t s, const void *src, void *dst, 
 void launch_cols_to_rows(hipStream_t s, const double *src, double *dst, int T, int C);            /* kfpos_k_misc.hip */
 
 /* ---- per-tag lifecycle (kfpos_k_tags.hip): gather / scatter / reset of a list of tags ----
- * One entry of the table that says where a component lives: kind = element type (TC_*), buf = index into TagArgs::buf,
- * row = row of that component-major array. aux -- gather / scatter: 1 = the entry is stored through this component
- * (0: not stored at all, or the lower-triangle mirror of a packed entry); reset: what a fresh handle holds (0 = zero,
- * 1..5 = TagArgs::cst[aux - 1], 1..3 taken from TagArgs::init when that is given). */
-struct TagComp {
-    uint8_t kind, buf, row, aux;
-};
-enum : int { TC_NONE = 0, TC_F64 = 1, TC_COV = 2, TC_REAL = 3 };                 /* double / stored covariance entry / kfpos_real */
-/* TB_* (TB_POS ... TB_LATCH, TB_N), the indices into TagArgs::buf: kfpos_host_layout.h */
+ * TagComp, TC_*, TAG_SECTIONS, TAG_COMPS and the two tables of comp[] (the record of a tag / its stored rows):
+ * kfpos_state_record.h. TB_* (TB_POS ... TB_LATCH, TB_N), the indices into TagArgs::buf: kfpos_host_layout.h */
 enum : int { TAGS_GATHER = 0, TAGS_SCATTER = 1, TAGS_RESET = 2, TAGS_WORK_IN = 3, TAGS_WORK_OUT = 4 };
-constexpr int TAG_SECTIONS = 4;            /* x | P | latch | height */
-constexpr int TAG_COMPS = 9 + 81 + 15 + 1; /* the longest record: no model has all of them at once */
 struct TagArgs {
     int T, n, psz;            /* tags in the bank, tags listed in this launch, stored covariance entries per tag */
     int w[TAG_SECTIONS];      /* gather / scatter: components per tag of each section present in `val`, 0 = section absent */
@@ -243,8 +236,8 @@ constexpr int PLANAR_HAS_SHIFT = 4;              /* planar flags word: bits 5..7
 
 } // namespace kfpos_k
 
-/* ---- what the host units share: defined in kfpos_hip.hip unless noted, used by kfpos_hip_replay.hip and
- * kfpos_hip_slots.hip as well ---- */
+/* ---- what the host units share: defined in kfpos_hip.hip unless noted, used by kfpos_hip_state.hip,
+ * kfpos_hip_replay.hip and kfpos_hip_slots.hip as well ---- */
 #define KFPOS_HIDDEN __attribute__((visibility("hidden")))
 /* A round: what one call feeds the bank. ROUND_TOA / _IMU / _FUSED are KFPOS_SLOT_TOA / _IMU / _TOA_IMU and the
  * MODE_* of the step kernels; ROUND_SENSOR carries a KFPOS_SENSOR_* kind beside it. */
@@ -296,6 +289,119 @@ KFPOS_HIDDEN size_t park9_bytes();
         }                                                                                         \
     } while (0)
 using DevScope = KfposDevScope; /* kfpos_internal.h */
+
+/* ---- staging (defined in kfpos_hip.hip; kfpos_hip_state.hip takes the same routes) ---- */
+/* a region of the row-major staging area; regions live until the next stage_reset() (start of an API call) */
+KFPOS_HIDDEN int stage_region(kfpos_handle *h, size_t bytes, void **out);
+inline void stage_reset(kfpos_handle *h) { h->stage_used = 0; }
+/* host row-major [n][C] -> component-major [C][n] of `esz`-byte elements: one copy (into `landing`, or a region of the
+ * staging area) + a device-side turn */
+KFPOS_HIDDEN int stage_in(kfpos_handle *h, void *dst, const void *src, size_t n, int C, size_t esz, void *landing = nullptr);
+/* device [C][n] doubles -> host row-major [n][C] */
+KFPOS_HIDDEN int stage_out(kfpos_handle *h, double *dst, const double *dsrc, size_t n, int C);
+template <typename E>
+inline void rows_to_cols_host(void *dst, const void *src, size_t n, int C) {
+    const E *s = (const E *)src;
+    E *d = (E *)dst;
+    for (size_t t = 0; t < n; ++t)
+        for (int c = 0; c < C; ++c) d[(size_t)c * n + t] = s[t * C + c];
+}
+
+/* ---- the route a host-buffer call takes to the device, chosen once per call ----
+ * mapped (small banks, kfpos_handle::sm): inputs and outputs live in one host-pinned, device-mapped block; the CPU turns
+ * the layout in place, the kernels read and write host memory over the bus, and the call ends with a synchronisation of
+ * the null stream. staged: plain copies into device buffers and a layout kernel per array, ended by a device
+ * synchronisation. A call names, per array, where it lives on either route (Place) and uses the operations below; it
+ * never asks which route it is on. */
+struct Place {
+    size_t mapped; /* offset in the mapped block */
+    void *dst;     /* staged: the component-major device array ... */
+    void *landing; /* ... and where the row-major copy lands before its turn (null: a region of the staging area) */
+};
+constexpr size_t TAGS_STAGE_MAX = (size_t)16 << 20;
+struct Route {
+    kfpos_handle *h;
+    unsigned char *host, *dev; /* the mapped block (host == null: staged; dev is then the region block() reserved) */
+    size_t chunk;              /* block(): records it holds */
+
+    void *at(const Place &p) const { return host ? dev + p.mapped : p.dst; }
+    /* row-major host array [n][C] of esz-byte elements in, component-major at(p) */
+    int in(const void *src, size_t n, int C, size_t esz, const Place &p) {
+        if (!host) return stage_in(h, p.dst, src, n, C, esz, p.landing);
+        if (esz == 4) rows_to_cols_host<uint32_t>(host + p.mapped, src, n, C);
+        else rows_to_cols_host<uint64_t>(host + p.mapped, src, n, C);
+        return KFPOS_OK;
+    }
+    /* dt of a call, validated: one value (dt_len == 1) travels in the arguments, an array goes up. null = shared */
+    int dt_in(const double *dt, int32_t dt_len, size_t n, const Place &p, const double **d_dt) {
+        *d_dt = dt_len == 1 ? nullptr : (const double *)at(p);
+        return dt_len == 1 ? KFPOS_OK : in(dt, n, 1, sizeof(double), p);
+    }
+    /* component-major doubles [C][n] at device address d (inside a Place of this call) out to row-major host */
+    int out(double *dst, const double *d, size_t n, int C) {
+        if (!host) return stage_out(h, dst, d, n, C);
+        const double *s = (const double *)(host + ((const unsigned char *)d - dev));
+        for (size_t t = 0; t < n; ++t)
+            for (int c = 0; c < C; ++c) dst[t * C + c] = s[(size_t)c * n + t];
+        return KFPOS_OK;
+    }
+    /* the call's launches have completed (a mapped block's results are visible) */
+    int sync() {
+        HIPCHK(host ? hipStreamSynchronize(nullptr) : hipDeviceSynchronize());
+        return KFPOS_OK;
+    }
+    /* n status words delivered, after sync() */
+    int words(uint32_t *status, const Place &p, size_t n) {
+        if (status && host) std::memcpy(status, host + p.mapped, sizeof(uint32_t) * n);
+        else if (status) HIPCHK(hipMemcpy(status, p.dst, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+        return KFPOS_OK;
+    }
+    int finish(uint32_t *status, const Place &p, size_t n) {
+        const int rc = sync();
+        return rc ? rc : words(status, p, n);
+    }
+    /* staged: p.dst = `bytes` of the staging area (reserve() first where several are held at once, so that none moves
+     * while another is in use); mapped: the block has its places already */
+    int reserve(size_t bytes) {
+        void *probe = nullptr;
+        const int rc = host ? KFPOS_OK : stage_region(h, bytes, &probe);
+        if (!host) stage_reset(h);
+        return rc;
+    }
+    int region(size_t bytes, Place &p) { return host ? KFPOS_OK : stage_region(h, bytes, &p.dst); }
+    /* The per-tag calls stage records: the whole mapped block, or one region of the staging area filled and emptied
+     * with plain copies, addressed as dev + offset. Sized for n records of `rec` bytes, at most TAGS_STAGE_MAX: longer
+     * lists go through it in chunks of `chunk` (>= 1) records. */
+    int block(size_t rec, size_t n) {
+        size_t cap = h->sm.bytes;
+        if (!host) {
+            cap = rec * n < TAGS_STAGE_MAX ? rec * n : TAGS_STAGE_MAX;
+            const int rc = stage_region(h, cap, (void **)&dev);
+            if (rc) return rc;
+        }
+        chunk = cap / rec;
+        if (chunk == 0) { /* (a loop over chunks of nothing would never end) */
+            g_err = "per-tag staging holds less than one tag";
+            return KFPOS_ERR_STATE;
+        }
+        return KFPOS_OK;
+    }
+    hipError_t up(size_t off, const void *src, size_t bytes) const {
+        if (!host) return hipMemcpy(dev + off, src, bytes, hipMemcpyHostToDevice);
+        std::memcpy(host + off, src, bytes);
+        return hipSuccess;
+    }
+    hipError_t down(void *dst, size_t off, size_t bytes) const {
+        if (!host) return hipMemcpy(dst, dev + off, bytes, hipMemcpyDeviceToHost);
+        std::memcpy(dst, host + off, bytes);
+        return hipSuccess;
+    }
+};
+KFPOS_HIDDEN Route route_of(kfpos_handle *h);
+/* kfpos_hip_state.hip, for the row-list steps: the part of the per-tag kernels' arguments every call shares (the bank's
+ * arrays), and the bounds check of a row list (every row inside [0, n_tags); unique: none twice) */
+KFPOS_HIDDEN void tag_args(const kfpos_handle *h, kfpos_k::TagArgs &a);
+KFPOS_HIDDEN int tags_check(const kfpos_handle *h, const char *who, const int32_t *rows, int32_t n, bool unique);
 
 namespace {
 

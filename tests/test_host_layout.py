@@ -41,5 +41,5 @@ def test_regions_are_aligned_disjoint_and_inside(driver):
 
 def test_one_region_bump():
     """the 256-byte bump exists once: no other host unit rounds a region up on its own"""
-    for name in ("kfpos_hip.hip", "kfpos_hip_slots.hip", "kfpos_hip_replay.hip"):
+    for name in ("kfpos_hip.hip", "kfpos_hip_state.hip", "kfpos_hip_slots.hip", "kfpos_hip_replay.hip"):
         assert "auto region" not in open(os.path.join(CSRC, name)).read(), name

@@ -17,7 +17,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 OUT = os.path.join(ROOT, "tools", "exp", "_build")
-UNITS = "kfpos_k_toa6f kfpos_k_toa6s kfpos_k_misc kfpos_k_coop kfpos_k_tags kfpos_hip kfpos_hip_slots kfpos_hip_replay kfpos_comm".split()
+UNITS = "kfpos_k_toa6f kfpos_k_toa6s kfpos_k_misc kfpos_k_coop kfpos_k_tags kfpos_hip kfpos_hip_state kfpos_hip_slots kfpos_hip_replay kfpos_comm".split()
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Rpass-analysis=kernel-resource-usage"]
 
 EDITS = {
