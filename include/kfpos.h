@@ -430,6 +430,52 @@ int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t
 #define KFPOS_SLOT_POSE_COV   0x1000
 int kfpos_slot_pose_rows(kfpos_handle *h, int32_t slot, double **cov3x3 /* [n][9] */, double **vel /* [n][3] */);
 
+/* Streaming slots: ranges as 16-bit deltas, decoded on the device. What crosses the bus in a whole-bank ranging round is
+ * mostly range_mm [max_anchors][n_tags] int32; a range changes by centimetres between two epochs of one tag, so it fits an
+ * int16 delta against the previous value, and the exceptions (a tag that first appears, an NLOS jump, a range beyond
+ * 32.767 m from a zero base) fit a short list. With KFPOS_SLOT_RANGES_D16 a round sends one int16 code per element plus
+ * that list, and a kernel (k_decode_d16) rebuilds the int32 matrix the unchanged step kernels read. Codes, encoder
+ * (kfpos_d16_put) and reference decoder: kfpos_d16.h, which also defines
+ *   typedef struct kfpos_delta_slot {
+ *       int16_t *code;         pinned, [max_anchors][n_tags]
+ *       int32_t *esc;          pinned, [esc_capacity][2]: flat index, value
+ *       int32_t *n_esc;        entries used; kfpos_slot_delta sets it to 0
+ *       int32_t  esc_capacity; max_anchors * n_tags: any matrix is representable
+ *       int32_t *base;         host mirror [max_anchors][n_tags], shared by the slots
+ *       int32_t  n_tags, max_anchors;
+ *   } kfpos_delta_slot;
+ * The base is one int32 [max_anchors][n_tags] matrix per handle, zero at first, and changes only through D16 rounds:
+ * a host mirror (moved by the encoder) and a device copy (moved by the decode kernel), kept equal by construction.
+ * Plain rounds and row-list rounds never touch the base; they may be interleaved freely with D16 rounds.
+ *
+ * kfpos_slot_delta(slot, out): the slot must be acquired (kfpos_slot_acquire) and not busy; opens it for a D16 round
+ *   and sets *n_esc = 0. At most one slot is open at a time: opening a second one is KFPOS_ERR_STATE. The D16 blocks
+ *   are allocated by the first call, as the KFPOS_SLOT_POSE_COV arrays are (per slot: code | esc, pinned and on the
+ *   device; per handle: the mirror and the device base). max_anchors * n_tags > INT32_MAX -> KFPOS_ERR_ARG.
+ * kfpos_slot_encode_ranges(slot, flags): convenience for callers that keep filling range_mm: encodes the open slot's int32
+ *   matrix through kfpos_d16_put, in ascending order. With KFPOS_SLOT_DT_PER_TAG in `flags`, tags whose slot dt < 0 are
+ *   left out. It costs a CPU pass over the matrix; producers that care write codes directly.
+ * kfpos_slot_submit(flags | KFPOS_SLOT_RANGES_D16): a round without ranging (KFPOS_SLOT_IMU) -> KFPOS_ERR_ARG;
+ *   kfpos_slot_submit_rows with the flag -> KFPOS_ERR_ARG; the slot was not opened -> KFPOS_ERR_STATE. The escape list
+ *   is validated on the host in O(n_esc) before anything is enqueued: 0 <= n_esc <= capacity, indices strictly
+ *   ascending and inside the matrix, values > 0, code[index] == KFPOS_D16_ESCAPE; otherwise KFPOS_ERR_ARG and
+ *   kfpos_last_error() names the first offending entry: the kernel never sees an unchecked index. Then code and the used
+ *   pairs go up on the copy stream (one copy) instead of the ranges region, the decode kernel runs on the compute
+ *   stream behind them, writing the slot's device ranges region and the device base, and the step and everything after
+ *   it are what they are without the flag; err, accel, cov, dt and the REUSE flags behave as ever. The submit closes
+ *   the slot, whatever it returns.
+ * RESTART RULE: any D16 submit that returns other than KFPOS_OK restarts the base at zero on both sides at the next
+ *   kfpos_slot_delta (one rule for every refusal after the mirror has moved). So does an open slot that is submitted
+ *   without the flag, as a row-list round, or opened again.
+ * SKIPPED TAGS: with KFPOS_SLOT_DT_PER_TAG the codes and escape entries of a tag whose dt < 0 are not read: the tag
+ *   decodes to 0 and its base is kept, so a producer may leave stale codes for silent tags (an entry's index is still
+ *   checked against the matrix and the list's order).
+ * KFPOS_VERSION is unchanged: detect the feature by symbol. */
+#include "kfpos_d16.h"
+#define KFPOS_SLOT_RANGES_D16 0x2000
+int kfpos_slot_delta(kfpos_handle *h, int32_t slot, kfpos_delta_slot *out);
+int kfpos_slot_encode_ranges(kfpos_handle *h, int32_t slot, int32_t flags);
+
 /* ---- asynchronous device-buffer API (inputs already resident in HBM) ----
  * All pointers are device pointers; `stream` is a hipStream_t (NULL = the default stream). Calls
  * enqueue work and return; the caller synchronises. Device layouts are component-major so that the

@@ -41,6 +41,7 @@ EXPORTS = [
     "kfpos_step_toa_rows", "kfpos_step_imu_rows", "kfpos_step_toa_imu_rows", "kfpos_step_sensor_rows",
     "kfpos_slot_acquire_rows", "kfpos_slot_submit_rows",
     "kfpos_get_pose_rows", "kfpos_get_predicted_rows", "kfpos_slot_pose_rows",
+    "kfpos_slot_delta", "kfpos_slot_encode_ranges",
     "kfpos_shard_range", "kfpos_comm_unique_id", "kfpos_comm_create", "kfpos_comm_create_all", "kfpos_comm_destroy",
     "kfpos_comm_world", "kfpos_comm_rank", "kfpos_comm_set_total", "kfpos_allgather_poses",
     "kfpos_allgather_poses_multi", "kfpos_comm_wait", "kfpos_comm_sync", "kfpos_assemble_poses_dev",
@@ -53,6 +54,8 @@ EVENT_IMU, EVENT_TOA = 0, 1  # kfpos_run_events_dev: newIMUMeasurement / newTOAM
 PLANAR_EVENT_TOA = 0  # kfpos_run_planar_events_dev: newTOAMeasurement; the other kinds are SENSOR_PX4FLOW .. SENSOR_COMPASS
 SLOT_DT_PER_TAG, SLOT_REUSE_ERR, SLOT_REUSE_COV, SLOT_NO_POSE = 0x100, 0x200, 0x400, 0x800
 SLOT_POSE_COV = 0x1000  # slot_submit_rows only: the round also returns cov3x3 and vel of its tags (slot_pose_rows)
+SLOT_RANGES_D16 = 0x2000  # slot_submit only: the ranges travel as int16 codes + an escape list (slot_delta, kfpos_d16.h)
+D16_ABSENT, D16_ESCAPE, D16_DELTA_MIN, D16_DELTA_MAX = -32768, -32767, -32766, 32767
 
 
 class KfposError(RuntimeError):
@@ -88,6 +91,12 @@ class _RowsSlot(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("range_mm", C.c_void_p), ("err_est", C.c_void_p), ("accel", C.c_void_p),
                 ("cov", C.c_void_p), ("dt", C.c_void_p), ("status", C.c_void_p), ("pos", C.c_void_p),
                 ("capacity", C.c_int32)]
+
+
+class _DeltaSlot(C.Structure):
+    """kfpos_delta_slot: one slot opened for a D16 round (kfpos_d16.h)."""
+    _fields_ = [("code", C.c_void_p), ("esc", C.c_void_p), ("n_esc", C.c_void_p), ("esc_capacity", C.c_int32),
+                ("base", C.c_void_p), ("n_tags", C.c_int32), ("max_anchors", C.c_int32)]
 
 
 class PlanarInputs(C.Structure):
@@ -173,6 +182,8 @@ def load():
     sig("kfpos_get_pose_rows", [vp, vp, i32, vp, i32, vp, vp, vp, vp])
     sig("kfpos_get_predicted_rows", [vp, vp, i32, vp, i32, vp, vp, vp])
     sig("kfpos_slot_pose_rows", [vp, i32, C.POINTER(vp), C.POINTER(vp)])
+    sig("kfpos_slot_delta", [vp, i32, C.POINTER(_DeltaSlot)])
+    sig("kfpos_slot_encode_ranges", [vp, i32, i32])
     sig("kfpos_timing_begin", [vp, vp])
     sig("kfpos_timing_end", [vp, vp, C.POINTER(C.c_float)])
     i64 = C.c_int64
@@ -564,6 +575,27 @@ class KfposBank:
             return np.frombuffer(buf, dtype=np.float64, count=cnt).reshape(shape)
 
         return view(cov.value, (int(n), 3, 3)), view(vel.value, (int(n), 3))
+
+    def slot_delta(self, slot):
+        """Open an acquired slot for a D16 round (submit it with SLOT_RANGES_D16): numpy views over the slot's pinned
+        memory and the handle's host mirror: dict(code (A, T) int16, esc (cap, 2) int32: flat index, value, n_esc (1,)
+        int32, base (A, T) int32). Codes and the encoder's rule: include/kfpos_d16.h."""
+        sl = _DeltaSlot()
+        self._chk(self.lib.kfpos_slot_delta(self._h, slot, C.byref(sl)))
+        T, A = self.T, self.A
+
+        def view(ptr, shape, dtype):
+            n = int(np.prod(shape))
+            buf = (C.c_char * (n * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dtype, count=n).reshape(shape)
+
+        return {"code": view(sl.code, (A, T), np.int16), "esc": view(sl.esc, (sl.esc_capacity, 2), np.int32),
+                "n_esc": view(sl.n_esc, (1,), np.int32), "base": view(sl.base, (A, T), np.int32)}
+
+    def slot_encode_ranges(self, slot, flags=0):
+        """Encode the open slot's range_mm into its codes and escape list (with SLOT_DT_PER_TAG in flags: tags whose
+        slot dt < 0 are left out)."""
+        self._chk(self.lib.kfpos_slot_encode_ranges(self._h, slot, int(flags)))
 
     # ---- device-buffer API (pointers: ints or torch tensors; layouts in include/kfpos.h) ----
     def step_toa_dev(self, range_mm, err_est, dt, status=None, stream=None, dt_dev=None):

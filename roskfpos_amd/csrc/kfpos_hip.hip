@@ -412,12 +412,15 @@ int kfpos_destroy(kfpos_handle *h) {
         if (sl.rows) (void)hipHostFree(sl.rows);
         if (sl.pose_host) (void)hipHostFree(sl.pose_host);
         if (sl.pose_dev) (void)hipFree(sl.pose_dev);
+        if (sl.d16_host) (void)hipHostFree(sl.d16_host);
+        if (sl.d16_dev) (void)hipFree(sl.d16_dev);
         if (sl.dev) (void)hipFree(sl.dev);
         if (sl.copied) (void)hipEventDestroy(sl.copied);
         if (sl.copied2) (void)hipEventDestroy(sl.copied2);
         if (sl.computed) (void)hipEventDestroy(sl.computed);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
+    if (h->d16_base) (void)hipFree(h->d16_base);
     if (h->s_copy) (void)hipStreamDestroy(h->s_copy);
     if (h->s_copy2) (void)hipStreamDestroy(h->s_copy2);
     if (h->s_comp) (void)hipStreamDestroy(h->s_comp);

@@ -1,7 +1,8 @@
 /*
  * kfpos_hip_slots.hip -- the streaming host API of libkfpos_hip.so (kfpos.h: kfpos_slot_*): KFPOS_N_SLOTS slots of pinned
  * host + device buffers and three streams, so that the upload of one round, the step of the one before and the return of
- * the one before that overlap. Whole-bank rounds and row-list rounds share the acquire, the round's part of the argument
+ * the one before that overlap (a whole-bank round may carry its ranges as int16 codes, KFPOS_SLOT_RANGES_D16: d16_*, below,
+ * and kfpos_k_d16.hip). Whole-bank rounds and row-list rounds share the acquire, the round's part of the argument
  * block and the third stage; what a round may feed is decided by round_check, the row-list machinery (rows_check,
  * rows_reserve, rows_step) lives in kfpos_hip.hip, the lifecycle code it is built on in kfpos_hip_state.hip (kfpos_kernels.h
  * declares both).
@@ -99,6 +100,81 @@ int submit_return(kfpos_handle *h, kfpos_handle::Slot &sl, Copies copies) {
     return KFPOS_OK;
 }
 
+/* ---- KFPOS_SLOT_RANGES_D16 (kfpos.h, kfpos_d16.h) ---- */
+/* the D16 blocks, allocated by the handle's first kfpos_slot_delta: per slot code | esc, pinned and on the device; per
+ * handle the mirror and the device base, both zero */
+int d16_init(kfpos_handle *h) {
+    if (h->d16_base) return KFPOS_OK;
+    const size_t n = (size_t)h->cfg.max_anchors * h->cfg.n_tags;
+    h->d16 = kfpos_layout::delta_layout(handle_sizes(h));
+    for (auto &sl : h->slot) {
+        if (!sl.d16_host) {
+            HIPCHK(hipHostMalloc((void **)&sl.d16_host, h->d16.bytes, hipHostMallocDefault));
+            std::memset(sl.d16_host, 0, h->d16.bytes);
+        }
+        if (!sl.d16_dev) {
+            HIPCHK(hipMalloc((void **)&sl.d16_dev, h->d16.bytes));
+            HIPCHK(hipMemset(sl.d16_dev, 0, h->d16.bytes));
+        }
+    }
+    h->d16_mirror.assign(n, 0);
+    int32_t *base = nullptr;
+    HIPCHK(hipMalloc((void **)&base, n * sizeof(int32_t)));
+    if (hipMemset(base, 0, n * sizeof(int32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(base);
+        g_err = "kfpos_slot_delta: clearing the device base failed";
+        return KFPOS_ERR_HIP;
+    }
+    h->d16_base = base;
+    return KFPOS_OK;
+}
+
+kfpos_delta_slot d16_view(kfpos_handle *h, kfpos_handle::Slot &sl) {
+    const int64_t n = (int64_t)h->cfg.max_anchors * h->cfg.n_tags;
+    return kfpos_delta_slot{(int16_t *)(sl.d16_host + h->d16.code), (int32_t *)(sl.d16_host + h->d16.esc), &sl.n_esc,
+                            (int32_t)n, h->d16_mirror.data(), h->cfg.n_tags, h->cfg.max_anchors};
+}
+
+/* the escape list of a D16 round, in O(n_esc), before anything is enqueued: the kernel never sees an unchecked index.
+ * dt: the slot's per-tag dt (the entries of a tag whose dt < 0 are not read beyond their index) or null */
+int d16_check(const kfpos_handle *h, const kfpos_handle::Slot &sl, int32_t n_esc, const double *dt) {
+    const int64_t n = (int64_t)h->cfg.max_anchors * h->cfg.n_tags, T = h->cfg.n_tags;
+    if (n_esc < 0 || (int64_t)n_esc > n) {
+        g_err = "kfpos_slot_submit: KFPOS_SLOT_RANGES_D16: n_esc = " + std::to_string(n_esc) + " is outside [0, " + std::to_string(n) + "] (the escape list's capacity)";
+        return KFPOS_ERR_ARG;
+    }
+    const int16_t *code = (const int16_t *)(sl.d16_host + h->d16.code);
+    const int32_t *esc = (const int32_t *)(sl.d16_host + h->d16.esc);
+    int64_t prev = -1;
+    for (int32_t k = 0; k < n_esc; ++k) {
+        const int64_t i = esc[2 * (size_t)k];
+        const int32_t v = esc[2 * (size_t)k + 1];
+        const char *what = nullptr;
+        if (i < 0 || i >= n) what = " lies outside the matrix";
+        else if (i <= prev) what = " does not ascend (the list is strictly ascending by index)";
+        else if (dt && dt[i % T] < 0.0) what = nullptr; /* a skipped tag's entry is not read */
+        else if (code[i] != KFPOS_D16_ESCAPE) what = " points at a code that is not KFPOS_D16_ESCAPE";
+        else if (v <= 0) what = " carries a value <= 0 (an absent range is KFPOS_D16_ABSENT)";
+        if (what) {
+            g_err = "kfpos_slot_submit: KFPOS_SLOT_RANGES_D16: escape entry " + std::to_string(k) + ": index " + std::to_string(i) + what;
+            return KFPOS_ERR_ARG;
+        }
+        prev = i;
+    }
+    return KFPOS_OK;
+}
+
+/* a slot's submit has ended: an open slot is closed, and the base restarts at the next kfpos_slot_delta unless this
+ * was a D16 round that went through (kfpos.h, "RESTART RULE") */
+void d16_close(kfpos_handle *h, int32_t slot, bool d16_round, int rc) {
+    if (h->d16_open == slot) {
+        h->d16_open = -1;
+        if (!d16_round || rc != KFPOS_OK) h->d16_restart = true;
+    } else if (d16_round && rc != KFPOS_OK) h->d16_restart = true;
+}
+
+int submit_whole(kfpos_handle *h, int32_t slot, int32_t flags, double dt_shared);
+
 } // namespace
 
 extern "C" {
@@ -119,9 +195,30 @@ int kfpos_slot_submit(kfpos_handle *h, int32_t slot, int32_t flags, double dt_sh
     g_err.clear();
     if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
     DevScope dev_(h->cfg.device);
+    const bool d16 = (flags & KFPOS_SLOT_RANGES_D16) != 0;
+    int rc = KFPOS_OK;
+    if (d16 && (flags & 0xff) == KFPOS_SLOT_IMU) {
+        g_err = "kfpos_slot_submit: KFPOS_SLOT_RANGES_D16 on a round without ranging (KFPOS_SLOT_IMU)";
+        rc = KFPOS_ERR_ARG;
+    } else if (d16 && h->d16_open != slot) {
+        g_err = "kfpos_slot_submit: KFPOS_SLOT_RANGES_D16: open the slot first (kfpos_slot_delta)";
+        rc = KFPOS_ERR_STATE;
+    }
+    if (rc == KFPOS_OK) rc = submit_whole(h, slot, flags, dt_shared);
+    d16_close(h, slot, d16, rc);
+    return rc;
+}
+
+} // extern "C"
+
+namespace {
+
+int submit_whole(kfpos_handle *h, int32_t slot, int32_t flags, double dt_shared) {
+    const bool d16 = (flags & KFPOS_SLOT_RANGES_D16) != 0;
     Round r;
     const int rc = submit_head(h, slot, flags, false, r);
     if (rc) return rc;
+    int rc_d16 = KFPOS_OK;
     auto &sl = h->slot[slot];
     const auto &so = h->so;
     const size_t T = h->cfg.n_tags, A = h->cfg.max_anchors, m = h->msz;
@@ -130,6 +227,9 @@ int kfpos_slot_submit(kfpos_handle *h, int32_t slot, int32_t flags, double dt_sh
         return KFPOS_OK;
     }
     if (r.answer) return round_refusal(r.answer);
+    const double *slot_dt = (const double *)(sl.host + so.dt);
+    const int32_t n_esc = sl.n_esc; /* read once: what is checked is what is copied and decoded */
+    if (d16 && (rc_d16 = d16_check(h, sl, n_esc, (flags & KFPOS_SLOT_DT_PER_TAG) ? slot_dt : nullptr))) return rc_d16;
     /* 1. inputs: pinned host -> device on the copy stream. A complete fused epoch is one contiguous block of the slot
      * (ranges | err | accel | cov | dt): one DMA instead of five. Measured on this platform (tools/exp/h2d_probe.hip,
      * profiles/r02g_*): a lone 7.3 MB copy moves at 27-35 GB/s while the GPU is otherwise idle and at 53 GB/s while a
@@ -161,14 +261,19 @@ int kfpos_slot_submit(kfpos_handle *h, int32_t slot, int32_t flags, double dt_sh
     }
     if (up_err && sl.err_reader) HIPCHK(guard(sl.err_reader));
     if (up_cov && sl.cov_reader) HIPCHK(guard(sl.cov_reader));
+    /* a D16 round: the block's upload starts behind the ranges region, which the decode kernel fills on the device */
     if (up_err && up_cov) { /* the whole block in one go */
         const size_t end = (flags & KFPOS_SLOT_DT_PER_TAG) ? so.dt + T * sizeof(double) : so.cov + 9 * T * m;
-        HIPCHK(h2d(so.ranges, end - so.ranges));
+        const size_t from = d16 ? so.err : so.ranges;
+        HIPCHK(h2d(from, end - from));
     } else {
-        if (r.has_rng) HIPCHK(h2d(so.ranges, up_err ? so.err + A * T * m - so.ranges : A * T * sizeof(int32_t)));
+        if (r.has_rng && !d16) HIPCHK(h2d(so.ranges, up_err ? so.err + A * T * m - so.ranges : A * T * sizeof(int32_t)));
+        if (r.has_rng && d16 && up_err) HIPCHK(h2d(so.err, A * T * m));
         if (r.has_imu) HIPCHK(h2d(so.accel, up_cov ? so.cov + 9 * T * m - so.accel : 3 * T * m));
         if (flags & KFPOS_SLOT_DT_PER_TAG) HIPCHK(h2d(so.dt, T * sizeof(double)));
     }
+    if (d16) /* code | the pairs in use: neighbours, one copy */
+        HIPCHK(hipMemcpyAsync(sl.d16_dev, sl.d16_host, h->d16.esc + (size_t)n_esc * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->s_copy));
     if (up_err) h->err_slot = slot;
     if (up_cov) h->cov_slot = slot;
     HIPCHK(hipEventRecord(sl.copied, h->s_copy));
@@ -176,6 +281,14 @@ int kfpos_slot_submit(kfpos_handle *h, int32_t slot, int32_t flags, double dt_sh
     /* 2. the step, on the compute stream (submissions run in order: the filter state is sequential) */
     HIPCHK(hipStreamWaitEvent(h->s_comp, sl.copied, 0));
     if (second) HIPCHK(hipStreamWaitEvent(h->s_comp, sl.copied2, 0));
+    if (d16) { /* codes -> the slot's device ranges region and the device base, ahead of the step on the same stream */
+        const kfpos_k::D16Args g = {(const int16_t *)(sl.d16_dev + h->d16.code), (const int32_t *)(sl.d16_dev + h->d16.esc),
+                                    (uint32_t)n_esc, (uint32_t)(A * T), (uint32_t)T,
+                                    (flags & KFPOS_SLOT_DT_PER_TAG) ? (const double *)(sl.dev + so.dt) : nullptr,
+                                    h->d16_base, (int32_t *)(sl.dev + so.ranges)};
+        kfpos_k::launch_decode_d16(h->s_comp, g);
+        HIPCHK(hipGetLastError());
+    }
     const RoundIn in = {(const int32_t *)(sl.dev + so.ranges), r.has_rng ? h->slot[h->err_slot].dev + so.err : nullptr,
                         sl.dev + so.accel, r.has_imu ? h->slot[h->cov_slot].dev + so.cov : nullptr, nullptr};
     const bool want_pose = !(flags & KFPOS_SLOT_NO_POSE);
@@ -195,6 +308,65 @@ int kfpos_slot_submit(kfpos_handle *h, int32_t slot, int32_t flags, double dt_sh
     });
 }
 
+} // namespace
+
+extern "C" {
+
+int kfpos_slot_delta(kfpos_handle *h, int32_t slot, kfpos_delta_slot *out) {
+    g_err.clear();
+    if (!h || !out || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
+    DevScope dev_(h->cfg.device);
+    const int64_t n = (int64_t)h->cfg.max_anchors * h->cfg.n_tags;
+    if (n > INT32_MAX) {
+        g_err = "kfpos_slot_delta: max_anchors * n_tags exceeds INT32_MAX (flat indices are int32)";
+        return KFPOS_ERR_ARG;
+    }
+    auto &sl = h->slot[slot];
+    if (!h->s_copy || sl.busy) {
+        g_err = "kfpos_slot_delta: acquire the slot first (kfpos_slot_acquire)";
+        return KFPOS_ERR_STATE;
+    }
+    if (h->d16_open >= 0 && h->d16_open != slot) {
+        g_err = "kfpos_slot_delta: slot " + std::to_string(h->d16_open) + " is open (one D16 round is encoded at a time: submit it first)";
+        return KFPOS_ERR_STATE;
+    }
+    if (h->d16_open == slot) h->d16_restart = true; /* opened again: the mirror may have moved for a round never sent */
+    const int rc = d16_init(h);
+    if (rc) return rc;
+    if (h->d16_restart) { /* behind every decode already queued, ahead of the next one */
+        HIPCHK(hipMemsetAsync(h->d16_base, 0, (size_t)n * sizeof(int32_t), h->s_comp));
+        std::memset(h->d16_mirror.data(), 0, (size_t)n * sizeof(int32_t));
+        h->d16_restart = false;
+    }
+    sl.n_esc = 0;
+    h->d16_open = slot;
+    *out = d16_view(h, sl);
+    return KFPOS_OK;
+}
+
+int kfpos_slot_encode_ranges(kfpos_handle *h, int32_t slot, int32_t flags) {
+    g_err.clear();
+    if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
+    if (h->d16_open != slot) {
+        g_err = "kfpos_slot_encode_ranges: open the slot first (kfpos_slot_delta)";
+        return KFPOS_ERR_STATE;
+    }
+    auto &sl = h->slot[slot];
+    const kfpos_delta_slot d = d16_view(h, sl);
+    const int32_t *r = (const int32_t *)(sl.host + h->so.ranges);
+    const double *dt = (flags & KFPOS_SLOT_DT_PER_TAG) ? (const double *)(sl.host + h->so.dt) : nullptr;
+    const int64_t T = h->cfg.n_tags, A = h->cfg.max_anchors;
+    for (int64_t a = 0; a < A; ++a) /* ascending flat index: the escape list comes out sorted */
+        for (int64_t t = 0; t < T; ++t) {
+            if (dt && dt[t] < 0.0) continue;
+            if (kfpos_d16_put(&d, a * T + t, r[a * T + t])) {
+                g_err = "kfpos_slot_encode_ranges: the escape list is full (elements were put before the call)";
+                return KFPOS_ERR_STATE;
+            }
+        }
+    return KFPOS_OK;
+}
+
 int kfpos_slot_wait(kfpos_handle *h, int32_t slot) {
     g_err.clear();
     if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
@@ -211,6 +383,12 @@ int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t
     g_err.clear();
     if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
     DevScope dev_(h->cfg.device);
+    d16_close(h, slot, false, KFPOS_OK); /* an open slot sent as a row list: its D16 round is abandoned */
+    if (flags & KFPOS_SLOT_RANGES_D16) {
+        h->d16_restart = true;
+        g_err = "kfpos_slot_submit_rows: KFPOS_SLOT_RANGES_D16 belongs to whole-bank rounds (row lists stay int32)";
+        return KFPOS_ERR_ARG;
+    }
     Round r;
     int rc = submit_head(h, slot, flags, true, r);
     if (rc) return rc;

@@ -1,6 +1,6 @@
 /*
  * kfpos_host_layout.h -- the byte layouts of the three blocks the host side carves up by offset: the mapped block of a
- * small bank, the pinned / device block of a streaming slot, and the device block of the row-list steps. Pure arithmetic
+ * small bank, the pinned / device block of a streaming slot (and its D16 block), and the device block of the row-list steps. Pure arithmetic
  * on the handle's sizes: no HIP header, g++ compiles it alone (tests/layout/layout_driver.cpp checks that the regions are
  * aligned, disjoint and inside the block -- the copy stream runs ahead of the compute stream on the strength of that).
  */
@@ -68,6 +68,21 @@ inline Slot slot_layout(const Sizes &s) {
     L.dt = b.region(s.T * sizeof(double));
     L.status = b.region(s.T * sizeof(uint32_t));
     L.pos = b.region(3 * s.T * sizeof(double));
+    L.bytes = b.off;
+    return L;
+}
+
+/* the D16 block of a streaming slot (KFPOS_SLOT_RANGES_D16), pinned host and device alike, beside the slot's own block:
+ * one int16 code per range element, then the escape list at full capacity ((flat index, value) int32 pairs). Neighbours,
+ * so that one copy moves the codes and the pairs in use */
+struct Delta {
+    size_t code, esc, bytes;
+};
+inline Delta delta_layout(const Sizes &s) {
+    Bump b;
+    Delta L{};
+    L.code = b.region(s.A * s.T * sizeof(int16_t));
+    L.esc = b.region(s.A * s.T * 2 * sizeof(int32_t));
     L.bytes = b.off;
     return L;
 }

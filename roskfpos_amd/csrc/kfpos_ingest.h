@@ -42,10 +42,16 @@
  * each call appends its row and one contiguous record, only the reporters' bytes cross the bus, and the GPU steps a
  * compact copy of them. Same filters, bit for bit; which mode is cheaper depends on the fraction of the bank that
  * reports per round.
+ *
+ * setDeltaRanges(true): whole-bank ranging rounds carry their ranges as 16-bit deltas (KFPOS_SLOT_RANGES_D16, kfpos_d16.h):
+ * the round's slot is opened with kfpos_slot_delta and a flushed epoch is written as codes through kfpos_d16_put instead
+ * of int32 ranges -- half the bytes of the largest array a round uploads; silent tags keep their stale codes (dt < 0:
+ * not read). Same filters, bit for bit. Sparse rounds ignore the switch: row lists stay int32.
  */
 #ifndef KFPOS_INGEST_H
 #define KFPOS_INGEST_H
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -221,6 +227,13 @@ public:
         sparse_ = on;
     }
     bool sparseRounds() const { return sparse_; }
+    /* Delta ranges (off by default): whole-bank ranging rounds go up as int16 codes -- see the head of this file. May be
+     * switched whenever no call is pending, like setSparseRounds. */
+    void setDeltaRanges(bool on) {
+        requireIdle("setDeltaRanges");
+        delta_ = on;
+    }
+    bool deltaRanges() const { return delta_; }
     /* Status words, if anybody wants them: sink(row, kind, status) for every estimator call made (kind 0 = ranging
      * epoch, KFPOS_SENSOR_* otherwise), in the order the calls were placed. A round's words are delivered when its slot
      * is taken again, or by deliverStatuses(), which waits for everything in flight. */
@@ -466,6 +479,7 @@ private:
                 check(kfpos_slot_acquire_rows(h_, s, &rslot_[s]), "kfpos_slot_acquire_rows"); /* waits for its previous round */
                 deliver(s);
                 rowsN_[s] = 0;
+                slotDelta_[s] = false;
                 slotInit_[s] = false; /* its dt array no longer holds -1 everywhere */
             } else {
                 check(kfpos_slot_acquire(h_, s, &slot_[s]), "kfpos_slot_acquire"); /* waits for its previous round */
@@ -476,6 +490,8 @@ private:
                 } else {
                     for (int t : written_[s]) slot_[s].dt[t] = -1.0;
                 }
+                slotDelta_[s] = kind == 0 && delta_;
+                if (slotDelta_[s]) check(kfpos_slot_delta(h_, s, &dslot_), "kfpos_slot_delta"); /* one ranging round is assembled at a time */
             }
             written_[s].clear();
             roundSlot_[kind] = s;
@@ -524,8 +540,14 @@ private:
                 std::memcpy((double *)sl.cov + i * 9, sample + 15, sizeof(double) * 9);
             }
         } else if (kind == 0) {
-            kfpos_epoch_slot &sl = slot_[slotFor(0)];
-            for (int a = 0; a < A_; ++a) sl.range_mm[(size_t)a * T + row] = mm[a] > 0 ? mm[a] : 0; /* only entries > 0 (:483) */
+            const int s = slotFor(0);
+            kfpos_epoch_slot &sl = slot_[s];
+            if (slotDelta_[s]) { /* a tag is placed once per round: every element is put at most once; <= 0 is ABSENT */
+                for (int a = 0; a < A_; ++a)
+                    if (kfpos_d16_put(&dslot_, (int64_t)a * T_ + row, mm[a])) throw std::logic_error("kfpos_d16_put: the escape list is full");
+            } else {
+                for (int a = 0; a < A_; ++a) sl.range_mm[(size_t)a * T + row] = mm[a] > 0 ? mm[a] : 0; /* only entries > 0 (:483) */
+            }
             if (real_ == 4) {
                 float *e = (float *)sl.err_est;
                 for (int a = 0; a < A_; ++a) e[(size_t)a * T + row] = (float)err[a];
@@ -564,7 +586,11 @@ private:
         for (const auto &k : kSlotKind) {
             const int s = roundSlot_[k[0]];
             if (s < 0) continue;
-            const int flags = k[1] | KFPOS_SLOT_DT_PER_TAG | KFPOS_SLOT_NO_POSE;
+            int flags = k[1] | KFPOS_SLOT_DT_PER_TAG | KFPOS_SLOT_NO_POSE;
+            if (!sparse_ && k[0] == 0 && slotDelta_[s]) {
+                sortEscapes();
+                flags |= KFPOS_SLOT_RANGES_D16;
+            }
             if (sparse_) check(kfpos_slot_submit_rows(h_, s, flags, rowsN_[s], 0.0), "kfpos_slot_submit_rows");
             else check(kfpos_slot_submit(h_, s, flags, 0.0), "kfpos_slot_submit");
             flightKind_[s] = k[0];
@@ -595,6 +621,22 @@ private:
         sensKinds_.clear();
         for (int r : touched_) taken_[r] = 0;
         touched_.clear();
+    }
+
+    /* tags are placed in arrival order, the escape list of a D16 round ascends by flat index: put it in order */
+    void sortEscapes() {
+        const int32_t n = *dslot_.n_esc;
+        int32_t *e = dslot_.esc;
+        bool sorted = true;
+        for (int32_t k = 1; k < n && sorted; ++k) sorted = e[2 * k] > e[2 * (k - 1)];
+        if (sorted) return;
+        escKeys_.resize((size_t)n);
+        for (int32_t k = 0; k < n; ++k) escKeys_[k] = ((int64_t)e[2 * k] << 32) | (uint32_t)e[2 * k + 1];
+        std::sort(escKeys_.begin(), escKeys_.end());
+        for (int32_t k = 0; k < n; ++k) {
+            e[2 * k] = (int32_t)(escKeys_[k] >> 32);
+            e[2 * k + 1] = (int32_t)(uint32_t)escKeys_[k];
+        }
     }
 
     /* A round takes at most one pending call per tag, in arrival order, and makes one submission per kind
@@ -650,6 +692,10 @@ private:
     /* sparse rounds: the same slots as row lists, and how many rows the round in each holds */
     static_assert(sizeof(int) == sizeof(int32_t), "row lists are int32_t");
     bool sparse_ = false;
+    /* delta ranges: is the ranging round in a slot a D16 round, and the one that is open */
+    bool delta_ = false, slotDelta_[kMaxSlots] = {false};
+    kfpos_delta_slot dslot_ = {};
+    std::vector<int64_t> escKeys_;
     kfpos_rows_slot rslot_[kMaxSlots];
     int rowsN_[kMaxSlots] = {0};
     /* what each slot has in flight (kind, -1 = nothing to deliver; assembled as a row list?) and who listens */

@@ -90,7 +90,18 @@ struct kfpos_handle {
          * 9 * n_tags doubles, pinned and on the device; pose_round: the slot's last row-list round filled them */
         double *pose_host = nullptr, *pose_dev = nullptr;
         bool pose_round = false;
+        /* KFPOS_SLOT_RANGES_D16, allocated by the handle's first kfpos_slot_delta: code | esc (kfpos_layout::Delta),
+         * pinned and on the device; n_esc: what kfpos_delta_slot::n_esc points at */
+        unsigned char *d16_host = nullptr, *d16_dev = nullptr;
+        int32_t n_esc = 0;
     } slot[KFPOS_N_SLOTS];
+    /* the base of the D16 rounds: host mirror and device copy [max_anchors][n_tags]; d16_open: the slot kfpos_slot_delta
+     * opened, or -1; d16_restart: the next kfpos_slot_delta zeroes both sides first */
+    std::vector<int32_t> d16_mirror;
+    int32_t *d16_base = nullptr;
+    kfpos_layout::Delta d16 = {};
+    int d16_open = -1;
+    bool d16_restart = false;
     kfpos_layout::Slot so = {};
     hipStream_t s_copy = nullptr, s_copy2 = nullptr, s_comp = nullptr, s_back = nullptr;
     size_t split_bytes = 0;                            /* H2D copies from this size on travel as two halves on two streams */

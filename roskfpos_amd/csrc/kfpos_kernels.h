@@ -26,7 +26,7 @@
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
  * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
- * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_hip (host side + C ABI), kfpos_hip_state (the state side of the C ABI: whole-bank accessors, per-tag lifecycle, pose for a row list), kfpos_hip_slots (the streaming slots of the C ABI, kfpos_slot_*), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
+ * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_k_d16 (the decoder of KFPOS_SLOT_RANGES_D16 rounds), kfpos_hip (host side + C ABI), kfpos_hip_state (the state side of the C ABI: whole-bank accessors, per-tag lifecycle, pose for a row list), kfpos_hip_slots (the streaming slots of the C ABI, kfpos_slot_*), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
 #define KFPOS_KERNELS_H
@@ -228,6 +228,18 @@ void launch_tags(int op, int st, hipStream_t s, const TagArgs &a);          /* k
 /* TAGS_WORK_IN: work[c][i] = bank[c][rows[i]] for every stored row c listed in comp[] (n_comp of them, the list reset
  * uses) and the flags word, raw stored bits; TAGS_WORK_OUT: the inverse. The step kernels then run on the work bank
  * with KArgs::T = n: they never see a row index. */
+
+/* ---- k_decode_d16 (kfpos_k_d16.hip): the int16 codes and the escape list of a KFPOS_SLOT_RANGES_D16 round -> the int32
+ * range matrix and the moved base (kfpos_d16.h). n = max_anchors * n_tags elements, flat; the escape indices have been
+ * validated by the host */
+struct D16Args {
+    const int16_t *code; /* [n], 16-byte aligned */
+    const int32_t *esc;  /* [n_esc][2]: flat index, value; 8-byte aligned */
+    uint32_t n_esc, n, T;
+    const double *dt;    /* [T] per-tag dt of the round (< 0: the tag's codes and entries are not read), or null */
+    int32_t *base, *out; /* [n] each, 16-byte aligned */
+};
+void launch_decode_d16(hipStream_t s, const D16Args &a);                    /* kfpos_k_d16.hip */
 
 constexpr int COOP_LANES = 8;                   /* kfpos_k_coop.hip: one tag per group of 8 lanes */
 constexpr int COOP_TAGS_PER_WAVE = 64 / COOP_LANES;

@@ -10,6 +10,11 @@
   slots+fill  the same, with a CPU producer that copies each epoch's 7.3 MB into the slot before submitting (numpy
             memcpy: the producer, not the library, is the bound here)
   reuse     `slots` with KFPOS_SLOT_REUSE_ERR | KFPOS_SLOT_REUSE_COV (constant errorEstimation / sensor covariance)
+  d16       `slots` with KFPOS_SLOT_RANGES_D16: the int16 codes and the escape list already in the slot, as `slots` has
+            its ranges (the slots' epochs repeat, so each slot's codes against the slot before it are the same every
+            time round); the round uploads code | escapes instead of the int32 ranges and runs k_decode_d16 ahead of
+            the step. `d16reuse`: the same on top of `reuse`. Named in --modes only: the default output is what it
+            always was. Their entries carry the bytes a round uploads, computed from the shapes
 
   --sparse F  adds the row-list entry points for a round in which a fraction F of the tags reports (rows spread over
             the bank): `rows_sync` = kfpos_step_*_rows from pageable arrays, `rows_slots` = kfpos_slot_submit_rows
@@ -79,7 +84,7 @@ cm = [(np.ascontiguousarray(r.T), np.ascontiguousarray(ac.T)) for r, ac, _ in in
 err_cm, cov_cm = np.ascontiguousarray(err.T), np.ascontiguousarray(cov.T)
 
 
-def stream(fill, reuse, want_pose=True):
+def stream(fill, reuse, want_pose=True, d16=False):
     bank = new_bank()
     kind = capi.SLOT_TOA_IMU if imu else capi.SLOT_TOA
     NS = bank.lib.kfpos_slot_count(bank._h)
@@ -89,9 +94,14 @@ def stream(fill, reuse, want_pose=True):
         v["err_est"][:] = err_cm
         v["accel"][:] = cm[k][1]
         v["cov"][:] = cov_cm
-    flags = kind | (0 if want_pose else capi.SLOT_NO_POSE)
+    flags = kind | (0 if want_pose else capi.SLOT_NO_POSE) | (capi.SLOT_RANGES_D16 if d16 else 0)
+    n_esc, delta, ds = [0] * NS, [None] * NS, capi._DeltaSlot() if d16 else None
     for s in range(2 * NS):         # warm-up, uploads err / cov at least once
         bank.slot_acquire(s % NS)
+        if d16:                     # the second time round every slot holds its codes against the slot before it
+            delta[s % NS] = bank.slot_delta(s % NS)
+            bank.slot_encode_ranges(s % NS)
+            n_esc[s % NS] = int(delta[s % NS]["n_esc"][0])
         bank.slot_submit(s % NS, flags, 0.1 if s == 0 else 0.05)
     for k in range(NS):
         bank.slot_wait(k)
@@ -110,6 +120,9 @@ def stream(fill, reuse, want_pose=True):
             if not reuse:
                 v["err_est"][:] = err_cm
                 v["cov"][:] = cov_cm
+        if d16:                     # open the slot; its codes and pairs are where the warm-up left them
+            bank._chk(bank.lib.kfpos_slot_delta(bank._h, k, capi.C.byref(ds)))
+            delta[k]["n_esc"][0] = n_esc[k]
         bank.slot_submit(k, flags, 0.05)
     for k in range(NS):
         bank.slot_wait(k)
@@ -117,13 +130,23 @@ def stream(fill, reuse, want_pose=True):
     x, _, _ = bank.get_state()
     bank.close()
     assert np.isfinite(x).all() and np.isfinite(checksum)
-    return {"ms_per_epoch": el / S * 1e3, "tag_steps_per_s": T * S / el}
+    res = {"ms_per_epoch": el / S * 1e3, "tag_steps_per_s": T * S / el}
+    if d16:
+        rest = (0 if reuse else A * T * 4 + (9 * T * 4 if imu else 0)) + (3 * T * 4 if imu else 0)
+        res["upload_bytes_per_round"] = ((A * T * 2 + 255) & ~255) + 8 * max(n_esc) + rest
+        res["upload_bytes_per_round_int32_ranges"] = A * T * 4 + rest
+        res["escapes_per_round"] = n_esc
+    return res
 
 
 if "slots" in MODES:
     out["slots"] = stream(fill=False, reuse=False)
 if "reuse" in MODES:
     out["slots_reuse_err_cov"] = stream(fill=False, reuse=True)
+if "d16" in MODES:
+    out["slots_d16"] = stream(fill=False, reuse=False, d16=True)
+if "d16reuse" in MODES:
+    out["slots_d16_reuse_err_cov"] = stream(fill=False, reuse=True, d16=True)
 if "nopose" in MODES:
     out["slots_no_pose"] = stream(fill=False, reuse=True, want_pose=False)
 if "fill" in MODES:
