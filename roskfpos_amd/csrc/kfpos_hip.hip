@@ -1,5 +1,6 @@
 /*
- * kfpos_hip.hip -- host side of libkfpos_hip.so: the handle, launch selection, two of the three ways in
+ * kfpos_hip.hip -- host side of libkfpos_hip.so: the handle, the step launch (a Plan of kfpos_launch_plan.h as a kernel,
+ * its grid and its LDS bytes: launch selection itself lives there), two of the three ways in
  * (synchronous host-buffer API, device-buffer API) and the C ABI of include/kfpos.h. The kernels live in
  * kfpos_k_*.hip (kfpos_kernels.h says which is where); the state side of the ABI (whole-bank accessors, per-tag lifecycle,
  * pose for a row list) in kfpos_hip_state.hip; the streaming slots in kfpos_hip_slots.hip; the replay entry points
@@ -23,11 +24,6 @@ std::string &kfpos_error_text() {
 }
 
 /* ------------------------------------------------------------------ host side */
-/* shared with kfpos_hip_replay.hip (declared in kfpos_kernels.h) */
-size_t lds_bytes(const kfpos_handle *h) { return (size_t)3 * h->cfg.max_anchors * WAVE * sizeof(double); }
-size_t park_bytes() { return (size_t)36 * WAVE * sizeof(double); } /* 36 doubles per lane: CovSpill8 (planar), Pinv6 (6-state, full) */
-size_t park9_bytes() { return (size_t)78 * WAVE * sizeof(double) + 24 * sizeof(double); } /* CovPark9: the 9-state covariance (45) and B^-1 (21) during the gain iteration, the accelerometer whitener and Sigma^-1 (12), a lane-addressable copy of 8 anchors: 39.2 KB per wavefront, four wavefronts per CU */
-
 void fill_args(const kfpos_handle *h, KArgs &a) {
     std::memcpy(a.anchors, h->anchors, sizeof(a.anchors));
     a.T = h->cfg.n_tags;
@@ -77,76 +73,26 @@ void fill_args(const kfpos_handle *h, KArgs &a) {
 
 namespace {
 
-/* Anchor-count specialisation. 8 anchors (BASELINE configs 2-4): epoch in registers (RegScratch), returns 8. 16 anchors
- * (config 5, 6-state): a register-resident epoch costs 96 more live registers and spills to scratch, which is no faster
- * than the run-time loop (measured in round 1), so the epoch stays in LDS and only the anchor loops are compile-time, in
- * groups of 8 (StaticScratch): returns -16. Everything else: 0, the run-time loop.
- * "No scratch" is a PERFORMANCE rule of this library (checked at build time), not a correctness crutch: round 1 saw
- * wrong, run-to-run varying positions from a work-in-progress build of the spilling 16-anchor kernel and dropped it
- * without a diagnosis. Round 2 could not reproduce that with the committed sources of either round -- the library as it
- * stood before that commit and today's kernels with the register-resident 16-anchor instantiations re-enabled
- * (236-960 bytes/lane of scratch) match the oracle and repeat bit for bit on full, partially filled and
- * skipped-lane wavefronts (tools/exp/, profiles/r02b_*) -- and a MemorySanitizer build of the kernel body with every
- * undefined input poisoned is clean (tests/emu/msan_audit.sh). DESIGN.md section 2. */
-/* the plain 8-anchor 6-state bank with more wavefronts than SIMDs: the two-wavefronts-per-SIMD build (k_step_toa6_w2) */
-bool toa6_two_waves(const kfpos_handle *h) {
-    return h->two_waves && h->cfg.model == KFPOS_MODEL_TOA && !h->full && !h->force_generic && !h->coop &&
-           h->cfg.max_anchors == 8 && h->cfg.ignore_worst == 0 && h->cfg.top_n == 0;
-}
-
-} // namespace
-
-int static_anchors(const kfpos_handle *h) {
-    if (h->cfg.max_anchors == 8) return 8;
-    /* 16 anchors (BASELINE config 5): compile-time loops over an LDS-resident epoch (StaticScratch), 6-state only */
-    if (h->cfg.max_anchors == 16 && h->cfg.model == KFPOS_MODEL_TOA) return -16;
-    return 0;
-}
-
-namespace {
-
-step_kernel_t step_kernel(const kfpos_handle *h, bool sensor_call = false, bool imu_only = false) {
-    const int st = h->cfg.storage, as = (h->force_generic || sensor_call) ? 0 : static_anchors(h);
-    if (h->cfg.model == KFPOS_MODEL_PLANAR) return kfpos_k::planar_kernel(st, h->planar_sensors || sensor_call, as);
-    if (h->cfg.model == KFPOS_MODEL_ML) return kfpos_k::ml_kernel(st, as);
+/* a step plan (kfpos_launch_plan.h) as the kernel it names: the covariance layout says which unit's selector is asked */
+step_kernel_t step_kernel(const kfpos_handle *h, const kfpos_plan::Plan &p) {
+    const int st = h->cfg.storage;
+    if (h->cfg.model == KFPOS_MODEL_PLANAR) return kfpos_k::planar_kernel(st, p.sensors, p.as);
+    if (h->cfg.model == KFPOS_MODEL_ML) return kfpos_k::ml_kernel(st, p.as);
+    if (h->cfg.model == KFPOS_MODEL_TOA_IMU) return kfpos_k::imu9_kernel(st, p.as, p.ranging);
     if (h->coop) return kfpos_k::toa6_coop_kernel(st);
-    if (h->cfg.model == KFPOS_MODEL_TOA) {
-        /* heur: 0 = the bank has no outlier heuristic (BASELINE configs 2 and 4), 1 = top-N only (config 5), 2 =
-         * leave-one-out (with or without top-N) */
-        const int heur = h->cfg.ignore_worst != 0 ? 2 : (h->cfg.top_n != 0 ? 1 : 0);
-        if (h->full) return kfpos_k::toa6_full_kernel(st, as, heur);
-        /* more wavefronts than SIMDs: the 256-register build of the plain kernel */
-        return kfpos_k::toa6_sym_kernel(st, as, heur, toa6_two_waves(h));
-    }
-    return kfpos_k::imu9_kernel(st, as, !imu_only);
+    return h->full ? kfpos_k::toa6_full_kernel(st, p.as, p.heur) : kfpos_k::toa6_sym_kernel(st, p.as, p.heur, p.two_waves);
 }
 
 } // namespace
 
-/* a.T tags: the whole bank, or the n tags of a work bank (row-list steps). WHICH kernel runs is a property of the handle,
- * never of a.T: a row-list step computes bit for bit what the whole-bank call does */
+/* a.T tags: the whole bank, or the n tags of a work bank (row-list steps). WHICH kernel runs is a property of the handle
+ * and of what the call feeds (a planar bank's a.mode is 0 or the sensor kind), never of a.T -- the plan is not told it: a
+ * row-list step computes bit for bit what the whole-bank call does */
 int launch_step(kfpos_handle *h, const KArgs &a, hipStream_t s) {
-    if (h->coop) {
-        const int groups = (a.T + COOP_TAGS_PER_WAVE - 1) / COOP_TAGS_PER_WAVE;
-        hipLaunchKernelGGL(step_kernel(h), dim3(groups), dim3(WAVE), 0, s, a);
-        HIPCHK(hipGetLastError());
-        h->stepped = true;
-        return KFPOS_OK;
-    }
-    const int blocks = (a.T + WAVE - 1) / WAVE;
-    /* does the selected kernel stage the epoch in LDS? */
-    const bool generic = h->force_generic || static_anchors(h) <= 0 || (h->cfg.model == KFPOS_MODEL_TOA && h->full) ||
-                         (h->cfg.model == KFPOS_MODEL_PLANAR && h->planar_sensors) || toa6_two_waves(h);
-    const bool planar_sensor = h->cfg.model == KFPOS_MODEL_PLANAR && a.mode != 0;
-    size_t lds = (a.mode == MODE_IMU_ONLY || planar_sensor || !generic) ? 0 : lds_bytes(h);
-    /* the 6-state compile-time-count kernels keep 4-byte errorEstimations as they are: 20 bytes per anchor and lane */
-    if (lds && h->cfg.model == KFPOS_MODEL_TOA && !h->force_generic && static_anchors(h) != 0 && h->msz == 4)
-        lds = lds * 5 / 6;
-    if (h->cfg.model == KFPOS_MODEL_PLANAR && (h->planar_sensors || planar_sensor)) lds += park_bytes();
-    if (h->cfg.model == KFPOS_MODEL_TOA && h->full) lds += park_bytes(); /* Pinv6 of the non-symmetric layout */
-    if (toa6_two_waves(h)) lds += (size_t)(h->msz == 4 ? 19 : 15) * WAVE * sizeof(double); /* covariance entries parked during the ML solve */
-    if (h->cfg.model == KFPOS_MODEL_TOA_IMU) lds += park9_bytes();
-    hipLaunchKernelGGL(step_kernel(h, planar_sensor, a.mode == MODE_IMU_ONLY && h->cfg.model == KFPOS_MODEL_TOA_IMU), dim3(blocks), dim3(WAVE), lds, s, a);
+    const bool planar = h->cfg.model == KFPOS_MODEL_PLANAR;
+    const kfpos_plan::Plan p = kfpos_plan::plan(plan_inputs(h), planar ? (a.mode != 0 ? kfpos_plan::STEP_SENSOR : kfpos_plan::STEP_RANGING)
+                                                                       : (a.mode == MODE_IMU_ONLY ? kfpos_plan::STEP_IMU_ONLY : kfpos_plan::STEP_RANGING));
+    hipLaunchKernelGGL(step_kernel(h, p), dim3(p.groups(a.T)), dim3(WAVE), p.bytes(), s, a);
     HIPCHK(hipGetLastError());
     h->stepped = true;
     return KFPOS_OK;
@@ -352,24 +298,15 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
         h->sm_h = (unsigned char *)hp;
         h->sm_d = (unsigned char *)dp;
     }
-    const bool parks = cfg->model == KFPOS_MODEL_PLANAR || (cfg->model == KFPOS_MODEL_TOA && h->full);
-    if (cfg->model == KFPOS_MODEL_TOA_IMU && lds_bytes(h) + park9_bytes() > 64 * 1024) {
-        hipError_t e_ = hipFuncSetAttribute((const void *)step_kernel(h), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)(lds_bytes(h) + park9_bytes()));
-        if (e_ != hipSuccess) {
-            g_err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(e_);
-            kfpos_destroy(h);
-            return KFPOS_ERR_HIP;
-        }
-    } else if (lds_bytes(h) + (parks ? park_bytes() : 0) > 64 * 1024) {
-        hipError_t e_ = hipFuncSetAttribute((const void *)step_kernel(h), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)(lds_bytes(h) + (h->full ? park_bytes() : 0)));
-        if (e_ == hipSuccess && cfg->model == KFPOS_MODEL_PLANAR) { /* the instantiation ranging epochs switch to */
-            h->planar_sensors = true;
-            e_ = hipFuncSetAttribute((const void *)step_kernel(h), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(lds_bytes(h) + park_bytes()));
-            h->planar_sensors = false;
-        }
+    /* every step launch this handle can ever make -- ranging, IMU-only, sensor call, ranging after a sensor sample --:
+     * a kernel whose plan takes more than 64 KB of LDS is allowed them here, once */
+    const kfpos_plan::Launch may[4] = {kfpos_plan::STEP_RANGING, kfpos_plan::STEP_IMU_ONLY, kfpos_plan::STEP_SENSOR, kfpos_plan::STEP_RANGING};
+    for (int k = 0; k < 4; ++k) {
+        kfpos_plan::Inputs in = plan_inputs(h);
+        in.planar_sensors = k == 3;
+        const kfpos_plan::Plan p = kfpos_plan::plan(in, may[k]);
+        if (p.bytes() <= 64 * 1024) continue;
+        hipError_t e_ = hipFuncSetAttribute((const void *)step_kernel(h, p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.bytes());
         if (e_ != hipSuccess) {
             g_err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(e_);
             kfpos_destroy(h);

@@ -3,8 +3,8 @@
  * launches. kfpos_run_trace_dev (ranging epochs, shared dt), kfpos_run_trace_each_dev (6-state, a timeline per tag),
  * kfpos_run_events_dev / _each_dev (9-state), kfpos_run_planar_events_dev / _each_dev (planar). Each of them is argument
  * checks plus what is its own; what they share is written once, above them: the validation of `kinds`, the two ranging
- * paths ahead of a replay kernel's first event, which kernel and how much LDS a family's replay takes, and the one loop
- * that launches. How a schedule is cut into launches and how `kinds` travels: kfpos_replay_plan.h. No kernel lives
+ * paths ahead of a replay kernel's first event, a family's replay plan (kfpos_launch_plan.h: form, grid, LDS bytes) as
+ * its kernel, and the one loop that launches. How a schedule is cut into launches and how `kinds` travels: kfpos_replay_plan.h. No kernel lives
  * here: like kfpos_hip.hip this unit obtains them through the selectors of kfpos_kernels.h.
  */
 #include <cstring>
@@ -118,44 +118,30 @@ int ranging_lead_each(kfpos_handle *h, int lead, int n_events, const double *dt_
     return lead > 0 && lead == n_events ? copy_last_status(h, n_events, status_events, status, s) : KFPOS_OK;
 }
 
-/* ---- which kernel and how much LDS a family's replay takes: the shared-timeline and the per-tag form alike ---- */
+/* ---- a family's replay plan (kfpos_launch_plan.h: the shared-timeline and the per-tag form alike) as its kernel ---- */
+using kfpos_plan::Plan;
+Plan replay_plan(const kfpos_handle *h, kfpos_plan::Launch what) { return kfpos_plan::plan(plan_inputs(h), what); }
 template <class K>
-int replay_kernel(K kern, size_t lds, K *out) {
-    if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+int replay_kernel(K kern, const Plan &p, K *out) {
+    if (p.bytes() > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.bytes()));
     *out = kern;
     return KFPOS_OK;
-}
-/* 9-state: CovPark9 alone (39.2 KB, four workgroups per CU); beside the generic epoch scratch of up to 64 anchors
- * 96 + 39.2 = 135.2 KB of the CU's 160 */
-template <class K>
-int imu9_replay_kernel(const kfpos_handle *h, K (*select)(int st, int as), K *kern, size_t *lds) {
-    const int as = (!h->force_generic && static_anchors(h) == 8) ? 8 : 0;
-    *lds = park9_bytes() + (as == 0 ? lds_bytes(h) : 0);
-    return replay_kernel(select(h->cfg.storage, as), *lds, kern);
-}
-/* planar: the epoch scratch (8 anchors: compile-time loops over it) and CovSpill8 behind it */
-template <class K>
-int planar_replay_kernel(const kfpos_handle *h, K (*select)(int st, int as), K *kern, size_t *lds) {
-    const int as = (!h->force_generic && static_anchors(h) == 8) ? -8 : 0;
-    *lds = park_bytes() + (as == 0 ? lds_bytes(h) : (size_t)3 * 8 * WAVE * sizeof(double));
-    return replay_kernel(select(h->cfg.storage, as), *lds, kern);
 }
 
 /* ---- the launch loop of every replay kernel: events [first, n_events), up to trace_chunk per launch ----
  * Sets what every argument block has -- the launch's event count, where its trajectory rows and per-event status words
  * start, the call's status on the last launch only --, then own(cut) fills in what is the caller's for this launch. */
 template <class K, class Args, class Own>
-int replay_launches(kfpos_handle *h, K kern, size_t lds, Args &ev, const uint8_t *kinds, int n_kinds, int first,
+int replay_launches(kfpos_handle *h, K kern, const Plan &p, Args &ev, const uint8_t *kinds, int n_kinds, int first,
                     int n_events, double *trajectory, uint32_t *status_events, uint32_t *status, hipStream_t s, Own own) {
     const size_t T = h->cfg.n_tags;
-    const int blocks = (int)((T + WAVE - 1) / WAVE);
     for (kfpos_replay_cut c(kinds, n_events, first, h->trace_chunk, n_kinds); c.next();) {
         ev.k.n_steps = c.n;
         ev.k.traj = trajectory ? trajectory + (size_t)c.e0 * 3 * T : nullptr;
         ev.status_events = status_events ? status_events + (size_t)c.e0 * T : nullptr;
         ev.k.status = c.last() ? status : nullptr;
         own(c);
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), lds, s, ev);
+        hipLaunchKernelGGL(kern, dim3(p.groups(h->cfg.n_tags)), dim3(WAVE), p.bytes(), s, ev);
         HIPCHK(hipGetLastError());
         h->stepped = true;
     }
@@ -265,8 +251,8 @@ int kfpos_run_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds
     /* From the first sample on: k_events_imu9. Every launch leaves its last sample and `cov` latched, so the next one
      * (and whoever calls next) finds them where single calls leave them. */
     kfpos_k::events_kernel_t kern;
-    size_t lds;
-    rc = imu9_replay_kernel(h, kfpos_k::imu9_events_kernel, &kern, &lds);
+    const Plan p = replay_plan(h, kfpos_plan::EVENTS9);
+    rc = replay_kernel(kfpos_k::imu9_events_kernel(h->cfg.storage, p.as), p, &kern);
     if (rc != KFPOS_OK) return rc;
     kfpos_k::EvArgs ev;
     fill_args(h, ev.k);
@@ -274,7 +260,7 @@ int kfpos_run_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds
     ev.k.stride_err = stride_err;
     ev.k.stride_accel = stride_accel;
     ev.k.cov = cov;
-    return replay_launches(h, kern, lds, ev, kinds, 2, lead, n_events, trajectory, status_events, status, s,
+    return replay_launches(h, kern, p, ev, kinds, 2, lead, n_events, trajectory, status_events, status, s,
                            [&](const kfpos_replay_cut &c) {
         imu9_inputs(h, ev, kinds, range_mm, err_est, accel, c);
         shared_dt(ev.k, dt_events, c);
@@ -298,8 +284,8 @@ int kfpos_run_events_each_dev(kfpos_handle *h, int32_t n_events, const uint8_t *
      * covariance's until the lane's own first sample, the call's from then on -- and every launch leaves the samples it
      * took latched with `cov`, so the next launch (and whoever calls next) finds them where single calls leave them. */
     kfpos_k::events_each_kernel_t kern;
-    size_t lds;
-    rc = imu9_replay_kernel(h, kfpos_k::imu9_events_each_kernel, &kern, &lds);
+    const Plan p = replay_plan(h, kfpos_plan::EVENTS9);
+    rc = replay_kernel(kfpos_k::imu9_events_each_kernel(h->cfg.storage, p.as), p, &kern);
     if (rc != KFPOS_OK) return rc;
     kfpos_k::EvEachArgs ev;
     fill_args(h, ev.k);
@@ -308,7 +294,7 @@ int kfpos_run_events_each_dev(kfpos_handle *h, int32_t n_events, const uint8_t *
     ev.k.stride_accel = stride_accel;
     no_shared_dt(ev.k);
     const size_t T = h->cfg.n_tags;
-    return replay_launches(h, kern, lds, ev, kinds, 2, 0, n_events, trajectory, status_events, status, (hipStream_t)stream,
+    return replay_launches(h, kern, p, ev, kinds, 2, 0, n_events, trajectory, status_events, status, (hipStream_t)stream,
                            [&](const kfpos_replay_cut &c) {
         imu9_inputs(h, ev, kinds, range_mm, err_est, accel, c);
         /* the kernel whitens `cov` only where a lane can come to use it: in a launch with an IMU slot */
@@ -336,17 +322,11 @@ int kfpos_run_trace_each_dev(kfpos_handle *h, int32_t n_steps, const double *dt_
         return ranging_lead_each(h, n_steps, n_steps, dt_steps_dev, range_mm, stride_ranges, err_est, stride_err, trajectory,
                                  status_steps, status, s);
     /* k_trace_toa6_each; a bank with more wavefronts than SIMDs runs it too (the two-wavefront build of the single
-     * calls computes the same bits). The kernel and its LDS follow the handle as step_kernel() / launch_step() do: the
-     * epoch of the LDS forms (4-byte errorEstimations kept as they are where the anchor count is a compile-time one),
-     * and Pinv6 of the non-symmetric layout behind it. */
-    const int as = h->force_generic ? 0 : static_anchors(h);
-    const int heur = h->cfg.ignore_worst != 0 ? 2 : (h->cfg.top_n != 0 ? 1 : 0);
-    size_t lds = (as == 8 && !h->full) ? 0 : lds_bytes(h);
-    if (lds && as != 0 && h->msz == 4) lds = lds * 5 / 6;
-    if (h->full) lds += park_bytes();
+     * calls computes the same bits): the plan of the 6-state step without that build. */
+    const Plan p = replay_plan(h, kfpos_plan::TRACE6_EACH);
     kfpos_k::trace_each_kernel_t kern;
-    const int rc = replay_kernel(h->full ? kfpos_k::toa6_each_full_kernel(h->cfg.storage, as, heur)
-                                         : kfpos_k::toa6_each_sym_kernel(h->cfg.storage, as, heur), lds, &kern);
+    const int rc = replay_kernel(h->full ? kfpos_k::toa6_each_full_kernel(h->cfg.storage, p.as, p.heur)
+                                         : kfpos_k::toa6_each_sym_kernel(h->cfg.storage, p.as, p.heur), p, &kern);
     if (rc != KFPOS_OK) return rc;
     kfpos_k::TraceEachArgs ev;
     fill_args(h, ev.k);
@@ -354,7 +334,7 @@ int kfpos_run_trace_each_dev(kfpos_handle *h, int32_t n_steps, const double *dt_
     ev.k.stride_ranges = stride_ranges;
     ev.k.stride_err = stride_err;
     no_shared_dt(ev.k);
-    return replay_launches(h, kern, lds, ev, nullptr, 0, 0, n_steps, trajectory, status_steps, status, s,
+    return replay_launches(h, kern, p, ev, nullptr, 0, 0, n_steps, trajectory, status_steps, status, s,
                            [&](const kfpos_replay_cut &c) {
         ev.k.ranges = range_mm + (size_t)c.e0 * stride_ranges;
         ev.k.err = (const char *)err_est + (size_t)c.e0 * stride_err * r;
@@ -382,13 +362,13 @@ int kfpos_run_planar_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t
     /* From the first sensor event on: k_events_planar. Every launch leaves the samples it latched in HBM, so the next
      * one (and whoever calls next) finds them where single calls leave them. */
     kfpos_k::planar_events_kernel_t kern;
-    size_t lds;
-    rc = planar_replay_kernel(h, kfpos_k::planar_events_kernel, &kern, &lds);
+    const Plan p = replay_plan(h, kfpos_plan::EVENTS_PLANAR);
+    rc = replay_kernel(kfpos_k::planar_events_kernel(h->cfg.storage, p.as), p, &kern);
     if (rc != KFPOS_OK) return rc;
     kfpos_k::PevArgs ev;
     fill_args(h, ev.k);
     planar_strides(ev, in);
-    return replay_launches(h, kern, lds, ev, kinds, 5, lead, n_events, trajectory, status_events, status, s,
+    return replay_launches(h, kern, p, ev, kinds, 5, lead, n_events, trajectory, status_events, status, s,
                            [&](const kfpos_replay_cut &c) {
         planar_inputs(h, ev, in, kinds, c);
         shared_dt(ev.k, dt_events, c);
@@ -419,15 +399,15 @@ int kfpos_run_planar_events_each_dev(kfpos_handle *h, int32_t n_events, const ui
     /* From there on: k_events_planar_each. Every launch leaves the samples its lanes latched in HBM, so the next one
      * (and whoever calls next) finds them where single calls leave them. */
     kfpos_k::planar_events_each_kernel_t kern;
-    size_t lds;
-    rc = planar_replay_kernel(h, kfpos_k::planar_events_each_kernel, &kern, &lds);
+    const Plan p = replay_plan(h, kfpos_plan::EVENTS_PLANAR);
+    rc = replay_kernel(kfpos_k::planar_events_each_kernel(h->cfg.storage, p.as), p, &kern);
     if (rc != KFPOS_OK) return rc;
     kfpos_k::PevEachArgs ev;
     fill_args(h, ev.k);
     planar_strides(ev, in);
     no_shared_dt(ev.k);
     const size_t T = h->cfg.n_tags;
-    return replay_launches(h, kern, lds, ev, kinds, 5, lead, n_events, trajectory, status_events, status, s,
+    return replay_launches(h, kern, p, ev, kinds, 5, lead, n_events, trajectory, status_events, status, s,
                            [&](const kfpos_replay_cut &c) {
         planar_inputs(h, ev, in, kinds, c);
         ev.dt_each = dt_events_dev + (size_t)c.e0 * T;

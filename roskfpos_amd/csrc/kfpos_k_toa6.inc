@@ -94,7 +94,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 2))) vo
  * wide as above) and most of the covariance joins it while the ML solve runs (step_toa6<..., PARKN>): 19.5 KB per
  * wavefront, eight wavefronts per CU. Same arithmetic, same bits (tests/test_two_waves_gpu.py). */
 template <typename MREAL>
-constexpr int toa6_w2_park() { return sizeof(MREAL) == 4 ? 19 : 15; } /* what 160 KB / 8 leave next to the epoch */
+constexpr int toa6_w2_park() { return kfpos_plan::toa6_w2_park(sizeof(MREAL)); } /* what 160 KB / 8 leave next to the epoch */
 template <typename REAL, typename MREAL>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_step_toa6_w2(const KArgs a) {
     extern __shared__ double lds[];

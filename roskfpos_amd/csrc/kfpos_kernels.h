@@ -2,7 +2,8 @@
  * kfpos_kernels.h -- what the kernel translation units of libkfpos_hip.so share: the kernel-argument blocks, the
  * device-side helpers that stage an epoch (component-major HBM -> registers / LDS), and the selector functions through
  * which the host side (kfpos_hip.hip, kfpos_hip_state.hip, kfpos_hip_slots.hip, kfpos_hip_replay.hip) obtains a kernel without seeing its template, and what those
- * host units share among themselves (at the end of namespace kfpos_k's declarations).
+ * host units share among themselves (at the end of namespace kfpos_k's declarations). WHICH kernel a launch takes, over
+ * how many workgroups and with how many bytes of LDS: kfpos_launch_plan.h.
  *
  * Execution model: ONE FILTER PER LANE, 64 filters per wavefront, one wavefront per workgroup.
  *  - The whole per-tag state (position, velocity, packed covariance: 21 / 36 / 45 doubles) lives in
@@ -26,7 +27,7 @@
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
  * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
- * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_k_d16 (the decoder of KFPOS_SLOT_RANGES_D16 rounds), kfpos_hip (host side + C ABI), kfpos_hip_state (the state side of the C ABI: whole-bank accessors, per-tag lifecycle, pose for a row list), kfpos_hip_slots (the streaming slots of the C ABI, kfpos_slot_*), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
+ * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_k_d16 (the decoder of KFPOS_SLOT_RANGES_D16 rounds), kfpos_hip (host side + C ABI; it and kfpos_hip_replay turn a Plan of kfpos_launch_plan.h into a kernel and launch it, and hold no LDS size or kernel form of their own), kfpos_hip_state (the state side of the C ABI: whole-bank accessors, per-tag lifecycle, pose for a row list), kfpos_hip_slots (the streaming slots of the C ABI, kfpos_slot_*), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
 #define KFPOS_KERNELS_H
@@ -41,6 +42,7 @@
 #define KFPOS_HD __host__ __device__
 #include "kfpos_core.h"
 #include "kfpos_internal.h"
+#include "kfpos_launch_plan.h"
 #include "kfpos_p48.h"
 #include "kfpos_replay_plan.h"
 #include "kfpos_state_record.h"
@@ -241,10 +243,8 @@ struct D16Args {
 };
 void launch_decode_d16(hipStream_t s, const D16Args &a);                    /* kfpos_k_d16.hip */
 
-constexpr int COOP_LANES = 8;                   /* kfpos_k_coop.hip: one tag per group of 8 lanes */
-constexpr int COOP_TAGS_PER_WAVE = 64 / COOP_LANES;
 constexpr int PLANAR_HAS_SHIFT = 4;              /* planar flags word: bits 5..7 = latched PX4Flow / IMU / magnetometer */
-/* LATCH_ROWS: kfpos_host_layout.h */
+/* LATCH_ROWS: kfpos_host_layout.h; COOP_LANES, COOP_TAGS_PER_WAVE: kfpos_launch_plan.h */
 
 } // namespace kfpos_k
 
@@ -284,12 +284,13 @@ inline kfpos_layout::Sizes handle_sizes(const kfpos_handle *h) {
 inline kfpos_layout::Rows rows_layout(const kfpos_handle *h, size_t n) { /* the work block as it is, n tags listed */
     return kfpos_layout::rows_layout(handle_sizes(h), KFPOS_N_SLOTS, h->work_cap, n);
 }
+/* what launch selection depends on (kfpos_launch_plan.h): the handle's configuration and kfpos_create's policy flags */
+inline kfpos_plan::Inputs plan_inputs(const kfpos_handle *h) {
+    return {h->cfg.model, h->cfg.storage, h->cfg.max_anchors, h->full != 0, h->cfg.ignore_worst != 0, h->cfg.top_n != 0,
+            h->force_generic, h->coop, h->two_waves, h->planar_sensors};
+}
 KFPOS_HIDDEN void fill_args(const kfpos_handle *h, kfpos_k::KArgs &a);           /* the handle's part of every argument block */
 KFPOS_HIDDEN int launch_step(kfpos_handle *h, const kfpos_k::KArgs &a, hipStream_t s); /* the step kernel of the handle, a.T tags */
-KFPOS_HIDDEN int static_anchors(const kfpos_handle *h);                          /* anchor-count specialisation: 8, -16 or 0 */
-KFPOS_HIDDEN size_t lds_bytes(const kfpos_handle *h);                            /* an LDS-resident epoch of max_anchors */
-KFPOS_HIDDEN size_t park_bytes();
-KFPOS_HIDDEN size_t park9_bytes();
 
 #define g_err (kfpos_error_text())
 #define HIPCHK(expr)                                                                              \
@@ -427,7 +428,7 @@ using kfpos_k::COOP_TAGS_PER_WAVE;
 using kfpos_k::PLANAR_HAS_SHIFT;
 using kfpos_k::LATCH_ROWS;
 
-constexpr int WAVE = 64; /* lanes per workgroup = one wavefront */
+constexpr int WAVE = kfpos_plan::LANES; /* lanes per workgroup = one wavefront */
 
 enum StepMode : int { MODE_TOA = 0, MODE_IMU_ONLY = 1, MODE_FUSED = 2 };
 
@@ -644,7 +645,7 @@ __device__ inline StaticScratchF<N> stage_epoch_lds_nf(const KArgs &a, double *l
 }
 /* doubles of LDS the epoch of a compile-time-count kernel takes per workgroup */
 template <typename MREAL, int N>
-constexpr size_t static_epoch_doubles() { return sizeof(MREAL) == 4 ? (size_t)N * WAVE * 5 / 2 : (size_t)N * WAVE * 3; }
+constexpr size_t static_epoch_doubles() { return kfpos_plan::static_epoch_doubles(sizeof(MREAL), N); }
 __device__ inline double epoch_dt(const KArgs &a, size_t t, int s) {
     return a.n_steps > 1 ? a.dt_steps[s] : (a.dt ? a.dt[(uint32_t)t] : a.dt_shared);
 }

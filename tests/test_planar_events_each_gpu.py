@@ -174,7 +174,7 @@ def _bit_identity(A, storage, combos, tags=None):
             if not pe.STARTS[start][0]:
                 assert (low & 0x08).any(), what                              # ML initialisations happened
             started = np.isfinite(ref[0][-1]).all(axis=0)
-            assert started[np.arange(T) != pee.NOWHERE].all(), what
+            assert started[(np.arange(T) if tags is None else np.asarray(tags)) != pee.NOWHERE].all(), what
 
 
 @pytest.mark.parametrize("A", [8, 5])               # compile-time anchor loops; run-time anchor loop
@@ -190,6 +190,19 @@ def test_one_call_equals_the_single_calls_for_a_single_tag(storage, A):
     if not has_gpu():
         pytest.skip("no GPU")
     _bit_identity(A, storage, [("fixed", True, False), ("ml2d", False, True)], tags=[1])   # tag 1 skips slots
+
+
+OVER_64K = [("fixed", True, False), ("ml3d", False, False)]   # (start, end_on_sensor, waiting)
+
+
+@pytest.mark.parametrize("storage", [0, 2])         # f64; mixed: 4-byte measurements
+def test_one_call_equals_the_single_calls_behind_a_raised_lds_limit(storage):
+    """31 anchors: the run-time loop's epoch and CovSpill8 take 66 048 bytes of LDS, the smallest count over 64 KB (30:
+    64 512), so k_events_planar_each runs behind a raised hipFuncAttributeMaxDynamicSharedMemorySize. Tags 0..64: a full
+    wavefront, whose lane 63 reaches the end of the block, and a ragged one"""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    _bit_identity(31, storage, OVER_64K, tags=np.arange(65))
 
 
 def test_a_schedule_that_crosses_the_launch_boundary():
@@ -352,7 +365,7 @@ def test_an_all_present_schedule_equals_run_planar_events_dev(storage, A):
 
 @pytest.mark.parametrize("A", [8, 5])
 @pytest.mark.parametrize("start", ["fixed", "fixed_free", "ml3d", "ml2d"])
-def test_f64_storage_matches_the_oracle_after_every_slot(start, A):
+def test_f64_storage_matches_the_oracle_after_every_slot(start, A, T=T):
     """position RMS <= 1e-9 m and max <= 1e-8 m after every slot over the tags that ran it (the bounds of
     tests/test_planar_events_gpu.py for the same comparison), every status word equal to the oracle's, a tag that sat
     the slot out reports the bytes of its previous row. Measured on an MI355X, worst over the slots, A = 8 / A = 5:
@@ -361,13 +374,14 @@ def test_f64_storage_matches_the_oracle_after_every_slot(start, A):
     if not has_gpu():
         pytest.skip("no GPU")
     from planar import PlanarOracle
-    inp = Inputs(A, 0, start, True, waiting=not pe.STARTS[start][0])
+    inp = Inputs(A, 0, start, True, waiting=not pe.STARTS[start][0], tags=np.arange(T))   # (the oracle: all 130)
     assert (inp.dt[inp.mask] > 0).all()           # dt = 0 stays out of this leg
     b = inp.bank()
     got = _one_call(b, inp)
     b.close()
     sch = inp.es.sch
     po, so = pee.replay(PlanarOracle(sch.w, pe.cfg_of(start), pe.init_of(sch, start)), inp.es)
+    po, so = po[:, :T], so[:, :T]
     worst = [0.0, 0.0]
     for e in range(inp.kinds.size):
         ran = inp.ran[e]
@@ -386,6 +400,16 @@ def test_f64_storage_matches_the_oracle_after_every_slot(start, A):
           f"{inp.kinds.size} slots")
     started = np.isfinite(got[0][-1]).all(axis=0)
     assert started[np.arange(T) != pee.NOWHERE].all() and np.isfinite(po[-1][np.arange(T) != pee.NOWHERE]).all()
+
+
+@pytest.mark.parametrize("start", ["fixed", "fixed_free"])
+def test_f64_storage_matches_the_oracle_behind_a_raised_lds_limit(start):
+    """the same bounds at 31 anchors and tags 0..64 (more than 64 KB of LDS), from a fixed start: an ML start stays with the
+    bit-identity test above. Beyond a dozen anchors the Gauss-Newton walk of a few tags' ML initialisation is chaotic
+    (cases.py, "No 16-anchor ML-init case"): on the CPU alone the host emulation of the kernel arithmetic and the oracle
+    then part by 1e-7 ... 3e-2 m on 2 to 4 of 130 tags and count different gain iterations. Measured with the library
+    before launch selection moved into kfpos_launch_plan.h, the 9-state replays at 17 anchors miss the bound from an ML start (tests/test_run_events_gpu.py)."""
+    test_f64_storage_matches_the_oracle_after_every_slot(start, 31, T=65)
 
 
 def _raw_call(b, n, kinds, d_dt, inputs):

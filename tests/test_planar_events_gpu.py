@@ -189,6 +189,19 @@ def test_one_call_equals_the_single_calls_for_a_single_tag(storage, A):
     _bit_identity(1, A, storage, [("fixed", True, False), ("ml2d", False, True)])
 
 
+OVER_64K = [("fixed", False, False), ("ml3d", True, True)]   # (start, end_on_sensor, waiting)
+
+
+@pytest.mark.parametrize("storage", [0, 2])         # f64; mixed: 4-byte measurements
+def test_one_call_equals_the_single_calls_behind_a_raised_lds_limit(storage):
+    """31 anchors: the run-time loop's epoch and CovSpill8 take 66 048 bytes of LDS, the smallest count over 64 KB (30:
+    64 512), so k_events_planar runs behind a raised hipFuncAttributeMaxDynamicSharedMemorySize. 65 tags: a full
+    wavefront, whose lane 63 reaches the end of the block, and a ragged one"""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    _bit_identity(65, 31, storage, OVER_64K)
+
+
 def test_a_schedule_that_crosses_the_launch_boundary():
     """the schedule four times over, 160 events: behind the leading ranging event a launch of 128 events -- all 16 words
     of its `kinds` in use, events of every kind at 64 or later in it -- and a second one for the rest"""
@@ -289,13 +302,12 @@ def test_an_event_with_dt_zero(storage, A):
 
 @pytest.mark.parametrize("A", [8, 5])
 @pytest.mark.parametrize("start", ["fixed", "ml3d", "ml2d"])
-def test_f64_storage_matches_the_oracle_after_every_event(start, A):
+def test_f64_storage_matches_the_oracle_after_every_event(start, A, T=130):
     """position RMS <= 1e-9 m and max <= 1e-8 m after every event (the bounds tests/test_run_events_gpu.py takes from
     tests/test_gpu_parity.py), every status word equal to the oracle's, no tag left out, every tag started by the end"""
     if not has_gpu():
         pytest.skip("no GPU")
     from planar import PlanarOracle
-    T = 130
     inp = Inputs(T, A, 0, start, True, waiting=start != "fixed")
     b = inp.bank()
     got = _one_call(b, inp, inp.kinds, inp.dts)
@@ -314,6 +326,16 @@ def test_f64_storage_matches_the_oracle_after_every_event(start, A):
     print(f"A={A} start={start}: worst RMS {worst[0]:.3e} m, worst max {worst[1]:.3e} m against the oracle over "
           f"{inp.kinds.size} events")
     assert np.isfinite(got[0][-1]).all() and np.isfinite(po[-1]).all()     # every tag has started by the end
+
+
+@pytest.mark.parametrize("start", ["fixed", "fixed_free"])
+def test_f64_storage_matches_the_oracle_behind_a_raised_lds_limit(start):
+    """the same bounds at 31 anchors and 65 tags (more than 64 KB of LDS), from a fixed start: an ML start stays with the
+    bit-identity test above. Beyond a dozen anchors the Gauss-Newton walk of a few tags' ML initialisation is chaotic
+    (cases.py, "No 16-anchor ML-init case"): on the CPU alone the host emulation of the kernel arithmetic and the oracle
+    then part by 1e-7 ... 3e-2 m on 2 to 4 of 130 tags and count different gain iterations. Measured with the library
+    before launch selection moved into kfpos_launch_plan.h, the 9-state replays at 17 anchors miss the bound from an ML start (tests/test_run_events_gpu.py)."""
+    test_f64_storage_matches_the_oracle_after_every_event(start, 31, T=65)
 
 
 def _raw_call(b, n, kinds, dts, inputs):

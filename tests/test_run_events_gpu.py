@@ -193,6 +193,19 @@ def test_one_call_equals_the_single_calls_for_a_single_tag(storage, A):
     _bit_identity(1, A, storage, [(True, False, True), (False, True, False)])
 
 
+OVER_64K = [(True, False, True), (False, True, False)]   # (fixed, cov_full, end_on_imu)
+
+
+@pytest.mark.parametrize("storage", [0, 2])         # f64; mixed: 4-byte measurements
+def test_one_call_equals_the_single_calls_behind_a_raised_lds_limit(storage):
+    """17 anchors: the run-time loop's epoch and CovPark9 take 66 240 bytes of LDS, the smallest count over 64 KB (16:
+    64 704), so k_events_imu9 runs behind a raised hipFuncAttributeMaxDynamicSharedMemorySize. 65 tags: a full wavefront,
+    whose lane 63 reaches the end of the block, and a ragged one"""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    _bit_identity(65, 17, storage, OVER_64K)
+
+
 def test_a_schedule_that_crosses_the_launch_boundary():
     """the schedule four times over, 156 events: behind the leading ranging event a launch of 128 events -- both words
     of its `kinds` in use, events of either kind at 64 or later in it -- and a second one for the rest"""
@@ -260,13 +273,12 @@ def test_leading_ranging_events_fuse_the_previously_latched_sample_with_its_cova
 @pytest.mark.parametrize("A", [8, 5])
 @pytest.mark.parametrize("fixed", [True, False])
 @pytest.mark.parametrize("cov_full", [False, True])
-def test_f64_storage_matches_the_oracle_after_every_event(cov_full, fixed, A):
+def test_f64_storage_matches_the_oracle_after_every_event(cov_full, fixed, A, T=130):
     """position RMS <= 1e-9 m and max <= 1e-8 m after every event (the bounds of test_gpu_parity.py for the 9-state
     cases), every status word equal to the oracle's, no tag left out"""
     if not has_gpu():
         pytest.skip("no GPU")
     import oracle_py
-    T = 130
     inp = Inputs(T, A, 0, fixed, cov_full, True)
     b = inp.bank()
     got = _one_call(b, inp, inp.kinds, inp.dts)
@@ -292,6 +304,16 @@ def test_f64_storage_matches_the_oracle_after_every_event(cov_full, fixed, A):
     print(f"A={A} fixed={fixed} cov_full={cov_full}: worst RMS {worst[0]:.3e} m, worst max {worst[1]:.3e} m "
           f"against the oracle over {inp.kinds.size} events")
     assert np.isfinite(got[0][-1]).all()   # every tag has started by the end, none was left out of the comparison
+
+
+@pytest.mark.parametrize("cov_full", [False, True])
+def test_f64_storage_matches_the_oracle_behind_a_raised_lds_limit(cov_full):
+    """the same bounds at 17 anchors and 65 tags (more than 64 KB of LDS), from a fixed start: an ML start stays with the
+    bit-identity test above. Beyond a dozen anchors the Gauss-Newton walk of a few tags' ML initialisation is chaotic
+    (cases.py, "No 16-anchor ML-init case"): on the CPU alone the host emulation of the kernel arithmetic and the oracle
+    then part by 1e-7 ... 3e-2 m on 2 to 4 of 130 tags and count different gain iterations. Measured with the library
+    before launch selection moved into kfpos_launch_plan.h, ML start, full covariance: RMS 1.6e-7 m (max 1.3e-6 m) after the first event."""
+    test_f64_storage_matches_the_oracle_after_every_event(cov_full, True, 17, T=65)
 
 
 def _raw_call(b, n, kinds, dts, r, e, a, c, A, T):

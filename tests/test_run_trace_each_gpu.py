@@ -86,23 +86,24 @@ def test_the_schedule_holds_what_it_is_meant_to_hold():
 class Inputs:
     """the schedule's inputs in HBM (component-major), and on the host in the (T, A) form the oracle takes"""
 
-    def __init__(self, A, storage, fixed=True, ignore_worst=False, top_n=0, slots=SLOTS, env=None, dev="cuda:0"):
+    def __init__(self, A, storage, fixed=True, ignore_worst=False, top_n=0, slots=SLOTS, env=None, tags=T, dev="cuda:0"):
+        """tags: the bank holds the first `tags` columns of the 130-tag schedule"""
         import torch
-        n = self.T = T
+        n = self.T = tags
         self.A, self.storage, self.fixed = A, storage, fixed
         self.ignore_worst, self.top_n, self.env = ignore_worst, top_n, dict(env or {})
         real = self.real = np.float64 if storage == F64 else np.float32
         case = Case("each", 0, A, fixed=fixed, T=T, outlier=bool(ignore_worst or top_n))
         w = Workload(T, A)
-        self.anchors, self.init = w.anchors, w.init_positions()
+        self.anchors, self.init = w.anchors, w.init_positions()[:n]
         self.slots = slots
-        self.mask = _mask(slots)
+        self.mask = _mask(slots)[:, :n]
         base = np.round(np.random.default_rng(20261017).uniform(0.02, 0.12, slots), 4)
         base[DT_ZERO] = 0.0
         self.dt = np.where(self.mask, base[:, None], -1.0)                        # (S, T)
-        self.ranges = np.stack([case.epoch(w, s) for s in range(slots)])           # (S, T, A), dropout rows kept
+        self.ranges = np.stack([case.epoch(w, s) for s in range(slots)])[:, :n]    # (S, T, A), dropout rows kept
         self.ranges[~self.mask] = ABSENT_MM
-        self.err = w.err_est(real)
+        self.err = w.err_est(real)[:n]
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
         self.d_r, self.d_e, self.d_dt = up(self.ranges.transpose(0, 2, 1)), up(self.err.T), up(self.dt)
         assert n == self.d_dt.shape[1]
@@ -176,6 +177,13 @@ CONFIGS = {
     "A8 fixed mixed generic": dict(A=8, storage=MIXED, env={"KFPOS_GENERIC_KERNEL": 1}),
     # no environment: the handle runs the 8-lanes-per-tag kernel, the call one launch per slot
     "A8 fixed mixed coop": dict(A=8, storage=MIXED),
+    # more than 64 KB of LDS, so k_trace_toa6_each runs behind a raised hipFuncAttributeMaxDynamicSharedMemorySize: the
+    # run-time loop's epoch alone from 43 anchors (66 048 bytes; 42: 64 512), with Pinv6 of the ML start behind it from 31
+    # (66 048; 30: 64 512). 65 tags: a full wavefront, whose lane 63 reaches the end of the block, and a ragged one
+    "A43 fixed f64 T65": dict(A=43, storage=F64, tags=65),
+    "A43 fixed mixed T65": dict(A=43, storage=MIXED, tags=65),
+    "A31 ml f64 T65": dict(A=31, storage=F64, fixed=False, tags=65),
+    "A31 ml mixed T65": dict(A=31, storage=MIXED, fixed=False, tags=65),
 }
 
 
@@ -292,6 +300,8 @@ ORACLE = {
     "A5 ml": dict(A=5, storage=F64, fixed=False),
     "A8 fixed ignore_worst": dict(A=8, storage=F64, ignore_worst=True),
     "A16 fixed top3": dict(A=16, storage=F64, top_n=3),
+    "A43 fixed T65": dict(A=43, storage=F64, tags=65),
+    "A31 ml T65": dict(A=31, storage=F64, fixed=False, tags=65),
 }
 
 
@@ -305,6 +315,7 @@ def test_f64_storage_matches_the_oracle_after_every_slot_a_tag_ran(name):
         pytest.skip("no GPU")
     import oracle_py
     inp = Inputs(**ORACLE[name])
+    T = inp.T
     b = inp.bank()
     got = _one_call(b, inp.d_r, inp.d_e, inp.d_dt)
     b.close()
