@@ -207,11 +207,10 @@ KFPOS_FN bool rel_change_below(double cost, double c, double tol) {
  * comparison itself (no bool rebuilt from an integer per lane), the product form is evaluated unconditionally and the
  * cold side overwrites it with the exact quotient -- one way in, one way out, nothing to re-test on the hot side.
  * Only that loop uses it. The other callers of rel_change_below / _above (6-state and planar iterations, the (I + M B)
- * form, every Gauss-Newton loop) keep their text on purpose: they are inlined into kernels that sit at their register
- * or occupancy limits, where any change of this text -- even sharing the three first lines through a helper -- moves
- * the schedule of every one of them; in ml_estimate the new shape made k_events_imu9<p48,float,8> spill inside its
- * loop (profiles/HISTORY.md), and none of those kernels has been measured with it. Whoever changes one of the three
- * changes all three. */
+ * form, the 2-D Gauss-Newton loop, the Gauss-Newton loop of a kernel that keeps the unpeeled text) keep their text on
+ * purpose: they are inlined into kernels that sit at their register or occupancy limits, where any change of this text
+ * -- even sharing the three first lines through a helper -- moves the schedule of every one of them. Whoever changes
+ * one of the four changes all four. */
 KFPOS_FN bool rel_change_below_voted(double cost, double c, double tol) {
     const double lhs = fabs(cost - c), rhs = tol * cost;
     const bool clear = cost > 0.0 && fabs(lhs - rhs) > 1e-13 * rhs; /* false for NaN and for cost <= 0 or inf */
@@ -227,6 +226,16 @@ KFPOS_FN bool rel_change_above(double cost, double c, double tol) {
     const bool clear = cost > 0.0 && fabs(lhs - rhs) > 1e-13 * rhs; /* false for NaN and for cost <= 0 or inf */
     if (KFPOS_WAVE_ALL(clear)) return lhs > rhs;
     return lhs / cost > tol;
+}
+/* ... and in the voted shape of rel_change_below_voted, for the peeled Gauss-Newton loop of ml_estimate: every epoch of
+ * every filter runs that loop, and the wavefront pays its slowest lane's passes. Same decision for every input as
+ * rel_change_above: there, too, one lane that is not clear sends the whole wavefront to the quotient. */
+KFPOS_FN bool rel_change_above_voted(double cost, double c, double tol) {
+    const double lhs = fabs(cost - c), rhs = tol * cost;
+    const bool clear = cost > 0.0 && fabs(lhs - rhs) > 1e-13 * rhs; /* false for NaN and for cost <= 0 or inf */
+    bool above = lhs > rhs;
+    if (KFPOS_WAVE_ANY(!clear)) above = lhs / cost > tol;
+    return above;
 }
 
 /* std::max as the reference uses it: (a < b) ? b : a (matters for NaN) */

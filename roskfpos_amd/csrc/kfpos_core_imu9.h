@@ -149,7 +149,7 @@ struct Iekf9Out {
 
 /* kalmanStep3D (KalmanFilterTOAIMU.cpp:242-340, with the 3-token repair), first part (:268-276): ML
  * position -> observation covariance of the ranging rows. Independent of P. */
-template <bool SELECTS = true, class SC>
+template <bool SELECTS = true, bool PEEL = true, class SC>
 KFPOS_FN void iekf9_weights(const double xhat[9], SC &sc, const Params &pr, bool has_ranging, int n_used,
                             Iekf9Out &o) {
     o.flags = (has_ranging && n_used < 4) ? ST_FEW_RANGES : 0u;
@@ -157,7 +157,7 @@ KFPOS_FN void iekf9_weights(const double xhat[9], SC &sc, const Params &pr, bool
     if (has_ranging) {
         double pml[3] = {xhat[0], xhat[1], xhat[2]}, e_ml;
         set_weights_ml<SELECTS>(sc, pr, 0ull);
-        o.ml_iters = ml_estimate(pml, sc, pr, 0ull, n_used, e_ml); /* no NaN fallback in this filter */
+        o.ml_iters = ml_estimate<PEEL>(pml, sc, pr, 0ull, n_used, e_ml); /* no NaN fallback in this filter */
         if (ml_covariance_throws<SELECTS>(sc, pr, 0ull, n_used, e_ml)) o.flags |= ST_UPDATE_SKIPPED;
         set_weights_iekf<SELECTS>(sc, pr, e_ml, 0ull);
     }
@@ -987,7 +987,7 @@ KFPOS_FN bool imu9_started(const Tag9 &tg, const Params &pr) {
 }
 /* ML initialisation of a tag that has not started (:121-137). true: pos is the ML position and c its covariance, of
  * which the filter keeps {00,01,11}; false: nothing changed. status is the step's status word either way. */
-template <bool RANGING, class SC>
+template <bool RANGING, bool PEEL = true, class SC>
 KFPOS_FN bool imu9_ml_init(double pos[3], SC &sc, const Params &pr, int n_valid, double c[6], uint32_t &status) {
     status = 0;
     if (!RANGING) return false;
@@ -995,7 +995,7 @@ KFPOS_FN bool imu9_ml_init(double pos[3], SC &sc, const Params &pr, int n_valid,
     if (n_valid < 4) return false;
     double p[3] = {1.0, 1.0, 4.0}, sse;
     set_weights_ml(sc, pr, 0ull);
-    const int it = ml_estimate(p, sc, pr, 0, n_valid, sse);
+    const int it = ml_estimate<PEEL>(p, sc, pr, 0, n_valid, sse);
     status = ST_UPDATE_SKIPPED;
     if (ml_covariance_throws(sc, pr, 0, n_valid, sse)) return false; /* reference: abort */
     if (!ml_covariance(p, sc, pr, sse, c)) return false;
@@ -1074,8 +1074,10 @@ KFPOS_FN void imu9_iterate(Tag9 &tg, const double xhat[9], SC &sc, const Params 
  * ~10 400 for wavefronts that are rare -- latched lanes exist only in MODE_TOA calls -- and lose 0.9 us an epoch.)
  * SELECTS: the weights of the epoch (set_weights_ml, ml_covariance_throws, set_weights_iekf) in their select forms.
  * false keeps the conditional text, same results: k_events_imu9 sets it, which spills inside its event loop with the
- * select forms (make check's scratch rule decides, as for HOLD). */
-template <bool RANGING, bool HOLD = true, bool TAIL = false, bool SELECTS = true, class SC>
+ * select forms (make check's scratch rule decides, as for HOLD).
+ * PEEL: the Gauss-Newton solves of the step (the seed of the gain iteration, the ML start) run ml_estimate's peeled
+ * text. false keeps the unpeeled one, same results, for a kernel that spills with the other: the same rule decides. */
+template <bool RANGING, bool HOLD = true, bool TAIL = false, bool SELECTS = true, bool PEEL = true, class SC>
 KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, const Imu &imu, const CovPark9 &park,
                               bool fast, Iekf9Out &o, uint32_t &status) {
     constexpr bool has_ranging = RANGING;
@@ -1087,7 +1089,7 @@ KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, con
         if (n_valid < 4) return false;
         double p[3] = {1.0, 1.0, 4.0}, sse, c[6];
         set_weights_ml<SELECTS>(sc, pr, 0ull);
-        const int it = ml_estimate(p, sc, pr, 0, n_valid, sse);
+        const int it = ml_estimate<PEEL>(p, sc, pr, 0, n_valid, sse);
         status = ST_UPDATE_SKIPPED;
         if (ml_covariance_throws<SELECTS>(sc, pr, 0, n_valid, sse)) return false; /* reference: abort */
         if (!ml_covariance(p, sc, pr, sse, c)) return false;
@@ -1121,7 +1123,7 @@ KFPOS_FN bool step_imu9_state(Tag9 &tg, SC &sc, const Params &pr, double dt, con
     /* B safely invertible on every lane: the information-form iteration (the usual case); otherwise -- right after a
      * fixed start, B is singular -- the (I + M B) form */
     const bool invertible = sym6_inverse(B, binv, park.stride, INFO_FORM_MIN_PIVOT);
-    iekf9_weights<SELECTS>(xhat, sc, pr, has_ranging, n_valid, o); /* position + epoch only */
+    iekf9_weights<SELECTS, PEEL>(xhat, sc, pr, has_ranging, n_valid, o); /* position + epoch only */
     /* The 9-state filter has no try/catch: the reference node aborts here. This core keeps the predicted
      * covariance and reports the tag instead. */
     if (o.flags & ST_UPDATE_SKIPPED) {
@@ -1169,14 +1171,14 @@ KFPOS_FN bool step_imu9_head(Tag9 &tg, const Params &pr, double dt, const CovPar
     imu9_park(tg.P, park);
     return false;
 }
-template <bool RANGING, bool HOLD = true, bool TAIL = false, class SC>
+template <bool RANGING, bool HOLD = true, bool TAIL = false, bool PEEL = true, class SC>
 KFPOS_FN bool step_imu9_state_parked(Tag9 &tg, SC &sc, const Params &pr, double dt, const Imu &imu,
                                      const CovPark9 &park, bool fast, bool invertible, Iekf9Out &o, uint32_t &status) {
     constexpr bool has_ranging = RANGING;
     const int n_valid = has_ranging ? count_used(sc, pr, 0) : 0;
     if (!imu9_started(tg, pr)) {
         double c[6];
-        if (imu9_ml_init<RANGING>(tg.pos, sc, pr, n_valid, c, status)) { /* xy block only, :134-137 */
+        if (imu9_ml_init<RANGING, PEEL>(tg.pos, sc, pr, n_valid, c, status)) { /* xy block only, :134-137 */
             park.a[Cov<9, true>::idx(0, 0) * park.stride] = c[0];
             park.a[Cov<9, true>::idx(0, 1) * park.stride] = c[1];
             park.a[Cov<9, true>::idx(1, 1) * park.stride] = c[3];
@@ -1186,7 +1188,7 @@ KFPOS_FN bool step_imu9_state_parked(Tag9 &tg, SC &sc, const Params &pr, double 
     }
     double xhat[9];
     imu9_predict_state(tg, dt, xhat);
-    iekf9_weights(xhat, sc, pr, has_ranging, n_valid, o); /* position + epoch only */
+    iekf9_weights<true, PEEL>(xhat, sc, pr, has_ranging, n_valid, o); /* position + epoch only */
     if (o.flags & ST_UPDATE_SKIPPED) { /* (the park holds the predicted covariance) */
         imu9_unpark(tg.P, park);
         status = ST_UPDATE_SKIPPED;

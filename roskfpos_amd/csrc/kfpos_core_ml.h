@@ -13,7 +13,9 @@ namespace kfpos {
 /* One sweep over the anchors at position p: weighted cost sum (r-d)^2/e, unweighted SSE
  * (estimationError, MLLocation.cpp:263-278), gradient g and Hessian-like Hs of
  * MLLocation.cpp:174-204 (Hs symmetric, packed {00,01,02,11,12,22}). */
-template <class SC>
+/* COST = false: the first sweep of a solve, whose cost and SSE nobody looks at (ml_estimate): g and Hs alone, the same
+ * expressions in the same anchor order; cw and sse are left alone. */
+template <bool COST = true, class SC>
 KFPOS_FN void ml_sweep(const double p[3], const SC &sc, const Params &pr, uint64_t drop,
                               double &cw, double &sse, double g[3], double hs[6]) {
     double cw_ = 0.0, sse_ = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0, c0s = 0.0;
@@ -30,8 +32,12 @@ KFPOS_FN void ml_sweep(const double p[3], const SC &sc, const Params &pr, uint64
         double d, invd;
         kf_sqrt_rsqrt_sweep(dx * dx + dy * dy + dz * dz, d, invd);
         const double rd = r - d, rd2 = rd * rd;
-        cw_ += rd2 * w;
-        sse_ += on ? rd2 : 0.0;
+        if constexpr (COST) {
+            cw_ += rd2 * w;
+            sse_ += on ? rd2 : 0.0;
+        } else {
+            (void)on; (void)rd2;
+        }
         /* with wi = w / d:  gradient weight (r - d) w / d,  Hessian terms w (1 - r/d) on the diagonal (summed once:
          * the same number goes to all three entries) and w r / d^3 on the dyadic part */
         const double wi = w * invd, gi = rd * wi, wq = r * wi;
@@ -50,7 +56,7 @@ KFPOS_FN void ml_sweep(const double p[3], const SC &sc, const Params &pr, uint64
     });
     /* 8 lanes per tag: the SSE is wanted of the LAST sweep only, so it stays a per-lane partial sum here and the caller
      * combines it once, behind the loop (three DPP exchanges less in every pass) */
-    cw = group_sum(sc, cw_); sse = SC::COOP ? sse_ : group_sum(sc, sse_);
+    if constexpr (COST) { cw = group_sum(sc, cw_); sse = SC::COOP ? sse_ : group_sum(sc, sse_); }
     g[0] = group_sum(sc, g0); g[1] = group_sum(sc, g1); g[2] = group_sum(sc, g2);
     /* (the diagonal term joins the partial sums before they are combined: no extra exchange in the 8-lanes-per-tag mode) */
     hs[0] = group_sum(sc, h0 + c0s); hs[1] = group_sum(sc, h1); hs[2] = group_sum(sc, h2);
@@ -101,6 +107,15 @@ KFPOS_FN void ml_terms_of_lane(const double p[3], const Params &pr, int v, doubl
     ml_terms_of<SC>(p, pr, v, r, w, t);
 }
 
+/* the Gauss-Newton step p - Hs^-1 g (the peeled text of ml_estimate, below, takes it at two places) */
+KFPOS_FN void ml_step(double p[3], const double g[3], const double hs[6]) {
+    double c[6];
+    const double idet = kf_rcp(sym3_cofactors(hs, c));
+    p[0] -= (c[0] * g[0] + c[1] * g[1] + c[2] * g[2]) * idet;
+    p[1] -= (c[1] * g[0] + c[3] * g[1] + c[4] * g[2]) * idet;
+    p[2] -= (c[2] * g[0] + c[4] * g[1] + c[5] * g[2]) * idet;
+}
+
 /* Gauss-Newton loop of MLLocation.cpp:164-225. p: seed in, estimate out. Requires sc.w = 1/e.
  * Returns the iteration count; sse_out = estimationError at the result. With n_used < 4 the
  * seed is returned untouched (MLLocation.cpp:158-161). The step p - Hs^-1 g equals the
@@ -108,12 +123,51 @@ KFPOS_FN void ml_terms_of_lane(const double p[3], const Params &pr, int v, doubl
  * and the gradient/Hessian for the next step (the reference evaluates them in two passes). */
 /* The leave-one-out heuristic hands in the gradient / Hessian sums of the first sweep (use_first, first) or asks for
  * them (keep_first, first_out); flags and references rather than pointers, so that the sums stay in registers. */
-template <class SC>
+/* PEEL (the default): the first pass stands in front of the loop. The reference's first test compares the constants
+ * 1e20 and 1 -- |1e20 - 1| / 1e20 > 1e-3 holds, and so does iter < 10000 --, so the first step is taken whatever the
+ * ranges are: the first sweep forms g and Hs alone (ml_sweep<false>: no cost, no SSE, nobody looks at them), no test is
+ * evaluated, and the loop proper starts with the second sweep at iter = 1, cost = 1. Its test is the voted form
+ * (rel_change_above_voted; the 8-lanes-per-tag kernel keeps its quotient) with one commit behind it. The same
+ * operations on the same numbers in the same order: iteration count, SSE and position are those of the unpeeled text
+ * for every input. PEEL = false keeps that text, below, for a kernel that spills inside a loop with the new one (make
+ * check's scratch rule decides, as for SELECTS and HOLD of the 9-state step). */
+template <bool PEEL = true, class SC>
 KFPOS_FN int ml_estimate(double p[3], const SC &sc, const Params &pr, uint64_t drop, int n_used, double &sse_out,
                          bool use_first, const MlFirst &first, bool keep_first, MlFirst &first_out) {
     if (n_used < 4) {
         sse_out = (n_used == 0) ? -1.0 : ml_sse(p, sc, pr, drop);
         return 0;
+    }
+    if constexpr (PEEL) {
+        double cost = 1.0, cw = 0.0, sse = 0.0, g[3], hs[6];
+        if (use_first) {
+            KFPOS_UNROLL
+            for (int k = 0; k < 3; ++k) g[k] = first.g[k];
+            KFPOS_UNROLL
+            for (int k = 0; k < 6; ++k) hs[k] = first.hs[k];
+        } else {
+            ml_sweep<false>(p, sc, pr, drop, cw, sse, g, hs);
+        }
+        if (keep_first) {
+            KFPOS_UNROLL
+            for (int k = 0; k < 3; ++k) first_out.g[k] = g[k];
+            KFPOS_UNROLL
+            for (int k = 0; k < 6; ++k) first_out.hs[k] = hs[k];
+        }
+        ml_step(p, g, hs);
+        int iter = 1;
+        for (;;) {
+            ml_sweep(p, sc, pr, drop, cw, sse, g, hs);
+            bool go_on; /* MLLocation.cpp:168 */
+            if constexpr (SC::COOP) go_on = fabs(cost - cw) / cost > 1e-3;
+            else go_on = rel_change_above_voted(cost, cw, 1e-3);
+            if (!(go_on && (iter < 10000))) break;
+            iter += 1;
+            cost = cw;
+            ml_step(p, g, hs);
+        }
+        sse_out = group_sum(sc, sse); /* (identity unless 8 lanes share the tag: ml_sweep) */
+        return iter;
     }
     double cost = 1e20, newCost = 1.0, cw = 0.0, sse = 0.0, g[3], hs[6], c[6];
     int iter = 0;
@@ -152,10 +206,10 @@ KFPOS_FN int ml_estimate(double p[3], const SC &sc, const Params &pr, uint64_t d
     return iter;
 }
 
-template <class SC>
+template <bool PEEL = true, class SC>
 KFPOS_FN int ml_estimate(double p[3], const SC &sc, const Params &pr, uint64_t drop, int n_used, double &sse_out) {
     MlFirst unused = {};
-    return ml_estimate(p, sc, pr, drop, n_used, sse_out, false, unused, false, unused);
+    return ml_estimate<PEEL>(p, sc, pr, drop, n_used, sse_out, false, unused, false, unused);
 }
 
 /* covariance of the ML estimate, inv(J' diag(max(e, e_ML))^-1 J) (MLLocation.cpp:229-252);
@@ -260,7 +314,7 @@ KFPOS_FN void set_weights_iekf(SC &sc, const Params &pr, double e_ml, uint64_t d
  *  - with at most two ranges to drop the two largest residuals are tracked in registers while they are computed, the
  *    working weights (1/e of every used range) stay where they are and only the dropped ones are zeroed: on return
  *    weights_kept says that the weights of the kept set are already in place (set_weights_ml(sc, pr, drop) done). */
-template <bool SHARE, class SC>
+template <bool SHARE, bool PEEL = true, class SC>
 KFPOS_FN uint64_t topn_mask(const double seed[3], SC &sc, const Params &pr, int n_valid, MlFirst &first_all,
                             bool &first_valid, bool &weights_kept, int *rank_iters = nullptr) {
     weights_kept = false;
@@ -272,7 +326,7 @@ KFPOS_FN uint64_t topn_mask(const double seed[3], SC &sc, const Params &pr, int 
     double p[3] = {seed[0], seed[1], seed[2]}, sse;
     set_weights_ml(sc, pr, 0ull);
     MlFirst unused = {};
-    const int it_rank = ml_estimate(p, sc, pr, 0, n_valid, sse, false, unused, SHARE, first_all);
+    const int it_rank = ml_estimate<PEEL>(p, sc, pr, 0, n_valid, sse, false, unused, SHARE, first_all);
     if (rank_iters) *rank_iters = it_rank;
     uint64_t drop = 0;
     if (SHARE && ndrop <= 2) {

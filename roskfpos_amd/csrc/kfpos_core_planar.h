@@ -413,8 +413,10 @@ KFPOS_FN void cov_update8(Cov<8, true> &P, const double m[3]) {
     }
 }
 
-/* KalmanFilter::estimatePositionKF (KalmanFilter.cpp:224-321) for one tag and one call carrying `rows`. */
-template <bool SENSORS, class SC>
+/* KalmanFilter::estimatePositionKF (KalmanFilter.cpp:224-321) for one tag and one call carrying `rows`.
+ * PEEL: the 3-D ML start runs ml_estimate's peeled text; false keeps the unpeeled one, same results, for a kernel that
+ * spills inside a loop with the other. */
+template <bool SENSORS, bool PEEL = true, class SC>
 KFPOS_FN uint32_t step_planar8(Tag8 &tg, SC &sc, const Params &pr, double dt, uint32_t rows, const Latch8 &lt,
                                CovSpill8 spill = CovSpill8{nullptr, 0}) {
     const bool has_r = (rows & ROW_RANGING) != 0;
@@ -435,7 +437,7 @@ KFPOS_FN uint32_t step_planar8(Tag8 &tg, SC &sc, const Params &pr, double dt, ui
         } else {
             if (n_valid < 4) return ST_FEW_RANGES;
             double p[3] = {1.0, 1.0, 4.0}, sse, c[6];
-            it = ml_estimate(p, sc, pr, 0, n_valid, sse);
+            it = ml_estimate<PEEL>(p, sc, pr, 0, n_valid, sse);
             if (ml_covariance_throws(sc, pr, 0, n_valid, sse)) return ST_UPDATE_SKIPPED;
             if (!ml_covariance(p, sc, pr, sse, c)) return ST_UPDATE_SKIPPED;
             tg.xy[0] = p[0]; tg.xy[1] = p[1];

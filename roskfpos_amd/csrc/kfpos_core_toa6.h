@@ -181,14 +181,14 @@ struct Iekf6Out {
 /* First half of kalmanStep3DIgnoreAnchor (KalmanFilterTOA.cpp:268-282): ML position -> observation
  * covariance. Touches the position and the epoch only, not P, so the kernels run it while the covariance
  * loads are still in flight. Leaves sc.w = 1/R. */
-template <class SC>
+template <bool PEEL = true, class SC>
 KFPOS_FN void iekf6_weights(const double xhat_p[3], SC &sc, const Params &pr, uint64_t drop, int n_used,
                             Iekf6Out &o, bool use_first, const MlFirst &first, bool keep_first, MlFirst &first_out,
                             bool weights_ready = false) {
     o.flags = (n_used < 4) ? ST_FEW_RANGES : 0u;
     double pml[3] = {xhat_p[0], xhat_p[1], xhat_p[2]}, e_ml;
     if (!weights_ready) set_weights_ml(sc, pr, drop); /* (the top-N ranking may have left them in place) */
-    o.ml_iters = ml_estimate(pml, sc, pr, drop, n_used, e_ml, use_first, first, keep_first, first_out);
+    o.ml_iters = ml_estimate<PEEL>(pml, sc, pr, drop, n_used, e_ml, use_first, first, keep_first, first_out);
     if (ml_covariance_throws(sc, pr, drop, n_used, e_ml)) o.flags |= ST_UPDATE_SKIPPED;
     if (isnan(pml[0]) || isnan(pml[1]) || isnan(pml[2])) {
         o.flags |= ST_ML_FALLBACK;
@@ -333,7 +333,9 @@ KFPOS_FN void cov_update6(Cov<6, SYMM> &P, const double m[6], bool pivot) {
 /* PARKN (symmetric layout only): the first PARKN covariance entries wait at park[k * park_stride] (LDS) while the
  * ML solve runs -- it does not touch P -- so that the solve has their registers: what lets the plain filter fit 256
  * registers, two wavefronts per SIMD (k_step_toa6_w2). */
-template <bool SYMM, int HEUR = 2, int PARKN = 0, class SC>
+/* PEEL: every Gauss-Newton solve of the step runs ml_estimate's peeled text; false keeps the unpeeled one, same
+ * results, for a kernel that spills inside a loop with the other. */
+template <bool SYMM, int HEUR = 2, int PARKN = 0, bool PEEL = true, class SC>
 KFPOS_FN uint32_t step_toa6(Tag6<SYMM> &tg, SC &sc, const Params &pr_in, double dt, double *park = nullptr,
                             int park_stride = 0) {
     static_assert(PARKN == 0 || SYMM, "the parking slots of the non-symmetric layout hold its pseudo-inverse");
@@ -351,7 +353,7 @@ KFPOS_FN uint32_t step_toa6(Tag6<SYMM> &tg, SC &sc, const Params &pr_in, double 
         if (n_valid < 4) return ST_FEW_RANGES;
         double p[3] = {1.0, 1.0, 4.0}, sse, c[6];
         set_weights_ml(sc, pr, 0ull);
-        const int it = ml_estimate(p, sc, pr, 0, n_valid, sse);
+        const int it = ml_estimate<PEEL>(p, sc, pr, 0, n_valid, sse);
         if (ml_covariance_throws(sc, pr, 0, n_valid, sse)) return ST_UPDATE_SKIPPED; /* reference: abort */
         if (!ml_covariance(p, sc, pr, sse, c)) return ST_UPDATE_SKIPPED;
         tg.pos[0] = p[0]; tg.pos[1] = p[1]; tg.pos[2] = p[2];
@@ -374,7 +376,7 @@ KFPOS_FN uint32_t step_toa6(Tag6<SYMM> &tg, SC &sc, const Params &pr_in, double 
     bool top_shared = false, top_weights = false;
     if (pr.top_n > 0 && !(isnan(tg.pos[0]) || isnan(tg.pos[1]) || isnan(tg.pos[2]))) {
         bool first_valid = false;
-        drop = topn_mask<SHARE_TOPN>(tg.pos, sc, pr, n_valid, first_top, first_valid, top_weights);
+        drop = topn_mask<SHARE_TOPN, PEEL>(tg.pos, sc, pr, n_valid, first_top, first_valid, top_weights);
         if (SHARE_TOPN && first_valid) { /* (nothing to drop: no ranking solve has run) */
             uint64_t rest = drop;
             KFPOS_UNROLL
@@ -456,7 +458,7 @@ KFPOS_FN uint32_t step_toa6(Tag6<SYMM> &tg, SC &sc, const Params &pr_in, double 
                 use_first = true;
             }
         }
-        iekf6_weights(xhat_p, sc, pr, mask, n_use, o, use_first, f, keep_first, first_all,
+        iekf6_weights<PEEL>(xhat_p, sc, pr, mask, n_use, o, use_first, f, keep_first, first_all,
                       SHARE_TOPN && last && top_weights);
         if (!predicted) { /* after the first ML solve: the covariance loads have landed by now */
             if constexpr (PARKN > 0) {

@@ -71,6 +71,9 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
      * measurements (22 more registers across the step) or the 4-byte covariance's rounding code the held values do not
      * fit: those two keep the tail that reads the park and a copy of the anchor table in every trip (iekf9_pairs). */
     constexpr bool TAIL = AS == 8 && RANGING && sizeof(MREAL) == 4 && !std::is_same<REAL, float>::value;
+    /* The Gauss-Newton solves in ml_estimate's peeled text (step_imu9_state). The same two 8-anchor instantiations as
+     * above, short of registers, spill inside the epoch loop with it and keep the unpeeled text. */
+    constexpr bool PEEL = AS != 8 || AHEAD;
     if constexpr (TAIL) pr.pair9 = a.pair9 != 0;
     else if constexpr (AS == 8 && RANGING) { /* the anchor table once more, where lanes can index it one by one */
         if (a.pair9) {
@@ -191,7 +194,7 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
             for (int k = 0; k < 6; ++k) { forget(o.w[k]); forget(o.mrlast[k]); }
 #pragma unroll
             for (int k = 0; k < 3; ++k) forget(o.dlast[k]);
-            const bool update = step_imu9_state_parked<RANGING, true, TAIL>(tg, sc, pr, dt, imu, park, fast, invertible, o, s);
+            const bool update = step_imu9_state_parked<RANGING, true, TAIL, PEEL>(tg, sc, pr, dt, imu, park, fast, invertible, o, s);
             if (a.traj) { /* the pose store between the two parts: see the other order below */
 #pragma unroll
                 for (int k = 0; k < 3; ++k) (a.traj + ((size_t)opaque_uniform(e) * 3 + k) * T)[t32] = tg.pos[k];
@@ -246,7 +249,7 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
 #pragma unroll
                 for (int k = 0; k < AS; ++k) sc.r[k] = sc.e[k] = sc.w[k] = 0.0;
             }
-            finish(step_imu9_state<RANGING, true, TAIL>(tg, sc, pr, dt, imu, park, fast, o, s));
+            finish(step_imu9_state<RANGING, true, TAIL, true, PEEL>(tg, sc, pr, dt, imu, park, fast, o, s));
             if constexpr (!AHEAD) { /* 8-byte measurements: the next epoch is fetched when this one is over */
                 if (e + 1 < a.n_steps) {
                     if (fresh_imu) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
@@ -256,7 +259,7 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
         } else {
             Scratch sc{nullptr, nullptr, nullptr, WAVE};
             if (has_ranging) sc = stage_epoch_lds<MREAL>(a, lds, lane, t, opaque_uniform(e));
-            finish(step_imu9_state<RANGING, true, TAIL>(tg, sc, pr, dt, imu, park, fast, o, s));
+            finish(step_imu9_state<RANGING, true, TAIL, true, PEEL>(tg, sc, pr, dt, imu, park, fast, o, s));
             if constexpr (!AHEAD) { /* the ranges are staged per epoch above; the next accelerometer sample is not */
                 if (e + 1 < a.n_steps && fresh_imu) fetch_imu<MREAL>(a, opaque_lane(t), opaque_uniform(e + 1), rawi);
             }

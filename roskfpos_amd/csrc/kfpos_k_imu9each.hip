@@ -28,6 +28,9 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9_each(const kfpos_k::EvEach
      * an epoch fetched ahead do not fit beside the per-lane dts and masks -- they spilled inside the loop, 52 / 68
      * bytes per lane -- so the ranges of the next slot are fetched between two slots */
     constexpr bool AHEAD = sizeof(MREAL) == 4 && !std::is_same<REAL, float>::value;
+    /* every 8-anchor instantiation spills inside the slot loop with the peeled Gauss-Newton text (step_imu9_state's
+     * PEEL): every instantiation of this kernel keeps the unpeeled text it always compiled */
+    constexpr bool PEEL = false;
     constexpr int NA = AS > 0 ? AS : 1;
     const int n = a.n_steps;
     /* the kind is wave-uniform and kept as an integer the optimiser cannot see through: carried round the loop as a
@@ -152,11 +155,11 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9_each(const kfpos_k::EvEach
                 RegScratch<AS> sc;
                 unpack_epoch<MREAL, AS>(raw, sc);
                 if constexpr (AHEAD) fetch_small();
-                if (run) update = step_imu9_state<true>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
+                if (run) update = step_imu9_state<true, true, false, true, PEEL>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
             } else {
                 Scratch sc = stage_epoch_lds<MREAL>(a, lds, lane, t, opaque_uniform(cur)); /* the whole wavefront */
                 if constexpr (AHEAD) fetch_small();
-                if (run) update = step_imu9_state<true>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
+                if (run) update = step_imu9_state<true, true, false, true, PEEL>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
             }
         } else { /* newIMUMeasurement: latch the sample, predict + IMU-only update */
             if (run) {
@@ -176,7 +179,7 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9_each(const kfpos_k::EvEach
             }
             if constexpr (AHEAD) fetch_small();
             Scratch sc{nullptr, nullptr, nullptr, WAVE};
-            if (run) update = step_imu9_state<false>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
+            if (run) update = step_imu9_state<false, true, false, true, PEEL>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
         }
         ran |= run;
         /* the pose store between the state part and the covariance part (k_step_imu9); a lane that sits the slot out

@@ -72,7 +72,9 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9(const kfpos_k::EvArgs ev) 
      * it spills inside the event loop, so its trips read them as before (make check's scratch rule decides) */
     constexpr bool HOLD = !(std::is_same<REAL, double>::value && sizeof(MREAL) == 4 && AS == 8);
     /* <p48, float, 8> spills inside the event loop with the select forms of the epoch's weights (step_imu9_state's
-     * SELECTS): every instantiation of this kernel keeps the conditional text it always compiled */
+     * SELECTS): every instantiation of this kernel keeps the conditional text it always compiled. The same goes for the
+     * peeled Gauss-Newton text (PEEL), with which all four 8-anchor instantiations spill */
+    constexpr bool PEEL = false;
     bool diag = false; /* the diagonal form of the gain iteration's pass: same bits (k_step_imu9) */
     if (a.imu9_diag) {
         const bool mine = imu.Wi(1) == 0.0 && imu.Wi(2) == 0.0 && imu.Wi(4) == 0.0;
@@ -112,11 +114,11 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9(const kfpos_k::EvArgs ev) 
                 RegScratch<AS> sc;
                 unpack_epoch<MREAL, AS>(raw, sc);
                 if constexpr (AHEAD) fetch_next();
-                update = step_imu9_state<true, HOLD, false, false>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
+                update = step_imu9_state<true, HOLD, false, false, PEEL>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
             } else {
                 Scratch sc = stage_epoch_lds<MREAL>(a, lds, lane, t, opaque_uniform(mine)); /* staged per event */
                 if constexpr (AHEAD) fetch_next();
-                update = step_imu9_state<true, HOLD, false, false>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
+                update = step_imu9_state<true, HOLD, false, false, PEEL>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
             }
         } else { /* newIMUMeasurement: latch the sample, predict + IMU-only update */
 #pragma unroll
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9(const kfpos_k::EvArgs ev) 
             sampled = 1;
             if constexpr (AHEAD) fetch_next();
             Scratch sc{nullptr, nullptr, nullptr, WAVE};
-            update = step_imu9_state<false, HOLD, false, false>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
+            update = step_imu9_state<false, HOLD, false, false, PEEL>(tg, sc, pr, dt, imu, park, imu9_fast(diag, imu.has), o, s);
         }
         /* the pose store between the state part and the covariance part (k_step_imu9) */
         if (a.traj) {

@@ -72,6 +72,9 @@ __global__ __launch_bounds__(WAVE) void k_step_planar(const KArgs a) {
     const int kind = a.mode;
     const bool has_ranging = kind == 0;
     constexpr int NA = AS > 0 ? AS : 1;
+    /* step_planar8's PEEL: the ML start in ml_estimate's peeled text. The sensor kernel over an LDS-resident 8-anchor
+     * epoch with the 48-bit covariance spills inside its epoch loop with it and keeps the unpeeled text. */
+    constexpr bool PEEL = !(SENS && AS == -8 && std::is_same<REAL, p48>::value);
     if (a.n_steps == 1 && a.dt && a.dt[t] < 0.0) { /* no epoch / sample for this tag in this call */
         skipped_lane(a, t, true);
         return;
@@ -167,14 +170,14 @@ __global__ __launch_bounds__(WAVE) void k_step_planar(const KArgs a) {
 #pragma unroll
                 for (int k = 0; k < AS; ++k) sc.r[k] = sc.e[k] = sc.w[k] = 0.0;
             }
-            s = step_planar8<SENS>(tg, sc, pr, dt, rows, lt, park);
+            s = step_planar8<SENS, PEEL>(tg, sc, pr, dt, rows, lt, park);
         } else if constexpr (AS < 0) { /* compile-time anchor loops over the LDS-resident epoch (ranging epochs only) */
             StaticScratch<-AS> sc = stage_epoch_lds_n<MREAL, -AS>(a, lds, lane, t, e);
-            s = step_planar8<SENS>(tg, sc, pr, dt, rows, lt, park);
+            s = step_planar8<SENS, PEEL>(tg, sc, pr, dt, rows, lt, park);
         } else {
             Scratch sc{nullptr, nullptr, nullptr, WAVE};
             if (has_ranging) sc = stage_epoch_lds<MREAL>(a, lds, lane, t, e);
-            s = step_planar8<SENS>(tg, sc, pr, dt, rows, lt, park);
+            s = step_planar8<SENS, PEEL>(tg, sc, pr, dt, rows, lt, park);
         }
         if (a.traj) { /* the pose a per-epoch caller would have read back (getPose at timeLag 0) */
             (a.traj + ((size_t)e * 3 + 0) * T)[t32] = tg.xy[0];

@@ -20,6 +20,10 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 2))) vo
     const uint32_t t32 = (uint32_t)t;
     const Params pr = make_params(a);
     constexpr int NA = AS > 0 ? AS : 1;
+    /* The Gauss-Newton solves in ml_estimate's peeled text (step_toa6's PEEL). The 8-anchor LDS form with both
+     * heuristics -- up to 65 solves around one inlined solver -- spills inside its loops with it and keeps the
+     * unpeeled text (make check's scratch rule decides). */
+    constexpr bool PEEL = !(AS == -8 && HEUR == 2);
     if (a.n_steps == 1 && a.dt && a.dt[t] < 0.0) { /* no epoch for this tag in this call */
         skipped_lane(a, t, true);
         return;
@@ -45,16 +49,16 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 2))) vo
             RegScratch<AS> sc;
             unpack_epoch<MREAL, AS>(raw, sc);
             if (e + 1 < a.n_steps) fetch_epoch<MREAL, AS>(a, t, e + 1, raw); /* next epoch in flight */
-            s = step_toa6<SYMM, HEUR>(tg, sc, pr, dt);
+            s = step_toa6<SYMM, HEUR, 0, PEEL>(tg, sc, pr, dt);
         } else if constexpr (AS < 0 && sizeof(MREAL) == 4) { /* compile-time count, epoch in LDS, 4-byte errorEstimations */
             StaticScratchF<-AS> sc = stage_epoch_lds_nf<-AS>(a, lds, lane, t, e);
-            s = step_toa6<SYMM, HEUR>(tg, sc, pr, dt, lds + static_epoch_doubles<MREAL, -AS>() + lane, WAVE);
+            s = step_toa6<SYMM, HEUR, 0, PEEL>(tg, sc, pr, dt, lds + static_epoch_doubles<MREAL, -AS>() + lane, WAVE);
         } else if constexpr (AS < 0) { /* compile-time count, epoch in LDS */
             StaticScratch<-AS> sc = stage_epoch_lds_n<MREAL, -AS>(a, lds, lane, t, e);
-            s = step_toa6<SYMM, HEUR>(tg, sc, pr, dt, lds + static_epoch_doubles<MREAL, -AS>() + lane, WAVE);
+            s = step_toa6<SYMM, HEUR, 0, PEEL>(tg, sc, pr, dt, lds + static_epoch_doubles<MREAL, -AS>() + lane, WAVE);
         } else {
             Scratch sc = stage_epoch_lds<MREAL>(a, lds, lane, t, e);
-            s = step_toa6<SYMM, HEUR>(tg, sc, pr, dt, lds + 3 * (size_t)a.A * WAVE + lane, WAVE);
+            s = step_toa6<SYMM, HEUR, 0, PEEL>(tg, sc, pr, dt, lds + 3 * (size_t)a.A * WAVE + lane, WAVE);
         }
         if (a.traj) { /* the pose a per-epoch caller would have read back (getPose at timeLag 0) */
 #pragma unroll

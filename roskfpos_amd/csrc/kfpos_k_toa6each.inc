@@ -24,6 +24,9 @@ __global__ __launch_bounds__(WAVE) void k_trace_toa6_each(const kfpos_k::TraceEa
     const uint32_t t32 = (uint32_t)t;
     const Params pr = make_params(a);
     constexpr int NA = AS > 0 ? AS : 1;
+    /* step_toa6's PEEL, as in k_step_toa6: here both 8-anchor forms with both heuristics spill inside the slot loop
+     * with the peeled Gauss-Newton text and keep the unpeeled one */
+    constexpr bool PEEL = !((AS == 8 || AS == -8) && HEUR == 2);
     constexpr int SZ = Cov<6, SYMM>::SZ;
     const int n = a.n_steps;
     auto load_dt = [&](int e) -> double { return (ev.dt_each + (size_t)e * T)[(uint32_t)opaque_lane(t)]; };
@@ -56,16 +59,16 @@ __global__ __launch_bounds__(WAVE) void k_trace_toa6_each(const kfpos_k::TraceEa
                 RegScratch<AS> sc;
                 unpack_epoch<MREAL, AS>(raw, sc);
                 if (more) fetch_epoch<MREAL, AS>(a, tl, opaque_uniform(e + 1), raw); /* next slot in flight */
-                if (run) s = step_toa6<SYMM, HEUR>(tg, sc, pr, dt);
+                if (run) s = step_toa6<SYMM, HEUR, 0, PEEL>(tg, sc, pr, dt);
             } else if constexpr (AS < 0 && sizeof(MREAL) == 4) { /* compile-time count, epoch in LDS, 4-byte errorEstimations */
                 StaticScratchF<-AS> sc = stage_epoch_lds_nf<-AS>(a, lds, lane, tl, opaque_uniform(e));
-                if (run) s = step_toa6<SYMM, HEUR>(tg, sc, pr, dt, lds + static_epoch_doubles<MREAL, -AS>() + lane, WAVE);
+                if (run) s = step_toa6<SYMM, HEUR, 0, PEEL>(tg, sc, pr, dt, lds + static_epoch_doubles<MREAL, -AS>() + lane, WAVE);
             } else if constexpr (AS < 0) { /* compile-time count, epoch in LDS */
                 StaticScratch<-AS> sc = stage_epoch_lds_n<MREAL, -AS>(a, lds, lane, tl, opaque_uniform(e));
-                if (run) s = step_toa6<SYMM, HEUR>(tg, sc, pr, dt, lds + static_epoch_doubles<MREAL, -AS>() + lane, WAVE);
+                if (run) s = step_toa6<SYMM, HEUR, 0, PEEL>(tg, sc, pr, dt, lds + static_epoch_doubles<MREAL, -AS>() + lane, WAVE);
             } else {
                 Scratch sc = stage_epoch_lds<MREAL>(a, lds, lane, tl, opaque_uniform(e));
-                if (run) s = step_toa6<SYMM, HEUR>(tg, sc, pr, dt, lds + 3 * (size_t)a.A * WAVE + lane, WAVE);
+                if (run) s = step_toa6<SYMM, HEUR, 0, PEEL>(tg, sc, pr, dt, lds + 3 * (size_t)a.A * WAVE + lane, WAVE);
             }
             ran |= run;
         } else {
