@@ -5,31 +5,26 @@ import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import epoch_loop_waits as elw  # noqa: E402
-
-NAME = "_ZN12_GLOBAL__N_111k_step_imu9IdfLi8ELb1EEEvN7kfpos_k5KArgsE"
+from disasm_fragment import NAME, Fragment  # noqa: E402
 
 
 def fragment(gap):
     """A kernel in llvm-objdump's format: a prologue with a load and its wait (outside the loop: not the rule's
     business), then one loop = load, `gap` - 1 arithmetic instructions, s_waitcnt vmcnt(0), a store, 350 more
     arithmetic instructions (so that the store is far from the wait around the back-edge), backward branch."""
-    body = ["global_load_dwordx2 v[0:1], v2, s[0:1]", "s_waitcnt vmcnt(0)", "v_mov_b32_e32 v9, 0"]
-    loop_at = len(body)
-    body += ["global_load_dword v3, v2, s[4:5]"]
-    body += ["v_fma_f64 v[4:5], v[0:1], v[0:1], v[4:5]"] * (gap - 1)
-    body += ["s_waitcnt vmcnt(0)", "v_cvt_f64_f32_e32 v[6:7], v3", "global_store_dwordx2 v2, v[4:5], s[6:7]"]
-    body += ["v_add_f64 v[4:5], v[4:5], v[6:7]"] * 350
-    body += ["s_add_i32 s8, s8, 1", "s_cmp_lt_i32 s8, s9", "s_cbranch_scc1 LOOP", "s_endpgm"]
-    base = 0x1000
-    lines = [f"{base:016x} <{NAME}>:"]
-    for i, ins in enumerate(body):
-        tail = ""
-        if ins.endswith("LOOP"):
-            ins = ins.replace("LOOP", str(loop_at - i - 1 + 65536))
-            tail = f" <{NAME}+{4 * loop_at:#x}>"
-        lines.append(f"\t{ins}  // {base + 4 * i:012X}: BF800000{tail}")
-    return "\n".join(lines) + "\n"
+    k = Fragment()
+    k.emit("global_load_dwordx2 v[0:1], v2, s[0:1]", "s_waitcnt vmcnt(0)", "v_mov_b32_e32 v9, 0")
+    k.label("LOOP")
+    k.emit("global_load_dword v3, v2, s[4:5]")
+    k.emit(*["v_fma_f64 v[4:5], v[0:1], v[0:1], v[4:5]"] * (gap - 1))
+    k.emit("s_waitcnt vmcnt(0)", "v_cvt_f64_f32_e32 v[6:7], v3", "global_store_dwordx2 v2, v[4:5], s[6:7]")
+    k.emit(*["v_add_f64 v[4:5], v[4:5], v[6:7]"] * 350)
+    k.emit("s_add_i32 s8, s8, 1", "s_cmp_lt_i32 s8, s9")
+    k.branch("s_cbranch_scc1", "LOOP")
+    k.emit("s_endpgm")
+    return k.text()
 
 
 def test_wait_ten_instructions_behind_its_load_fails():

@@ -9,11 +9,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "roskfpos_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import epoch_turnaround_shape as ets  # noqa: E402
+from disasm_fragment import FMA, KERNEL, NAME, Fragment  # noqa: E402
 
-NAME = "_ZN12_GLOBAL__N_111k_step_imu9IdfLi8ELb1EEEvN7kfpos_k5KArgsE"
-KERNEL = (r"k_step_imu9IdfLi8ELb1E",)
-FMA = "v_fma_f64 v[4:5], v[0:1], v[0:1], v[4:5]"
 
 
 def fragment(latch_copies=(), body_copies=()):
@@ -21,17 +20,8 @@ def fragment(latch_copies=(), body_copies=()):
     a nested trip loop of 40 fp64 instructions, a divergent early exit that reloads from LDS, a covariance update, and a
     latch block of its own -- entered by a branch, so that it holds nothing but what the back-edge costs -- with
     `latch_copies`. body_copies go into the covariance update (none of the rule's business)."""
-    body, labels, fix = [], {}, []
-
-    def emit(*ins):
-        body.extend(ins)
-
-    def label(name):
-        labels[name] = len(body)
-
-    def branch(op, name):
-        fix.append((len(body), name))
-        body.append(op)
+    kernel = Fragment()
+    emit, label, branch = kernel.emit, kernel.label, kernel.branch
 
     emit("global_load_dwordx2 v[0:1], v2, s[0:1]", "s_waitcnt vmcnt(0)", *[FMA] * 10)
     label("EPOCH")
@@ -51,14 +41,7 @@ def fragment(latch_copies=(), body_copies=()):
     branch("s_branch", "EPOCH")
     label("DONE")
     emit("global_store_dwordx2 v2, v[4:5], s[0:1]", "s_endpgm")
-    base = 0x1000
-    tails = {i: f" <{NAME}+{4 * labels[name]:#x}>" for i, name in fix}
-    lines = [f"{base:016x} <{NAME}>:"]
-    for i, ins in enumerate(body):
-        if i in tails:
-            ins += f" {(labels[dict(fix)[i]] - i - 1) % 65536}"
-        lines.append(f"\t{ins}  // {base + 4 * i:012X}: BF800000{tails.get(i, '')}")
-    return "\n".join(lines) + "\n"
+    return kernel.text()
 
 
 # position and velocity to where the header expects them, three words: what a lane legitimately carries

@@ -10,11 +10,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "roskfpos_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import epoch_weights_branches as ewb  # noqa: E402
+from disasm_fragment import FMA, KERNEL, NAME, Fragment  # noqa: E402
 
-NAME = "_ZN12_GLOBAL__N_111k_step_imu9IdfLi8ELb1EEEvN7kfpos_k5KArgsE"
-KERNEL = (r"k_step_imu9IdfLi8ELb1E",)
-FMA = "v_fma_f64 v[4:5], v[0:1], v[0:1], v[4:5]"
 LOAD = "global_load_dword v9, v[2:3], off"
 SELECT = "v_cndmask_b32_e32 v7, 0, v7, vcc"
 
@@ -23,17 +22,8 @@ def fragment(regions=0, regions_in_solve=0, regions_behind=0, loads=16):
     """A kernel in llvm-objdump's format: a prologue; an epoch loop whose header unpacks (`loads` loads); `regions`
     masked regions of a reciprocal each (saveexec, execz, five fp64, restore); a Gauss-Newton loop of 60 fp64 with
     `regions_in_solve` regions inside; eight selects; a trip loop of 420 fp64; `regions_behind` regions; the latch."""
-    body, labels, fix = [], {}, []
-
-    def emit(*ins):
-        body.extend(ins)
-
-    def label(name):
-        labels[name] = len(body)
-
-    def branch(op, name):
-        fix.append((len(body), name))
-        body.append(op)
+    kernel = Fragment()
+    emit, label, branch = kernel.emit, kernel.label, kernel.branch
 
     def region(tag):
         emit("v_cmp_lt_f64_e32 vcc, 0, v[10:11]", "s_and_saveexec_b64 s[10:11], vcc")
@@ -62,14 +52,7 @@ def fragment(regions=0, regions_in_solve=0, regions_behind=0, loads=16):
     emit("ds_write_b64 v240, v[20:21]", "s_add_i32 s8, s8, 1", "s_cmp_lt_i32 s8, s9")
     branch("s_cbranch_scc1", "EPOCH")
     emit("global_store_dwordx2 v2, v[4:5], s[0:1]", "s_endpgm")
-    base = 0x1000
-    tails = {i: f" <{NAME}+{4 * labels[name]:#x}>" for i, name in fix}
-    lines = [f"{base:016x} <{NAME}>:"]
-    for i, ins in enumerate(body):
-        if i in tails:
-            ins += f" {(labels[dict(fix)[i]] - i - 1) % 65536}"
-        lines.append(f"\t{ins}  // {base + 4 * i:012X}: BF800000{tails.get(i, '')}")
-    return "\n".join(lines) + "\n"
+    return kernel.text()
 
 
 def _check(text, **kw):

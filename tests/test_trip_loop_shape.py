@@ -9,12 +9,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "roskfpos_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import trip_loop_shape as tls  # noqa: E402
-
-NAME = "_ZN12_GLOBAL__N_111k_step_imu9IdfLi8ELb1EEEvN7kfpos_k5KArgsE"
-KERNEL = (r"k_step_imu9IdfLi8ELb1E",)
-FMA = "v_fma_f64 v[4:5], v[0:1], v[0:1], v[4:5]"
-
+from disasm_fragment import FMA, KERNEL, NAME, Fragment  # noqa: E402
 
 PER_LANE = ("s_and_saveexec_b64 s[90:91], s[6:7]", "s_cbranch_execz 0 <NEXT>", FMA, FMA, "s_or_b64 exec, exec, s[90:91]")
 
@@ -26,17 +23,8 @@ def fragment(in_trip=(), extra_branches=0, solve=300):
     instructions, the back-edge = 4 branches a trip. in_trip: instructions put into the sweep (PER_LANE: the masked
     block of the per-lane form, whose branch goes to the next instruction); extra_branches: that many more conditional
     branches (to the next instruction) in the sweep."""
-    body, labels, fix = [], {}, []
-
-    def emit(*ins):
-        body.extend(ins)
-
-    def label(name):
-        labels[name] = len(body)
-
-    def branch(op, name):
-        fix.append((len(body), name))
-        body.append(op)
+    kernel = Fragment()
+    emit, label, branch = kernel.emit, kernel.label, kernel.branch
 
     emit("global_load_dwordx2 v[0:1], v2, s[0:1]", "s_waitcnt vmcnt(0)")
     label("EPOCH")
@@ -47,8 +35,8 @@ def fragment(in_trip=(), extra_branches=0, solve=300):
     emit(*[FMA] * 160)
     for ins in in_trip:
         if ins.endswith(" 0 <NEXT>"):
-            branch(ins[:-len(" 0 <NEXT>")], f"N{len(body)}")
-            label(f"N{len(body) - 1}")
+            branch(ins[:-len(" 0 <NEXT>")], f"N{len(kernel.body)}")
+            label(f"N{len(kernel.body) - 1}")
         else:
             emit(ins)
     for k in range(extra_branches):
@@ -66,14 +54,7 @@ def fragment(in_trip=(), extra_branches=0, solve=300):
     emit("s_or_b64 exec, exec, s[30:31]", *[FMA] * 20, "s_add_i32 s8, s8, 1", "s_cmp_lt_i32 s8, s9")
     branch("s_cbranch_scc1", "EPOCH")
     emit("s_endpgm")
-    base = 0x1000
-    tails = {i: f" <{NAME}+{4 * labels[name]:#x}>" for i, name in fix}
-    lines = [f"{base:016x} <{NAME}>:"]
-    for i, ins in enumerate(body):
-        if i in tails:
-            ins += f" {(labels[dict(fix)[i]] - i - 1) % 65536}"
-        lines.append(f"\t{ins}  // {base + 4 * i:012X}: BF800000{tails.get(i, '')}")
-    return "\n".join(lines) + "\n"
+    return kernel.text()
 
 
 def _check(text, **kw):

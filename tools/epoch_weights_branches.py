@@ -22,28 +22,27 @@ that count with the instruction mix of the stretch and fails when the count is a
 usage: epoch_weights_branches.py LIB [--kernel REGEX ...] [--max-execz 12] [--min-loads 8] [--quiet]
 (LIB: the library, or a disassembly as .s / .txt; --quiet: the verdict only)
 """
-import os
-import re
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from epoch_loop_waits import KERNELS, VMEM, parse  # noqa: E402  (same kernels, same disassembly parsing)
-from epoch_turnaround_shape import COLUMNS, epoch_loop, mix  # noqa: E402
-from trip_loop_shape import trip_loops  # noqa: E402
+from kernel_text import KERNELS, VMEM, indices, kernels_matching, largest_loop, main, mix, parsed, trip_loops
 
 MAX_EXECZ = 12
 MIN_LOADS = 8
+OPTIONS = (("--max-execz", int, MAX_EXECZ), ("--min-loads", int, MIN_LOADS))
+HEADING = "the weights of a 9-state epoch are masked regions again, not selects"
+COLUMNS = ("instructions", "fp64", "valu_other", "agpr_read", "agpr_write", "v_mov", "lane_read", "lane_write", "ds",
+           "vmem", "salu", "branches", "saveexec", "mem_waits")
 
 
 def stretch(ins, min_loads=MIN_LOADS):
     """(blocks of the stretch, address of the unpack block, address of the first trip loop, cfg), or a string that says
     what is missing"""
-    found = epoch_loop(ins)
+    found = largest_loop(ins)
     if found is None:
         return "no loop"
     _, _, _, outside, cfg = found
-    starts, ends, _ = cfg
-    loads = lambda b: sum(ins[i][1].startswith(VMEM) for i in range(starts[b], ends[b]))
+    starts = cfg[0]
+    loads = lambda b: sum(ins[i][1].startswith(VMEM) for i in indices(cfg, [b]))
     unpack = next((b for b in sorted(outside) if loads(b) >= min_loads), None)
     if unpack is None:
         return f"no block of the epoch loop with {min_loads} vector-memory instructions: where is the unpack?"
@@ -57,59 +56,30 @@ def stretch(ins, min_loads=MIN_LOADS):
 
 def check(text, kernels=KERNELS, max_execz=MAX_EXECZ, min_loads=MIN_LOADS, report=None):
     problems = []
-    insns = parse(text)
-    for pattern in kernels:
-        names = [f for f in insns if re.search(pattern, f) and insns[f]]
-        if not names:
-            problems.append(f"{pattern}: no kernel of that name")
-        for f in names:
-            ins = insns[f]
-            found = stretch(ins, min_loads)
-            if isinstance(found, str):
-                problems.append(f"{f}: {found}")
-                continue
-            between, a_unpack, a_trip, (starts, ends, _) = found
-            idx = [i for b in between for i in range(starts[b], ends[b])]
-            last_of_unpack = max(i for i in range(len(ins)) if ins[i][0] < ins[starts[between[0]]][0]) if between else None
-            execz = sum(ins[i][1] == "s_cbranch_execz" for i in idx)
-            execz += last_of_unpack is not None and ins[last_of_unpack][1] == "s_cbranch_execz"
-            if report is not None:
-                m = mix(ins, idx)
-                m["saveexec"] = sum("saveexec" in ins[i][1] for i in idx)
-                m["mem_waits"] = sum(ins[i][1] == "s_waitcnt" and ("lgkmcnt" in ins[i][2] or "vmcnt" in ins[i][2])
-                                     for i in idx)
-                report.append(f"{f}: unpack block at {a_unpack:#x}, first trip loop at {a_trip:#x}, {len(between)} blocks "
-                              "outside nested loops between them: "
-                              + ", ".join(f"{c} {m[c]}" for c in COLUMNS + ("saveexec", "mem_waits")))
-                report.append(f"{f}: {execz} s_cbranch_execz between the unpack and the first trip loop")
-            if execz > max_execz:
-                problems.append(f"{f}: {execz} s_cbranch_execz between the unpack block at {a_unpack:#x} and the first "
-                                f"trip loop at {a_trip:#x} (maximum {max_execz})")
+    for f, ins in kernels_matching(parsed(text), kernels, problems):
+        found = stretch(ins, min_loads)
+        if isinstance(found, str):
+            problems.append(f"{f}: {found}")
+            continue
+        between, a_unpack, a_trip, cfg = found
+        idx = indices(cfg, between)
+        last_of_unpack = max(i for i in range(len(ins)) if ins[i][0] < ins[idx[0]][0]) if between else None
+        execz = sum(ins[i][1] == "s_cbranch_execz" for i in idx)
+        execz += last_of_unpack is not None and ins[last_of_unpack][1] == "s_cbranch_execz"
+        if report is not None:
+            report.append(f"{f}: unpack block at {a_unpack:#x}, first trip loop at {a_trip:#x}, {len(between)} blocks "
+                          "outside nested loops between them: "
+                          + ", ".join(f"{c} {n}" for c, n in mix(ins, idx, COLUMNS).items()))
+            report.append(f"{f}: {execz} s_cbranch_execz between the unpack and the first trip loop")
+        if execz > max_execz:
+            problems.append(f"{f}: {execz} s_cbranch_execz between the unpack block at {a_unpack:#x} and the first "
+                            f"trip loop at {a_trip:#x} (maximum {max_execz})")
     return problems
 
 
+def verdict(insns, opts):
+    return f"at most {opts['max_execz']} s_cbranch_execz between the unpack of a 9-state epoch and its first trip loop"
+
+
 if __name__ == "__main__":
-    args = sys.argv[1:]
-    kernels, mx, ml = [], MAX_EXECZ, MIN_LOADS
-    quiet = "--quiet" in args
-    if quiet:
-        args.remove("--quiet")
-    while "--kernel" in args:
-        i = args.index("--kernel"); kernels.append(args[i + 1]); del args[i:i + 2]
-    if "--max-execz" in args:
-        i = args.index("--max-execz"); mx = int(args[i + 1]); del args[i:i + 2]
-    if "--min-loads" in args:
-        i = args.index("--min-loads"); ml = int(args[i + 1]); del args[i:i + 2]
-    if args[0].endswith((".s", ".txt")):
-        text = open(args[0]).read()
-    else:
-        from check_scratch import disassemble
-        text = disassemble(args[0])
-    rep = []
-    probs = check(text, tuple(kernels) or KERNELS, mx, ml, rep)
-    if rep and not quiet:
-        print("\n".join(rep))
-    if probs:
-        print("the weights of a 9-state epoch are masked regions again, not selects:\n" + "\n".join(probs))
-        sys.exit(1)
-    print(f"at most {mx} s_cbranch_execz between the unpack of a 9-state epoch and its first trip loop")
+    main(sys.modules[__name__])
