@@ -6,12 +6,11 @@ epoch, x, P, flags and status words.
 
 The synthetic trace has the same dt in every epoch after the first, which would hide an off-by-one in the dt that is read
 ahead: these tests give every epoch its own."""
-import contextlib
-import os
 
 import numpy as np
 import pytest
 
+import replay_checks as rc
 from conftest import has_gpu
 from roskfpos_amd.synth import Workload
 
@@ -20,25 +19,6 @@ pytestmark = pytest.mark.gpu
 
 def _dts(S):
     return np.array([0.03 + 0.01 * (s % 5) for s in range(S)])
-
-
-@contextlib.contextmanager
-def _env(**kv):
-    """environment variables the library reads in kfpos_create"""
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _trace(w, S, storage, dev, cov=None):
@@ -57,7 +37,7 @@ def _trace(w, S, storage, dev, cov=None):
 
 def _bank(w, T, storage, chunk=None, diag=None, init=True):
     from roskfpos_amd import capi
-    with _env(KFPOS_TRACE_CHUNK_STEPS=chunk, KFPOS_IMU9_DIAG=diag):
+    with rc.env(KFPOS_TRACE_CHUNK_STEPS=chunk, KFPOS_IMU9_DIAG=diag):
         return capi.KfposBank(capi.MODEL_TOA_IMU, T, w.anchors, storage=storage,
                               init_pos=w.init_positions() if init else None)
 

@@ -19,7 +19,8 @@ import pytest
 
 import ml_seed_cases as mc
 from conftest import has_gpu
-from test_imu9_epoch_loop_gpu import _env, _fused
+from replay_checks import env
+from test_imu9_epoch_loop_gpu import _fused
 from test_pairs9_tail_gpu import _same_bits, _single_calls
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +41,7 @@ def _trace(w, r, err, real, dev):
 
 def _bank(w, init, T, model, storage, no_coop):
     from roskfpos_amd import capi
-    with _env(KFPOS_NO_COOP=no_coop, KFPOS_TRACE_CHUNK_STEPS=25):
+    with env(KFPOS_NO_COOP=no_coop, KFPOS_TRACE_CHUNK_STEPS=25):
         return capi.KfposBank(model, T, w.anchors, storage=storage, init_pos=init)
 
 

@@ -21,8 +21,9 @@ import numpy as np
 import pytest
 
 from conftest import has_gpu
+from replay_checks import env
 from roskfpos_amd.synth import Workload
-from test_imu9_epoch_loop_gpu import _dts, _env, _fused, _per_epoch, _trace
+from test_imu9_epoch_loop_gpu import _dts, _fused, _per_epoch, _trace
 
 pytestmark = pytest.mark.gpu
 
@@ -74,7 +75,7 @@ def _seed():
 
 def _bank(w, T, storage, pairs, chunk=None, diag=None):
     from roskfpos_amd import capi
-    with _env(KFPOS_PAIR9=None if pairs else 0, KFPOS_TRACE_CHUNK_STEPS=chunk, KFPOS_IMU9_DIAG=diag):   # None: unset
+    with env(KFPOS_PAIR9=None if pairs else 0, KFPOS_TRACE_CHUNK_STEPS=chunk, KFPOS_IMU9_DIAG=diag):   # None: unset
         return capi.KfposBank(capi.MODEL_TOA_IMU, T, w.anchors, storage=storage, init_pos=w.init_positions())
 
 

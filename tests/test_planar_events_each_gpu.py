@@ -6,15 +6,14 @@ rows, the status word and the position of every slot -- and stays with the oracl
 One schedule serves every test (tests/planar_events_each.py; tests/test_planar_events_each_schedule.py asserts on the
 CPU that it holds what it is meant to hold): the kinds of tests/planar_events.py and an explicit participation mask over
 130 tags. Absent (tag, slot) pairs and dropped PX4Flow samples carry NaN / a sentinel range in the inputs."""
-import contextlib
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import planar_events as pe
 import planar_events_each as pee
+import replay_checks as rc
 from conftest import has_gpu
 
 pytestmark = pytest.mark.gpu
@@ -27,31 +26,11 @@ ST_SKIPPED = pee.ST_SKIPPED
 SENTINEL = -12345.6789
 
 
-@contextlib.contextmanager
-def _env(**kv):
-    """environment variables the library reads in kfpos_create"""
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 class Inputs:
     """a schedule's inputs in HBM, component-major; tags: the columns of the 130-tag schedule the bank holds"""
 
     def __init__(self, A, storage, start, end_on_sensor=True, waiting=False, kinds=None, tags=None, fill=True,
                  dev="cuda:0"):
-        import torch
         from roskfpos_amd import capi
         tags = np.arange(T) if tags is None else np.asarray(tags)
         self.T, self.A, self.storage, self.start = tags.size, A, storage, start
@@ -61,7 +40,7 @@ class Inputs:
         self.mask, self.ran, self.dt = es.mask[:, tags], es.ran[:, tags], es.dt[:, tags]
         init = pe.init_of(es.sch, start)
         self.init = None if init is None else init[tags]
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        up = lambda a: rc.up(a, dev)  # noqa: E731
         self.d_r = up(es.ranges[:, tags].transpose(0, 2, 1))
         self.d_e = up(es.sch.err[tags].T)
         self.d_s = {kind: up(es.samples[kind][:, tags].transpose(0, 2, 1)) for kind in pe.WIDTH}     # (n, C, T)
@@ -69,7 +48,7 @@ class Inputs:
 
     def bank(self, chunk=None):
         from roskfpos_amd import capi
-        with _env(KFPOS_TRACE_CHUNK_STEPS=chunk):
+        with rc.env(KFPOS_TRACE_CHUNK_STEPS=chunk):
             return capi.KfposBank(capi.MODEL_PLANAR, self.T, self.es.sch.w.anchors, storage=self.storage,
                                   init_pos=self.init, planar=pe.cfg_of(self.start))
 
@@ -79,93 +58,36 @@ def _final(b):
     return x, P, fl, b.get_latch(), b.get_height()
 
 
-def _events(kinds):
-    n = [0] * 5
-    for e, kind in enumerate(kinds):
-        yield e, int(kind), n[kind]
-        n[kind] += 1
+def _single(b, inp, e, kind, i, status, stream, dt):
+    if kind == pe.TOA:
+        b.step_toa_dev(inp.d_r[i], inp.d_e, 0.0, status=status, stream=stream, dt_dev=dt)
+    else:
+        b.step_sensor_dev(kind, inp.d_s[kind][i], 0.0, status=status, stream=stream, dt_dev=dt)
 
 
-def _single_calls(b, inp, d_dt=None, n_slots=None):
-    """the slots as single _dev calls with the slot's dt array -> (position after every slot, status of every slot, x,
-    P, flags, latch, height)"""
-    import torch
-    d_dt = inp.d_dt if d_dt is None else d_dt
-    n, nt = n_slots or inp.kinds.size, inp.T
-    st = torch.full((n, nt), -1, dtype=torch.int32, device=inp.d_r.device)
-    stream = torch.cuda.current_stream().cuda_stream
-    traj = np.zeros((n, 3, nt))
-    for e, kind, i in _events(inp.kinds[:n]):
-        if kind == pe.TOA:
-            b.step_toa_dev(inp.d_r[i], inp.d_e, 0.0, status=st[e], stream=stream, dt_dev=d_dt[e])
-        else:
-            b.step_sensor_dev(kind, inp.d_s[kind][i], 0.0, status=st[e], stream=stream, dt_dev=d_dt[e])
-        torch.cuda.synchronize()
-        traj[e, :2] = b.get_state()[0][:, :2].T
-        traj[e, 2] = b.get_height()
-    return (traj, st.cpu().numpy()) + _final(b)
-
-
-def _one_call(b, inp, outputs=True, d_dt=None, n_slots=None, call="run_planar_events_each_dev", dts=None):
-    import torch
-    n, nt, A = n_slots or inp.kinds.size, inp.T, inp.A
-    dev = inp.d_r.device
-    traj = torch.full((n, 3, nt), 7.0, dtype=torch.float64, device=dev) if outputs else None
-    ste = torch.full((n, nt), -1, dtype=torch.int32, device=dev) if outputs else None
-    st = torch.full((nt,), -1, dtype=torch.int32, device=dev)
-    if dts is None:
-        dts = (inp.d_dt if d_dt is None else d_dt)[:n]
-    s = inp.d_s
-    getattr(b, call)(inp.kinds[:n], dts, range_mm=inp.d_r, stride_ranges=A * nt, err_est=inp.d_e, stride_err=0,
-                     px4flow=s[pe.PX4], stride_px4flow=5 * nt, imu=s[pe.IMU], stride_imu=24 * nt,
-                     mag=s[pe.MAG], stride_mag=3 * nt, compass=s[pe.COMPASS], stride_compass=nt,
-                     trajectory=traj, status_events=ste, status=st, stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    last = st.cpu().numpy()
-    if not outputs:
-        return (None, last) + _final(b)
-    assert np.array_equal(last, ste[-1].cpu().numpy()), "status is not the last slot's"
-    return (traj.cpu().numpy(), ste.cpu().numpy()) + _final(b)
+def _call(method):
+    def call(b, inp, n, dts, traj, ste, st, stream):
+        nt, A, s = inp.T, inp.A, inp.d_s
+        getattr(b, method)(inp.kinds[:n], dts, range_mm=inp.d_r, stride_ranges=A * nt, err_est=inp.d_e, stride_err=0,
+                           px4flow=s[pe.PX4], stride_px4flow=5 * nt, imu=s[pe.IMU], stride_imu=24 * nt,
+                           mag=s[pe.MAG], stride_mag=3 * nt, compass=s[pe.COMPASS], stride_compass=nt,
+                           trajectory=traj, status_events=ste, status=st, stream=stream)
+    return call
 
 
 NAMES = ("position after every slot", "status of every slot", "x", "P", "flags", "latch", "height")
-
-
-def _same_bytes(got, ref, what, first=0):
-    for g, r, name in list(zip(got, ref, NAMES))[first:]:
-        assert g.shape == r.shape and g.dtype == r.dtype, (what, name)
-        assert g.tobytes() == r.tobytes(), (what, name)
-
-
-def _check_one_call(inp, what, prepare=None, chunks=(None, 7), d_dt=None, n_slots=None):
-    """single calls against one call per chunk size, and once with trajectory = status_events = NULL"""
-    def bank(chunk=None):
-        b = inp.bank(chunk)
-        if prepare:
-            prepare(b)
-        return b
-
-    b = bank()
-    ref = _single_calls(b, inp, d_dt, n_slots)
-    b.close()
-    for chunk in chunks:
-        b = bank(chunk)
-        got = _one_call(b, inp, d_dt=d_dt, n_slots=n_slots)
-        b.close()
-        _same_bytes(got, ref, f"{what} chunk={chunk}")
-    b = bank(chunks[-1])
-    bare = _one_call(b, inp, outputs=False, d_dt=d_dt, n_slots=n_slots)
-    b.close()
-    assert bare[1].tobytes() == ref[1][-1].tobytes(), (what, "last status")
-    _same_bytes(bare, ref, f"{what} without per-slot outputs", first=2)
-    return ref
+EACH = rc.Family(names=NAMES, n_kinds=5, dts=lambda inp: inp.d_dt, final=_final,
+                 position=lambda b: np.vstack([b.get_state()[0][:, :2].T, b.get_height()]),
+                 single=_single, call=_call("run_planar_events_each_dev"))
+# the shared-timeline entry point over the same inputs; its dts: one scalar per slot
+SHARED = rc.Family(**{**vars(EACH), "call": _call("run_planar_events_dev")})
 
 
 def _bit_identity(A, storage, combos, tags=None):
     for start, end_on_sensor, waiting in combos:
         inp = Inputs(A, storage, start, end_on_sensor, waiting, tags=tags)
         what = f"start={start} end_on_sensor={end_on_sensor} waiting={waiting}"
-        ref = _check_one_call(inp, what)
+        ref = rc.check_one_call(EACH, inp, what)
         words = ref[1]
         assert np.array_equal(words == ST_SKIPPED, ~inp.ran), what   # the reference run skips where the schedule says
         if inp.T > 1:
@@ -220,15 +142,15 @@ def test_a_schedule_that_crosses_the_launch_boundary():
     assert inp.kinds.size >= 130 and lead == 1 and len(pe.launch_starts(inp.kinds, 128)) == 2
     assert set(inp.kinds[lead + 64:lead + 128].tolist()) == {0, 1, 2, 3, 4}
     b = inp.bank()
-    ref = _single_calls(b, inp)
+    ref = rc.single_calls(EACH, b, inp)
     b.close()
     assert np.array_equal(ref[1] == ST_SKIPPED, ~inp.ran)
     low = ref[1][inp.ran] & 0xFF
     assert (low == 0).mean() > 0.5 and (low != 0).any() and np.isfinite(ref[0][-1]).all()
     b = inp.bank()
-    got = _one_call(b, inp)
+    got = rc.one_call(EACH, b, inp)
     b.close()
-    _same_bytes(got, ref, "four times the schedule")
+    rc.same_bytes(got, ref, NAMES, "four times the schedule")
 
 
 @pytest.mark.parametrize("start,waiting,storage,A", [("fixed", False, 2, 5), ("fixed_free", False, 3, 8),
@@ -256,9 +178,9 @@ def test_leading_ranging_slots_on_a_fresh_handle_and_on_one_with_latches(storage
     inp = Inputs(A, storage, "fixed", kinds=LEAD)
     lead = inp.mask[:3]
     assert (~lead).any(axis=1).all() and lead.any(axis=1).all() and not lead[:, 64:128].all(axis=0).all()
-    ref = _check_one_call(inp, "fresh handle", chunks=(None, 3))
+    ref = rc.check_one_call(EACH, inp, "fresh handle", chunks=(None, 3))
     assert (ref[4][np.arange(T) != pee.NOWHERE] & FL_STARTED).all()
-    _check_one_call(inp, "fresh handle, ranging slots only", chunks=(None, 2), n_slots=3)
+    rc.check_one_call(EACH, inp, "fresh handle, ranging slots only", chunks=(None, 2), n_slots=3)
 
     def prepare(b):
         stream = torch.cuda.current_stream().cuda_stream
@@ -266,9 +188,9 @@ def test_leading_ranging_slots_on_a_fresh_handle_and_on_one_with_latches(storage
             b.step_sensor_dev(kind, inp.d_s[kind][-1], 0.01, stream=stream, dt_dev=inp.d_dt[-1])
         torch.cuda.synchronize()
 
-    latched = _check_one_call(inp, "latched before the call", prepare, chunks=(None, 3))
+    latched = rc.check_one_call(EACH, inp, "latched before the call", prepare, chunks=(None, 3))
     assert latched[3].tobytes() != ref[3].tobytes()               # the leading slots carried the latches
-    _check_one_call(inp, "latched before the call, ranging slots only", prepare, chunks=(None, 2), n_slots=3)
+    rc.check_one_call(EACH, inp, "latched before the call, ranging slots only", prepare, chunks=(None, 2), n_slots=3)
 
 
 @pytest.mark.parametrize("storage,A,start", [(3, 8, "fixed"), (1, 5, "ml3d"), (3, 5, "ml2d"), (1, 8, "fixed")])
@@ -307,7 +229,7 @@ def test_a_tag_that_runs_nothing_keeps_every_stored_byte(storage, A, start):
         b.set_tags([6], flags=np.array([FL_STARTED | HAS_PX4 | HAS_MAG], dtype=np.uint32))
         before = b.get_tags(quiet)
         assert before[2].tolist() == [0, FL_STARTED | HAS_PX4 | HAS_MAG] and not np.array_equal(before[1], P)
-        got = _one_call(b, inp, d_dt=d_dt)
+        got = rc.one_call(EACH, b, inp, dts=d_dt)
         after = b.get_tags(quiet)
         for u, v, name in zip(before, after, ("x", "P", "flags", "latch", "height")):
             assert u.tobytes() == v.tobytes(), (name, chunk)
@@ -339,7 +261,7 @@ def test_a_nan_dt_runs_the_event_as_the_single_call_does(storage, A):
     dt[e_imu, [3, 70]] = np.nan
     dt[e_toa, [9, 129]] = np.nan
     d_dt = torch.from_numpy(dt).to(inp.d_r.device)
-    ref = _check_one_call(inp, "NaN dt", d_dt=d_dt)
+    ref = rc.check_one_call(EACH, inp, "NaN dt", dts=d_dt)
     assert not (ref[1][e_imu, [3, 70]] == ST_SKIPPED).any() and not (ref[1][e_toa, [9, 129]] == ST_SKIPPED).any()
     assert (ref[1][e_imu, [3, 70]] & 32).all() and (ref[1][e_toa, [9, 129]] & 32).all()   # ... and KFPOS_ST_NONFINITE
 
@@ -354,12 +276,12 @@ def test_an_all_present_schedule_equals_run_planar_events_dev(storage, A):
         d_dt = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(inp.base[:, None], inp.dt.shape))).to(inp.d_r.device)
         for chunk in (None, 7):
             b = inp.bank(chunk)
-            ref = _one_call(b, inp, call="run_planar_events_dev", dts=inp.base)
+            ref = rc.one_call(SHARED, b, inp, dts=inp.base)
             b.close()
             b = inp.bank(chunk)
-            got = _one_call(b, inp, d_dt=d_dt)
+            got = rc.one_call(EACH, b, inp, dts=d_dt)
             b.close()
-            _same_bytes(got, ref, f"start={start} chunk={chunk}")
+            rc.same_bytes(got, ref, NAMES, f"start={start} chunk={chunk}")
         assert np.array_equal(ref[1] == ST_SKIPPED, inp.es.dropped)
 
 
@@ -377,7 +299,7 @@ def test_f64_storage_matches_the_oracle_after_every_slot(start, A, T=T):
     inp = Inputs(A, 0, start, True, waiting=not pe.STARTS[start][0], tags=np.arange(T))   # (the oracle: all 130)
     assert (inp.dt[inp.mask] > 0).all()           # dt = 0 stays out of this leg
     b = inp.bank()
-    got = _one_call(b, inp)
+    got = rc.one_call(EACH, b, inp)
     b.close()
     sch = inp.es.sch
     po, so = pee.replay(PlanarOracle(sch.w, pe.cfg_of(start), pe.init_of(sch, start)), inp.es)
@@ -444,7 +366,7 @@ def test_argument_errors_are_decided_before_anything_runs():
         return capi.PlanarInputs(**full)
 
     b = inp.bank()
-    _one_call(b, inp, n_slots=14)                              # a bank with something in it
+    rc.one_call(EACH, b, inp, n_slots=14)                              # a bank with something in it
     before = _snapshot(b)
     k, d = inp.kinds[:14].copy(), inp.d_dt
     assert set(k.tolist()) == {0, 1, 2, 3, 4}

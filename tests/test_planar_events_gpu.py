@@ -8,14 +8,14 @@ holds what it is meant to hold): a leading ranging event on a handle without lat
 samples of quality 0 on every 16th tag, the dropout rows of planar.epoch_ranges; it ends on a ranging event or on a
 sensor event, and prefixed with two sensor events it has tags waiting for their ML start. With KFPOS_TRACE_CHUNK_STEPS=7
 a launch boundary falls between two sensor events and another directly before a ranging event."""
-import contextlib
+import copy
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import planar_events as pe
+import replay_checks as rc
 from conftest import has_gpu
 
 pytestmark = pytest.mark.gpu
@@ -24,44 +24,30 @@ ERR_ARG, ERR_MODEL, ERR_STATE = 1, 4, 5
 HAS_PX4, HAS_IMU, HAS_MAG = 1 << 5, 1 << 6, 1 << 7      # planar flags word: what a tag has latched
 
 
-@contextlib.contextmanager
-def _env(**kv):
-    """environment variables the library reads in kfpos_create"""
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 class Inputs:
     """a schedule's inputs in HBM, component-major"""
 
     def __init__(self, T, A, storage, start, end_on_sensor=True, waiting=False, dev="cuda:0"):
-        import torch
         from roskfpos_amd import capi
         self.T, self.A, self.storage, self.start = T, A, storage, start
         real = np.float64 if storage == capi.STORE_F64 else np.float32
         sch = self.sch = pe.Schedule(T, A, end_on_sensor, waiting, real)
         self.kinds, self.dts = sch.kinds, sch.dts.copy()
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        up = lambda a: rc.up(a, dev)  # noqa: E731
         self.d_r, self.d_e = up(sch.ranges.transpose(0, 2, 1)), up(sch.err.T)
         self.d_s = {kind: up(sch.samples[kind].transpose(0, 2, 1)) for kind in pe.WIDTH}     # (n, C, T)
 
     def bank(self, chunk=None):
         from roskfpos_amd import capi
-        with _env(KFPOS_TRACE_CHUNK_STEPS=chunk):
+        with rc.env(KFPOS_TRACE_CHUNK_STEPS=chunk):
             return capi.KfposBank(capi.MODEL_PLANAR, self.T, self.sch.w.anchors, storage=self.storage,
                                   init_pos=pe.init_of(self.sch, self.start), planar=pe.cfg_of(self.start))
+
+    def under(self, kinds):
+        """the same inputs under other kinds, with the first dts of the schedule"""
+        other = copy.copy(self)
+        other.kinds = kinds
+        return other
 
 
 def _final(b):
@@ -69,90 +55,25 @@ def _final(b):
     return x, P, fl, b.get_latch(), b.get_height()
 
 
-def _events(kinds):
-    n = [0] * 5
-    for e, kind in enumerate(kinds):
-        yield e, int(kind), n[kind]
-        n[kind] += 1
+def _single(b, inp, e, kind, i, status, stream, dt):
+    if kind == pe.TOA:
+        b.step_toa_dev(inp.d_r[i], inp.d_e, dt, status=status, stream=stream)
+    else:
+        b.step_sensor_dev(kind, inp.d_s[kind][i], dt, status=status, stream=stream)
 
 
-def _single_calls(b, inp, kinds, dts):
-    """the events as single _dev calls -> (position after every event, status of every event, x, P, flags, latch,
-    height)"""
-    import torch
-    n, T = kinds.size, inp.T
-    st = torch.zeros(n, T, dtype=torch.int32, device=inp.d_r.device)
-    stream = torch.cuda.current_stream().cuda_stream
-    traj = np.zeros((n, 3, T))
-    for e, kind, i in _events(kinds):
-        if kind == pe.TOA:
-            b.step_toa_dev(inp.d_r[i], inp.d_e, dts[e], status=st[e], stream=stream)
-        else:
-            b.step_sensor_dev(kind, inp.d_s[kind][i], dts[e], status=st[e], stream=stream)
-        torch.cuda.synchronize()
-        traj[e, :2] = b.get_state()[0][:, :2].T
-        traj[e, 2] = b.get_height()
-    return (traj, st.cpu().numpy()) + _final(b)
-
-
-def _call(b, inp, kinds, dts, traj=None, ste=None, st=None):
-    import torch
-    T, A = inp.T, inp.A
-    s = inp.d_s
-    b.run_planar_events_dev(kinds, dts, range_mm=inp.d_r, stride_ranges=A * T, err_est=inp.d_e, stride_err=0,
+def _call(b, inp, n, dts, traj, ste, st, stream):
+    T, A, s = inp.T, inp.A, inp.d_s
+    b.run_planar_events_dev(inp.kinds[:n], dts, range_mm=inp.d_r, stride_ranges=A * T, err_est=inp.d_e, stride_err=0,
                             px4flow=s[pe.PX4], stride_px4flow=5 * T, imu=s[pe.IMU], stride_imu=24 * T,
                             mag=s[pe.MAG], stride_mag=3 * T, compass=s[pe.COMPASS], stride_compass=T,
-                            trajectory=traj, status_events=ste, status=st,
-                            stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-
-
-def _one_call(b, inp, kinds, dts, outputs=True):
-    import torch
-    n, T = kinds.size, inp.T
-    dev = inp.d_r.device
-    traj = torch.full((n, 3, T), 7.0, dtype=torch.float64, device=dev) if outputs else None
-    ste = torch.full((n, T), -1, dtype=torch.int32, device=dev) if outputs else None
-    st = torch.full((T,), -1, dtype=torch.int32, device=dev)
-    _call(b, inp, kinds, dts, traj, ste, st)
-    last = st.cpu().numpy()
-    if not outputs:
-        return (None, last) + _final(b)
-    assert np.array_equal(last, ste[-1].cpu().numpy()), "status is not the last event's"
-    return (traj.cpu().numpy(), ste.cpu().numpy()) + _final(b)
+                            trajectory=traj, status_events=ste, status=st, stream=stream)
 
 
 NAMES = ("position after every event", "status of every event", "x", "P", "flags", "latch", "height")
-
-
-def _same_bytes(got, ref, what, first=0):
-    for g, r, name in list(zip(got, ref, NAMES))[first:]:
-        assert g.shape == r.shape and g.dtype == r.dtype, (what, name)
-        assert g.tobytes() == r.tobytes(), (what, name)
-
-
-def _check_one_call(inp, kinds, dts, what, prepare=None, chunks=(None, 7)):
-    """single calls against one call per chunk size, and once with trajectory = status_events = NULL"""
-    def bank(chunk=None):
-        b = inp.bank(chunk)
-        if prepare:
-            prepare(b)
-        return b
-
-    b = bank()
-    ref = _single_calls(b, inp, kinds, dts)
-    b.close()
-    for chunk in chunks:
-        b = bank(chunk)
-        got = _one_call(b, inp, kinds, dts)
-        b.close()
-        _same_bytes(got, ref, f"{what} chunk={chunk}")
-    b = bank(7)
-    bare = _one_call(b, inp, kinds, dts, outputs=False)
-    b.close()
-    assert bare[1].tobytes() == ref[1][-1].tobytes(), (what, "last status")
-    _same_bytes(bare, ref, f"{what} without per-event outputs", first=2)
-    return ref
+FAM = rc.Family(names=NAMES, n_kinds=5, dts=lambda inp: inp.dts, final=_final,
+                position=lambda b: np.vstack([b.get_state()[0][:, :2].T, b.get_height()]),
+                single=_single, call=_call)
 
 
 # start x ends on a sensor event x sensor events ahead of the first ranging (the waiting case of an ML start)
@@ -163,7 +84,7 @@ def _bit_identity(T, A, storage, combos):
     for start, end_on_sensor, waiting in combos:
         inp = Inputs(T, A, storage, start, end_on_sensor, waiting)
         what = f"start={start} end_on_sensor={end_on_sensor} waiting={waiting}"
-        ref = _check_one_call(inp, inp.kinds, inp.dts, what)
+        ref = rc.check_one_call(FAM, inp, what)
         low = ref[1] & 0xFF
         assert (low == 0).mean() > 0.5, what                 # most status words are plain
         if T > 16:
@@ -210,21 +131,22 @@ def test_a_schedule_that_crosses_the_launch_boundary():
     from roskfpos_amd import capi
     reps = 4
     inp = Inputs(130, 8, capi.STORE_F64, "fixed")
-    kinds, dts = np.tile(inp.kinds, reps), np.tile(inp.dts, reps)
+    kinds, inp.dts = np.tile(inp.kinds, reps), np.tile(inp.dts, reps)
+    inp.kinds = kinds
     inp.d_r = inp.d_r.repeat(reps, 1, 1)
     inp.d_s = {kind: s.repeat(reps, 1, 1) for kind, s in inp.d_s.items()}
     lead = pe.launch_starts(kinds, 128)[0]
     assert kinds.size >= 130 and lead == 1 and len(pe.launch_starts(kinds, 128)) == 2
     assert set(kinds[lead + 64:lead + 128].tolist()) == {0, 1, 2, 3, 4}
     b = inp.bank()
-    ref = _single_calls(b, inp, kinds, dts)
+    ref = rc.single_calls(FAM, b, inp)
     b.close()
     low = ref[1] & 0xFF
     assert (low == 0).mean() > 0.5 and (low != 0).any() and np.isfinite(ref[0][-1]).all()
     b = inp.bank()
-    got = _one_call(b, inp, kinds, dts)
+    got = rc.one_call(FAM, b, inp)
     b.close()
-    _same_bytes(got, ref, "four times the schedule")
+    rc.same_bytes(got, ref, NAMES, "four times the schedule")
 
 
 @pytest.mark.parametrize("storage,A", [(0, 8), (2, 5), (3, 8)])
@@ -242,7 +164,7 @@ def test_a_handle_that_already_holds_latched_samples(storage, A):
             b.step_sensor_dev(kind, inp.d_s[kind][-1], 0.01, stream=stream)
         torch.cuda.synchronize()
 
-    ref = _check_one_call(inp, inp.kinds, inp.dts, "latched before the call", prepare)
+    ref = rc.check_one_call(FAM, inp, "latched before the call", prepare)
     assert (ref[4] & (HAS_PX4 | HAS_IMU | HAS_MAG) == (HAS_PX4 | HAS_IMU | HAS_MAG)).all()
     # ranging and IMU events only: the PX4Flow and magnetometer rows are what the earlier calls left
     only = np.array([0, 2, 0, 2, 2, 0, 2], dtype=np.uint8)
@@ -250,8 +172,8 @@ def test_a_handle_that_already_holds_latched_samples(storage, A):
     prepare(b)
     before = b.get_latch()
     b.close()
-    ref = _check_one_call(inp, only, inp.dts[:only.size], "latched before the call, IMU and ranging only", prepare,
-                          chunks=(None, 3))
+    ref = rc.check_one_call(FAM, inp.under(only), "latched before the call, IMU and ranging only", prepare,
+                            chunks=(None, 3, 7))
     assert ref[5][:, :5].tobytes() == before[:, :5].tobytes() and ref[5][:, 13:].tobytes() == before[:, 13:].tobytes()
     assert (ref[5][:, 5:7] != before[:, 5:7]).all()
 
@@ -272,8 +194,8 @@ def test_latch_rows_of_kinds_a_lane_never_sampled_keep_what_hbm_holds(storage, A
     for kinds, sampled in (([0, 2, 0, 2, 2, 0], [False, True, False]), ([1, 0, 2, 0, 3, 2], [True, True, True]),
                            ([0, 4, 1, 0], [True, False, True])):
         kinds = np.array(kinds, dtype=np.uint8)
-        ref = _check_one_call(inp, kinds, inp.dts[:kinds.size], f"sentinel kinds={kinds.tolist()}", prepare,
-                              chunks=(None, 2))
+        ref = rc.check_one_call(FAM, inp.under(kinds), f"sentinel kinds={kinds.tolist()}", prepare,
+                                chunks=(None, 2, 7))
         latch, flags = ref[5], ref[4]
         n_px4 = int((kinds == pe.PX4).sum())
         got_px4 = (inp.sch.samples[pe.PX4][:n_px4, :, 4] != 0).any(axis=0) if n_px4 else np.zeros(inp.T, dtype=bool)
@@ -297,7 +219,7 @@ def test_an_event_with_dt_zero(storage, A):
     assert inp.kinds[at] == pe.IMU and inp.kinds[at - 1] == pe.IMU
     dts = inp.dts.copy()
     dts[at] = 0.0
-    _check_one_call(inp, inp.kinds, dts, "dt = 0")
+    rc.check_one_call(FAM, inp, "dt = 0", dts=dts)
 
 
 @pytest.mark.parametrize("A", [8, 5])
@@ -310,7 +232,7 @@ def test_f64_storage_matches_the_oracle_after_every_event(start, A, T=130):
     from planar import PlanarOracle
     inp = Inputs(T, A, 0, start, True, waiting=start != "fixed")
     b = inp.bank()
-    got = _one_call(b, inp, inp.kinds, inp.dts)
+    got = rc.one_call(FAM, b, inp)
     b.close()
     po, so = pe.replay(PlanarOracle(inp.sch.w, pe.cfg_of(start), pe.init_of(inp.sch, start)), inp.sch)
     worst = [0.0, 0.0]
@@ -369,7 +291,7 @@ def test_argument_errors_are_decided_before_anything_runs():
         return capi.PlanarInputs(**full)
 
     b = inp.bank()
-    _one_call(b, inp, inp.kinds[:14], inp.dts[:14])            # a bank with something in it
+    rc.one_call(FAM, b, inp, n_slots=14)            # a bank with something in it
     before = _snapshot(b)
     k, d = inp.kinds[:14].copy(), inp.dts[:14].copy()
     assert set(k.tolist()) == {0, 1, 2, 3, 4}

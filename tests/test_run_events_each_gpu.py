@@ -5,13 +5,12 @@ after every slot.
 
 One schedule serves every test: the kinds pattern RUNS + TAIL below (39 slots) and an explicit participation mask over
 130 tags whose properties the first test asserts."""
-import contextlib
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
+import replay_checks as rc
 from cases import Case, rms_and_max
 from conftest import has_gpu
 from roskfpos_amd.synth import Workload
@@ -29,25 +28,6 @@ ABSENT_MM = 1999999999                        # what the ranges of an absent (ta
 ST_SKIPPED, ST_ML_INIT = 64, 8
 FL_STARTED, FL_HAS_IMU = 1, 2
 ERR_ARG, ERR_MODEL, ERR_STATE = 1, 4, 5
-
-
-@contextlib.contextmanager
-def _env(**kv):
-    """environment variables the library reads in kfpos_create"""
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _kinds():
@@ -102,7 +82,6 @@ class Inputs:
 
     def __init__(self, A, storage, fixed, cov_full, tags=None, fill=True, dev="cuda:0"):
         """fill: the input entries of absent (tag, slot) pairs hold NaN (accel) / ABSENT_MM (ranges)"""
-        import torch
         from roskfpos_amd import capi
         tags = np.arange(T) if tags is None else np.asarray(tags)
         n = self.T = tags.size
@@ -130,7 +109,7 @@ class Inputs:
         self.err = w.err_est(real)[tags]
         self.cov = case.accel_cov(w).astype(real)[tags]
         self.cov_other = Case("other", 1, A, T=T, cov_full=not cov_full).accel_cov(w).astype(real)[tags]
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        up = lambda a: rc.up(a, dev)  # noqa: E731
         self.d_r, self.d_e = up(self.ranges.transpose(0, 2, 1)), up(self.err.T)
         self.d_a, self.d_c, self.d_c_other = up(self.accel.transpose(0, 2, 1)), up(self.cov.T), up(self.cov_other.T)
         self.d_a_full, self.d_dt = up(self.accel_full.T), up(self.dt)
@@ -138,7 +117,7 @@ class Inputs:
 
     def bank(self, chunk=None):
         from roskfpos_amd import capi
-        with _env(KFPOS_TRACE_CHUNK_STEPS=chunk):
+        with rc.env(KFPOS_TRACE_CHUNK_STEPS=chunk):
             return capi.KfposBank(capi.MODEL_TOA_IMU, self.T, self.anchors, storage=self.storage,
                                   init_pos=self.init if self.fixed else None)
 
@@ -148,62 +127,33 @@ def _final(b):
     return x, P, fl, b.get_latch()
 
 
-def _single_calls(b, inp, d_dt=None, n_slots=None):
-    """the (first n_slots) slots as single _dev calls with the slot's dt array -> (position after every slot, status of
-    every slot, x, P, flags, latch)"""
-    import torch
-    d_dt = inp.d_dt if d_dt is None else d_dt
-    n, nt = n_slots or inp.kinds.size, inp.T
-    st = torch.full((n, nt), -1, dtype=torch.int32, device=inp.d_r.device)
-    stream = torch.cuda.current_stream().cuda_stream
-    traj = np.zeros((n, 3, nt))
-    j = i = 0
-    for e in range(n):
-        if inp.kinds[e] == TOA:
-            b.step_toa_dev(inp.d_r[j], inp.d_e, 0.0, status=st[e], stream=stream, dt_dev=d_dt[e])
-            j += 1
-        else:
-            b.step_imu_dev(inp.d_a[i], inp.d_c, 0.0, status=st[e], stream=stream, dt_dev=d_dt[e])
-            i += 1
-        torch.cuda.synchronize()
-        traj[e] = b.get_state()[0][:, :3].T
-    return (traj, st.cpu().numpy()) + _final(b)
+def _single(b, inp, e, kind, i, status, stream, dt):
+    if kind == TOA:
+        b.step_toa_dev(inp.d_r[i], inp.d_e, 0.0, status=status, stream=stream, dt_dev=dt)
+    else:
+        b.step_imu_dev(inp.d_a[i], inp.d_c, 0.0, status=status, stream=stream, dt_dev=dt)
 
 
-def _one_call(b, inp, outputs=True, d_dt=None, n_slots=None):
-    import torch
-    n, nt, A = n_slots or inp.kinds.size, inp.T, inp.A
-    dev = inp.d_r.device
-    traj = torch.full((n, 3, nt), 7.0, dtype=torch.float64, device=dev) if outputs else None
-    ste = torch.full((n, nt), -1, dtype=torch.int32, device=dev) if outputs else None
-    st = torch.full((nt,), -1, dtype=torch.int32, device=dev)
-    dts = (inp.d_dt if d_dt is None else d_dt)[:n]
-    b.run_events_each_dev(inp.kinds[:n], dts, range_mm=inp.d_r, stride_ranges=A * nt, err_est=inp.d_e, stride_err=0, accel=inp.d_a, stride_accel=3 * nt, cov=inp.d_c,
-                          trajectory=traj, status_events=ste, status=st,
-                          stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    last = st.cpu().numpy()
-    if not outputs:
-        return (None, last) + _final(b)
-    assert np.array_equal(last, ste[-1].cpu().numpy()), "status is not the last slot's"
-    return (traj.cpu().numpy(), ste.cpu().numpy()) + _final(b)
+def _call(method):
+    def call(b, inp, n, dts, traj, ste, st, stream):
+        nt, A = inp.T, inp.A
+        getattr(b, method)(inp.kinds[:n], dts, range_mm=inp.d_r, stride_ranges=A * nt, err_est=inp.d_e, stride_err=0,
+                           accel=inp.d_a, stride_accel=3 * nt, cov=inp.d_c, trajectory=traj, status_events=ste,
+                           status=st, stream=stream)
+    return call
 
 
 NAMES = ("position after every slot", "status of every slot", "x", "P", "flags", "latch")
-
-
-def _same_bytes(got, ref, what, first=0):
-    for g, r, name in list(zip(got, ref, NAMES))[first:]:
-        assert g.shape == r.shape and g.dtype == r.dtype, (what, name)
-        assert g.tobytes() == r.tobytes(), (what, name)
+EACH = rc.Family(names=NAMES, n_kinds=2, dts=lambda inp: inp.d_dt, final=_final,
+                 position=lambda b: b.get_state()[0][:, :3].T, single=_single, call=_call("run_events_each_dev"))
+# the shared-timeline entry point over the same inputs; its dts: one scalar per slot
+SHARED = rc.Family(**{**vars(EACH), "call": _call("run_events_dev")})
 
 
 def _bit_identity(A, storage, combos, tags=None):
     for fixed, cov_full in combos:
         inp = Inputs(A, storage, fixed, cov_full, tags)
-        b = inp.bank()
-        ref = _single_calls(b, inp)
-        b.close()
+        ref = rc.check_one_call(EACH, inp, f"fixed={fixed} cov_full={cov_full}")
         words = ref[1]
         assert ((words == ST_SKIPPED) == ~inp.mask).all()        # the reference run itself skips where the mask says
         low = words[inp.mask] & 0xFF
@@ -211,17 +161,6 @@ def _bit_identity(A, storage, combos, tags=None):
             assert (low == 0).mean() > 0.5 and (low != 0).any()  # most events are plain, the dropout paths ran
             if not fixed:
                 assert (words[inp.mask] & ST_ML_INIT).any()      # ML initialisations happened
-        what = f"fixed={fixed} cov_full={cov_full}"
-        for chunk in (None, 7):
-            b = inp.bank(chunk)
-            got = _one_call(b, inp)
-            b.close()
-            _same_bytes(got, ref, f"{what} chunk={chunk}")
-        b = inp.bank(7)
-        bare = _one_call(b, inp, outputs=False)                  # trajectory = status_events = NULL
-        b.close()
-        assert bare[1].tobytes() == ref[1][-1].tobytes(), (what, "last status")
-        _same_bytes(bare, ref, f"{what} without per-slot outputs", first=2)
 
 
 EVERY = [(f, c) for f in (True, False) for c in (False, True)]
@@ -268,15 +207,15 @@ def test_a_schedule_that_crosses_the_launch_boundary():
     assert inp.kinds.size >= 130 and inp.kinds.size > 128
     assert set(inp.kinds[64:128].tolist()) == {IMU, TOA}
     b = inp.bank()
-    ref = _single_calls(b, inp)
+    ref = rc.single_calls(EACH, b, inp)
     b.close()
     assert ((ref[1] == ST_SKIPPED) == ~inp.mask).all()
     low = ref[1][inp.mask] & 0xFF
     assert (low == 0).mean() > 0.5 and (low != 0).any() and np.isfinite(ref[0][-1]).all()
     b = inp.bank()
-    got = _one_call(b, inp)
+    got = rc.one_call(EACH, b, inp)
     b.close()
-    _same_bytes(got, ref, "four times the schedule")
+    rc.same_bytes(got, ref, NAMES, "four times the schedule")
 
 
 @pytest.mark.parametrize("storage,A", [(0, 8), (1, 5), (2, 8), (3, 5), (2, 5)])
@@ -301,7 +240,7 @@ def test_slots_ahead_of_a_tags_first_sample_fuse_its_earlier_latch_with_its_own_
 
         def bank(chunk=None, cov=None):
             b = inp.bank(chunk)
-            _single_calls(b, inp, d_dt=d_pre)
+            rc.single_calls(EACH, b, inp, dts=d_pre)
             b.step_imu_dev(inp.d_a_full, inp.d_c_other if cov is None else cov, 0.0, dt_dev=early,
                            stream=torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
@@ -314,20 +253,20 @@ def test_slots_ahead_of_a_tags_first_sample_fuse_its_earlier_latch_with_its_own_
         assert (latched[tags % 4 == 0] == inp.cov.astype(np.float64)[0]).all()
         has = (b.get_state()[2] & FL_HAS_IMU) != 0
         assert has.tolist() == (~nothing).tolist() and (b.get_state()[2][nothing] & FL_STARTED).all()
-        ref = _single_calls(b, inp)
+        ref = rc.single_calls(EACH, b, inp)
         b.close()
         for chunk in (None, 3):
             b = bank(chunk)
-            got = _one_call(b, inp)
+            got = rc.one_call(EACH, b, inp)
             b.close()
-            _same_bytes(got, ref, f"cov_full={cov_full} chunk={chunk}")
+            rc.same_bytes(got, ref, NAMES, f"cov_full={cov_full} chunk={chunk}")
         # the comparison has teeth: tag 7 (odd) runs a TOA slot ahead of its own first sample; had that slot fused the
         # latched sample with the CALL's covariance, its covariance would have come out of that slot differently (the
         # acceleration block, which the tag's next own sample overwrites: hence the comparison right behind the slot)
         behind = []
         for cov in (None, inp.d_c):
             b = bank(cov=cov)
-            behind.append(_single_calls(b, inp, n_slots=LATE_FIRST + 1))
+            behind.append(rc.single_calls(EACH, b, inp, n_slots=LATE_FIRST + 1))
             b.close()
         assert LATE % 2 == 1 and behind[0][3].tobytes() != behind[1][3].tobytes()
         if storage != 1:   # (a difference of 1.4e-7 of the entry: below what 24 mantissa bits keep)
@@ -335,9 +274,9 @@ def test_slots_ahead_of_a_tags_first_sample_fuse_its_earlier_latch_with_its_own_
         # ... and the call that ends right behind that slot leaves exactly the bytes of the single calls
         for chunk in (None, 3):
             b = bank(chunk)
-            got = _one_call(b, inp, n_slots=LATE_FIRST + 1)
+            got = rc.one_call(EACH, b, inp, n_slots=LATE_FIRST + 1)
             b.close()
-            _same_bytes(got, behind[0], f"cov_full={cov_full} chunk={chunk}, {LATE_FIRST + 1} slots")
+            rc.same_bytes(got, behind[0], NAMES, f"cov_full={cov_full} chunk={chunk}, {LATE_FIRST + 1} slots")
 
 
 @pytest.mark.parametrize("storage,A", [(2, 8), (0, 5)])
@@ -356,13 +295,13 @@ def test_a_nan_dt_runs_the_event_as_the_single_call_does(storage, A):
     dt[e_toa, [9, 129]] = np.nan
     d_dt = torch.from_numpy(dt).to(inp.d_r.device)
     b = inp.bank()
-    ref = _single_calls(b, inp, d_dt=d_dt)
+    ref = rc.single_calls(EACH, b, inp, dts=d_dt)
     b.close()
     assert not (ref[1][e_imu, [3, 70]] == ST_SKIPPED).any() and not (ref[1][e_toa, [9, 129]] == ST_SKIPPED).any()
     assert (ref[1][e_imu, [3, 70]] & 32).all() and (ref[1][e_toa, [9, 129]] & 32).all()   # ... and KFPOS_ST_NONFINITE
     for chunk in (None, 7):
         b = inp.bank(chunk)
-        got = _one_call(b, inp, d_dt=d_dt)
+        got = rc.one_call(EACH, b, inp, dts=d_dt)
         b.close()
         for g, r, name in zip(got, ref, NAMES):
             assert g.shape == r.shape and g.dtype == r.dtype, name
@@ -386,7 +325,7 @@ def test_a_tag_that_runs_nothing_keeps_every_stored_byte(storage, A, fixed):
         b.set_tags([5], P=P5, latch=latch5)           # no flags: the tag stays as fresh as the handle made it
         before = b.get_tags([5])
         assert before[2][0] == 0 and not np.array_equal(before[1], P5)   # not started, nothing latched; P was rounded
-        _one_call(b, inp)
+        rc.one_call(EACH, b, inp)
         after = b.get_tags([5])
         for x, y, name in zip(before[:4], after[:4], ("x", "P", "flags", "latch")):
             assert x.tobytes() == y.tobytes(), (name, chunk)
@@ -406,23 +345,15 @@ def test_an_all_synchronous_schedule_equals_run_events_dev(storage, A):
         inp = Inputs(A, storage, fixed, cov_full, fill=False)   # every tag takes part: every input entry is read
         base = inp.base                                          # every tag at the slot's shared dt
         d_dt = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(base[:, None], inp.dt.shape))).to(inp.d_r.device)
-        n, dev = inp.kinds.size, inp.d_r.device
         out = []
         for chunk in (None, 7):
             b = inp.bank(chunk)
-            traj = torch.full((n, 3, T), 7.0, dtype=torch.float64, device=dev)
-            ste = torch.full((n, T), -1, dtype=torch.int32, device=dev)
-            st = torch.full((T,), -1, dtype=torch.int32, device=dev)
-            b.run_events_dev(inp.kinds, base, range_mm=inp.d_r, stride_ranges=A * T, err_est=inp.d_e, stride_err=0,
-                             accel=inp.d_a, stride_accel=3 * T, cov=inp.d_c, trajectory=traj, status_events=ste,
-                             status=st, stream=torch.cuda.current_stream().cuda_stream)
-            torch.cuda.synchronize()
-            ref = (traj.cpu().numpy(), ste.cpu().numpy()) + _final(b)
+            ref = rc.one_call(SHARED, b, inp, dts=base)
             b.close()
             b = inp.bank(chunk)
-            got = _one_call(b, inp, d_dt=d_dt)
+            got = rc.one_call(EACH, b, inp, dts=d_dt)
             b.close()
-            _same_bytes(got, ref, f"fixed={fixed} cov_full={cov_full} chunk={chunk}")
+            rc.same_bytes(got, ref, NAMES, f"fixed={fixed} cov_full={cov_full} chunk={chunk}")
             out.append(ref)
         assert not (out[0][1] == ST_SKIPPED).any()
 
@@ -439,7 +370,7 @@ def test_f64_storage_matches_the_oracle_after_every_event_a_tag_ran(cov_full, fi
     import oracle_py
     inp = Inputs(A, 0, fixed, cov_full, tags=np.arange(T))
     b = inp.bank()
-    got = _one_call(b, inp)
+    got = rc.one_call(EACH, b, inp)
     b.close()
     o = oracle_py.OracleBank(1, T, inp.anchors, init_pos=inp.init if fixed else None, n_threads=8)
     j = i = 0
@@ -501,7 +432,7 @@ def test_argument_errors_are_decided_before_anything_runs():
     A = 8
     inp = Inputs(A, capi.STORE_MIXED, True, False, fill=False)
     b = inp.bank()
-    _one_call(b, inp)                                        # a bank with something in it
+    rc.one_call(EACH, b, inp)                                        # a bank with something in it
     before = _snapshot(b)
     k, d = inp.kinds[:9].copy(), inp.d_dt
     only_imu, only_toa = np.zeros(3, dtype=np.uint8), np.ones(3, dtype=np.uint8)

@@ -6,13 +6,13 @@ One schedule serves every test: a leading ranging event on a handle with nothing
 between rangings, two rangings back to back, one event with dt = 0, the dropout rows of cases.Case.epoch; it ends on a
 ranging event, or -- three more samples appended -- on an IMU event. With KFPOS_TRACE_CHUNK_STEPS=7 a launch boundary
 falls inside a run of IMU samples and another directly before a ranging event (asserted below)."""
-import contextlib
+import copy
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
+import replay_checks as rc
 from cases import Case, rms_and_max
 from conftest import has_gpu
 from roskfpos_amd.synth import Workload
@@ -24,25 +24,6 @@ RUNS = (0, 1, 4, 0, 4, 4, 1, 0, 4, 1, 4, 1)   # IMU samples ahead of each rangin
 TAIL = 3                                      # IMU samples behind the last ranging event ("ends on an IMU event")
 DT_ZERO = 10                                  # the event with dt = 0 (an IMU sample inside a run of four)
 ERR_ARG, ERR_MODEL, ERR_STATE = 1, 4, 5
-
-
-@contextlib.contextmanager
-def _env(**kv):
-    """environment variables the library reads in kfpos_create"""
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _kinds(end_on_imu):
@@ -72,7 +53,6 @@ class Inputs:
     """the schedule's inputs in HBM (component-major), and on the host in the (T, ...) form the oracle takes"""
 
     def __init__(self, T, A, storage, fixed, cov_full, end_on_imu, dev="cuda:0"):
-        import torch
         from roskfpos_amd import capi
         self.T, self.A, self.storage, self.fixed = T, A, storage, fixed
         real = self.real = np.float64 if storage == capi.STORE_F64 else np.float32
@@ -88,15 +68,21 @@ class Inputs:
         self.err = w.err_est(real)
         self.cov = case.accel_cov(w).astype(real)
         self.cov_other = Case("other", 1, A, T=T, cov_full=not cov_full).accel_cov(w).astype(real)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        up = lambda a: rc.up(a, dev)  # noqa: E731
         self.d_r, self.d_e = up(self.ranges.transpose(0, 2, 1)), up(self.err.T)
         self.d_a, self.d_c, self.d_c_other = up(self.accel.transpose(0, 2, 1)), up(self.cov.T), up(self.cov_other.T)
 
     def bank(self, chunk=None):
         from roskfpos_amd import capi
-        with _env(KFPOS_TRACE_CHUNK_STEPS=chunk):
+        with rc.env(KFPOS_TRACE_CHUNK_STEPS=chunk):
             return capi.KfposBank(capi.MODEL_TOA_IMU, self.T, self.w.anchors, storage=self.storage,
                                   init_pos=self.w.init_positions() if self.fixed else None)
+
+    def under(self, kinds):
+        """the same inputs under other kinds, with the first dts of the schedule"""
+        other = copy.copy(self)
+        other.kinds = kinds
+        return other
 
 
 def _final(b):
@@ -104,74 +90,33 @@ def _final(b):
     return x, P, fl, b.get_latch()
 
 
-def _single_calls(b, inp, kinds, dts):
-    """the events as single _dev calls -> (position after every event, status of every event, x, P, flags, latch)"""
-    import torch
-    n, T = kinds.size, inp.T
-    st = torch.zeros(n, T, dtype=torch.int32, device=inp.d_r.device)
-    stream = torch.cuda.current_stream().cuda_stream
-    traj = np.zeros((n, 3, T))
-    j = i = 0
-    for e in range(n):
-        if kinds[e] == TOA:
-            b.step_toa_dev(inp.d_r[j], inp.d_e, dts[e], status=st[e], stream=stream)
-            j += 1
-        else:
-            b.step_imu_dev(inp.d_a[i], inp.d_c, dts[e], status=st[e], stream=stream)
-            i += 1
-        torch.cuda.synchronize()
-        traj[e] = b.get_state()[0][:, :3].T
-    return (traj, st.cpu().numpy()) + _final(b)
+def _single(b, inp, e, kind, i, status, stream, dt):
+    if kind == TOA:
+        b.step_toa_dev(inp.d_r[i], inp.d_e, dt, status=status, stream=stream)
+    else:
+        b.step_imu_dev(inp.d_a[i], inp.d_c, dt, status=status, stream=stream)
 
 
-def _one_call(b, inp, kinds, dts, outputs=True):
-    import torch
-    n, T, A = kinds.size, inp.T, inp.A
-    dev = inp.d_r.device
-    traj = torch.full((n, 3, T), 7.0, dtype=torch.float64, device=dev) if outputs else None
-    ste = torch.full((n, T), -1, dtype=torch.int32, device=dev) if outputs else None
-    st = torch.full((T,), -1, dtype=torch.int32, device=dev)
-    b.run_events_dev(kinds, dts, range_mm=inp.d_r, stride_ranges=A * T, err_est=inp.d_e, stride_err=0, accel=inp.d_a,
-                     stride_accel=3 * T, cov=inp.d_c, trajectory=traj, status_events=ste, status=st,
-                     stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    last = st.cpu().numpy()
-    if not outputs:
-        return (None, last) + _final(b)
-    assert np.array_equal(last, ste[-1].cpu().numpy()), "status is not the last event's"
-    return (traj.cpu().numpy(), ste.cpu().numpy()) + _final(b)
+def _call(b, inp, n, dts, traj, ste, st, stream):
+    T, A = inp.T, inp.A
+    b.run_events_dev(inp.kinds[:n], dts, range_mm=inp.d_r, stride_ranges=A * T, err_est=inp.d_e, stride_err=0,
+                     accel=inp.d_a, stride_accel=3 * T, cov=inp.d_c, trajectory=traj, status_events=ste, status=st,
+                     stream=stream)
 
 
 NAMES = ("position after every event", "status of every event", "x", "P", "flags", "latch")
-
-
-def _same_bytes(got, ref, what, first=0):
-    for g, r, name in list(zip(got, ref, NAMES))[first:]:
-        assert g.shape == r.shape and g.dtype == r.dtype, (what, name)
-        assert g.tobytes() == r.tobytes(), (what, name)
+FAM = rc.Family(names=NAMES, n_kinds=2, dts=lambda inp: inp.dts, final=_final,
+                position=lambda b: b.get_state()[0][:, :3].T, single=_single, call=_call)
 
 
 def _bit_identity(T, A, storage, combos):
     for fixed, cov_full, end_on_imu in combos:
         inp = Inputs(T, A, storage, fixed, cov_full, end_on_imu)
-        b = inp.bank()
-        ref = _single_calls(b, inp, inp.kinds, inp.dts)
-        b.close()
+        ref = rc.check_one_call(FAM, inp, f"fixed={fixed} cov_full={cov_full} end_on_imu={end_on_imu}")
         low = ref[1] & 0xFF
         assert (low == 0).mean() > 0.5 and (low != 0).any()      # most steps are plain, the dropout paths ran
         if not fixed:
             assert (ref[1] & 0x08).any()                         # ML initialisations happened
-        what = f"fixed={fixed} cov_full={cov_full} end_on_imu={end_on_imu}"
-        for chunk in (None, 7):
-            b = inp.bank(chunk)
-            got = _one_call(b, inp, inp.kinds, inp.dts)
-            b.close()
-            _same_bytes(got, ref, f"{what} chunk={chunk}")
-        b = inp.bank(7)
-        bare = _one_call(b, inp, inp.kinds, inp.dts, outputs=False)   # trajectory = status_events = NULL
-        b.close()
-        assert bare[1].tobytes() == ref[1][-1].tobytes(), (what, "last status")
-        _same_bytes(bare, ref, f"{what} without per-event outputs", first=2)
 
 
 EVERY = [(f, c, e) for f in (True, False) for c in (False, True) for e in (False, True)]
@@ -214,20 +159,21 @@ def test_a_schedule_that_crosses_the_launch_boundary():
     from roskfpos_amd import capi
     reps = 4
     inp = Inputs(130, 8, capi.STORE_MIXED, True, False, True)       # the register-resident kernel
-    kinds, dts = np.tile(inp.kinds, reps), np.tile(inp.dts, reps)
+    kinds, inp.dts = np.tile(inp.kinds, reps), np.tile(inp.dts, reps)
+    inp.kinds = kinds
     inp.d_r, inp.d_a = inp.d_r.repeat(reps, 1, 1), inp.d_a.repeat(reps, 1, 1)
     lead = int(np.flatnonzero(kinds == IMU)[0])
     assert kinds.size >= 130 and lead == 1 and kinds.size - lead > 128
     assert set(kinds[lead + 64:lead + 128].tolist()) == {IMU, TOA}
     b = inp.bank()
-    ref = _single_calls(b, inp, kinds, dts)
+    ref = rc.single_calls(FAM, b, inp)
     b.close()
     low = ref[1] & 0xFF
     assert (low == 0).mean() > 0.5 and (low != 0).any() and np.isfinite(ref[0][-1]).all()
     b = inp.bank()
-    got = _one_call(b, inp, kinds, dts)
+    got = rc.one_call(FAM, b, inp)
     b.close()
-    _same_bytes(got, ref, "four times the schedule")
+    rc.same_bytes(got, ref, NAMES, "four times the schedule")
 
 
 @pytest.mark.parametrize("storage,A", [(0, 8), (1, 5), (2, 8), (3, 5), (2, 5)])
@@ -237,33 +183,26 @@ def test_leading_ranging_events_fuse_the_previously_latched_sample_with_its_cova
     import torch
     kinds = np.array([TOA, TOA, IMU, TOA, IMU, IMU, TOA, TOA], dtype=np.uint8)
     for cov_full in (False, True):
-        inp = Inputs(130, A, storage, True, cov_full, False)
-        dts = inp.dts[:kinds.size].copy()
-        out = []
-        for one_call in (False, True):
-            for chunk in ((None, 3) if one_call else (None,)):
-                b = inp.bank(chunk)
-                # an earlier sample, latched with ANOTHER covariance than the call's
-                b.step_imu_dev(inp.d_a[-1], inp.d_c_other, 0.02, stream=torch.cuda.current_stream().cuda_stream)
-                torch.cuda.synchronize()
-                out.append((_one_call if one_call else _single_calls)(b, inp, kinds, dts))
-                b.close()
-        _same_bytes(out[1], out[0], f"cov_full={cov_full}")
-        _same_bytes(out[2], out[0], f"cov_full={cov_full} chunk=3")
+        inp = Inputs(130, A, storage, True, cov_full, False).under(kinds)
+
+        def prepare(b):   # an earlier sample, latched with ANOTHER covariance than the call's
+            b.step_imu_dev(inp.d_a[-1], inp.d_c_other, 0.02, stream=torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+
+        rc.check_one_call(FAM, inp, f"cov_full={cov_full}", prepare, chunks=(None, 3))
         # the comparison has teeth: had the two leading events fused the latched sample with the CALL's covariance
         # (here: the latch rewritten to carry it, then the single calls), the covariance would have come out differently
         def lead(swap):
             stream = torch.cuda.current_stream().cuda_stream
             b = inp.bank()
-            b.step_imu_dev(inp.d_a[-1], inp.d_c_other, 0.02, stream=stream)
-            torch.cuda.synchronize()
+            prepare(b)
             if swap:
                 b2 = inp.bank()
                 b2.step_imu_dev(inp.d_a[-1], inp.d_c, 0.02, stream=stream)
                 torch.cuda.synchronize()
                 b.set_latch(b2.get_latch())
                 b2.close()
-            res = _single_calls(b, inp, kinds[:2], dts[:2])
+            res = rc.single_calls(FAM, b, inp, n_slots=2)
             b.close()
             return res
 
@@ -281,7 +220,7 @@ def test_f64_storage_matches_the_oracle_after_every_event(cov_full, fixed, A, T=
     import oracle_py
     inp = Inputs(T, A, 0, fixed, cov_full, True)
     b = inp.bank()
-    got = _one_call(b, inp, inp.kinds, inp.dts)
+    got = rc.one_call(FAM, b, inp)
     b.close()
     o = oracle_py.OracleBank(1, T, inp.w.anchors, init_pos=inp.w.init_positions() if fixed else None, n_threads=8)
     j = i = 0
@@ -337,7 +276,7 @@ def test_argument_errors_are_decided_before_anything_runs():
     T, A = 130, 8
     inp = Inputs(T, A, capi.STORE_MIXED, True, False, False)
     b = inp.bank()
-    _one_call(b, inp, inp.kinds[:9], inp.dts[:9])            # a bank with something in it
+    rc.one_call(FAM, b, inp, n_slots=9)            # a bank with something in it
     before = _snapshot(b)
     k, d = inp.kinds[:9].copy(), inp.dts[:9].copy()
     only_imu, only_toa = np.zeros(3, dtype=np.uint8), np.ones(3, dtype=np.uint8)

@@ -4,15 +4,15 @@ covariance as stored, flags, the status word and the position of every slot -- a
 
 One schedule serves every test: SLOTS ranging slots from cases.Case.epoch (dropout rows inside) and an explicit
 participation mask over 130 tags whose properties the first test asserts. The single-call reference of a configuration
-is computed once and shared by the launch sizes compared against it."""
-import contextlib
+is computed once and shared by the launch sizes compared against it (tests/replay_checks.py)."""
 import ctypes
 import functools
-import os
+import types
 
 import numpy as np
 import pytest
 
+import replay_checks as rc
 from cases import Case, rms_and_max
 from conftest import has_gpu
 from roskfpos_amd.synth import Workload
@@ -30,25 +30,6 @@ FL_STARTED = 1
 ERR_ARG, ERR_MODEL, ERR_STATE = 1, 4, 5
 F64, F32, MIXED, P48 = 0, 1, 2, 3
 NO_COOP = {"KFPOS_NO_COOP": 1}
-
-
-@contextlib.contextmanager
-def _env(**kv):
-    """environment variables the library reads in kfpos_create"""
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _mask(slots=SLOTS):
@@ -88,7 +69,6 @@ class Inputs:
 
     def __init__(self, A, storage, fixed=True, ignore_worst=False, top_n=0, slots=SLOTS, env=None, tags=T, dev="cuda:0"):
         """tags: the bank holds the first `tags` columns of the 130-tag schedule"""
-        import torch
         n = self.T = tags
         self.A, self.storage, self.fixed = A, storage, fixed
         self.ignore_worst, self.top_n, self.env = ignore_worst, top_n, dict(env or {})
@@ -96,7 +76,7 @@ class Inputs:
         case = Case("each", 0, A, fixed=fixed, T=T, outlier=bool(ignore_worst or top_n))
         w = Workload(T, A)
         self.anchors, self.init = w.anchors, w.init_positions()[:n]
-        self.slots = slots
+        self.slots, self.kinds = slots, np.zeros(slots, dtype=np.uint8)   # ranging slots only
         self.mask = _mask(slots)[:, :n]
         base = np.round(np.random.default_rng(20261017).uniform(0.02, 0.12, slots), 4)
         base[DT_ZERO] = 0.0
@@ -104,57 +84,30 @@ class Inputs:
         self.ranges = np.stack([case.epoch(w, s) for s in range(slots)])[:, :n]    # (S, T, A), dropout rows kept
         self.ranges[~self.mask] = ABSENT_MM
         self.err = w.err_est(real)[:n]
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        up = lambda a: rc.up(a, dev)  # noqa: E731
         self.d_r, self.d_e, self.d_dt = up(self.ranges.transpose(0, 2, 1)), up(self.err.T), up(self.dt)
         assert n == self.d_dt.shape[1]
 
     def bank(self, chunk=None):
         from roskfpos_amd import capi
-        with _env(KFPOS_TRACE_CHUNK_STEPS=chunk, **self.env):
+        with rc.env(KFPOS_TRACE_CHUNK_STEPS=chunk, **self.env):
             return capi.KfposBank(capi.MODEL_TOA, self.T, self.anchors, storage=self.storage,
                                   ignore_worst=self.ignore_worst, top_n=self.top_n,
                                   init_pos=self.init if self.fixed else None)
 
 
-def _single_calls(b, d_r, d_e, d_dt):
-    """the slots as single kfpos_step_toa_dev calls with the slot's dt row -> (position after every slot, status of
-    every slot, x, P, flags)"""
-    import torch
-    n, nt = d_dt.shape
-    st = torch.full((n, nt), -1, dtype=torch.int32, device=d_r.device)
-    stream = torch.cuda.current_stream().cuda_stream
-    traj = np.zeros((n, 3, nt))
-    for e in range(n):
-        b.step_toa_dev(d_r[e], d_e, 0.0, status=st[e], stream=stream, dt_dev=d_dt[e])
-        torch.cuda.synchronize()
-        traj[e] = b.get_state()[0][:, :3].T
-    return (traj, st.cpu().numpy()) + b.get_state()
+def _single(b, inp, e, kind, i, status, stream, dt):
+    b.step_toa_dev(inp.d_r[e], inp.d_e, 0.0, status=status, stream=stream, dt_dev=dt)
 
 
-def _one_call(b, d_r, d_e, d_dt, outputs=True):
-    import torch
-    n, nt = d_dt.shape
-    A, dev = d_r.shape[1], d_r.device
-    traj = torch.full((n, 3, nt), 7.0, dtype=torch.float64, device=dev) if outputs else None
-    sts = torch.full((n, nt), -1, dtype=torch.int32, device=dev) if outputs else None
-    st = torch.full((nt,), -1, dtype=torch.int32, device=dev)
-    b.run_trace_each_dev(d_dt, d_r, A * nt, d_e, 0, trajectory=traj, status_steps=sts, status=st,
-                         stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    last = st.cpu().numpy()
-    if not outputs:
-        return (None, last) + b.get_state()
-    assert np.array_equal(last, sts[-1].cpu().numpy()), "status is not the last slot's"
-    return (traj.cpu().numpy(), sts.cpu().numpy()) + b.get_state()
+def _call(b, inp, n, dts, traj, sts, st, stream):
+    b.run_trace_each_dev(dts, inp.d_r, inp.A * inp.T, inp.d_e, 0, trajectory=traj, status_steps=sts, status=st,
+                         stream=stream)
 
 
 NAMES = ("position after every slot", "status of every slot", "x", "P", "flags")
-
-
-def _same_bytes(got, ref, what, first=0):
-    for g, r, name in list(zip(got, ref, NAMES))[first:]:
-        assert g.shape == r.shape and g.dtype == r.dtype, (what, name)
-        assert g.tobytes() == r.tobytes(), (what, name)
+FAM = rc.Family(names=NAMES, n_kinds=1, dts=lambda inp: inp.d_dt, final=lambda b: b.get_state(),
+                position=lambda b: b.get_state()[0][:, :3].T, single=_single, call=_call)
 
 
 CONFIGS = {
@@ -188,57 +141,43 @@ CONFIGS = {
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(name, slots=SLOTS):
-    """the inputs of a configuration and what the single calls leave of them; read-only from here on"""
-    inp = Inputs(slots=slots, **CONFIGS[name])
-    b = inp.bank()
-    ref = _single_calls(b, inp.d_r, inp.d_e, inp.d_dt)
-    b.close()
-    for a in ref:
-        a.setflags(write=False)
-    return inp, ref
+def _inputs(name, slots=SLOTS):
+    """the inputs of a configuration; read-only"""
+    return Inputs(slots=slots, **CONFIGS[name])
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))
 def test_one_call_equals_the_single_calls_bit_for_bit(name):
     if not has_gpu():
         pytest.skip("no GPU")
-    inp, ref = _reference(name)
+    inp = _inputs(name)
+    ref = rc.check_one_call(FAM, inp, name, chunks=(1, None, 7))
     words = ref[1]
     assert ((words == ST_SKIPPED) == ~inp.mask).all()            # the reference run itself skips where the mask says
     low = words[inp.mask] & 0xFF
     assert (low == 0).any() and (low != 0).any()                 # plain slots, and the dropout paths ran
     if not inp.fixed:
         assert (low & ST_ML_INIT).any()                          # ML initialisations happened
-    for chunk in (7, 1, None):
-        b = inp.bank(chunk)
-        got = _one_call(b, inp.d_r, inp.d_e, inp.d_dt)
-        b.close()
-        _same_bytes(got, ref, f"{name} chunk={chunk}")
-    b = inp.bank(7)
-    bare = _one_call(b, inp.d_r, inp.d_e, inp.d_dt, outputs=False)   # trajectory = status_steps = NULL
-    b.close()
-    assert bare[1].tobytes() == ref[1][-1].tobytes(), (name, "last status")
-    _same_bytes(bare, ref, f"{name} without per-slot outputs", first=2)
 
 
 def test_a_schedule_that_crosses_the_launch_boundary():
     """130 slots at the default launch size: 128 in the first launch, 2 in the second"""
     if not has_gpu():
         pytest.skip("no GPU")
-    inp, ref = _reference("A8 fixed mixed", 130)
+    inp = _inputs("A8 fixed mixed", 130)
     assert inp.d_dt.shape[0] == 130
-    b = inp.bank()
-    got = _one_call(b, inp.d_r, inp.d_e, inp.d_dt)
-    b.close()
-    _same_bytes(got, ref, "130 slots")
+    out = []
+    for run in (rc.single_calls, rc.one_call):
+        b = inp.bank()
+        out.append(run(FAM, b, inp))
+        b.close()
+    rc.same_bytes(out[1], out[0], NAMES, "130 slots")
 
 
 def test_a_bank_with_more_wavefronts_than_simds():
     """65 600 tags: the single calls run the two-wavefront build, the one call k_trace_toa6_each"""
     if not has_gpu():
         pytest.skip("no GPU")
-    import torch
     from roskfpos_amd import capi
     n, A, S = 65600, 8, 3
     w = Workload(n, A)
@@ -248,15 +187,15 @@ def test_a_bank_with_more_wavefronts_than_simds():
     dt = np.where(mask, np.array([0.1, 0.05, 0.07])[:, None], -1.0)
     ranges = np.stack([w.ranges_mm(s) for s in range(S)])
     ranges[~mask] = ABSENT_MM
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")  # noqa: E731
-    d_r, d_e, d_dt = up(ranges.transpose(0, 2, 1)), up(w.err_est(np.float32).T), up(dt)
+    inp = types.SimpleNamespace(T=n, A=A, kinds=np.zeros(S, dtype=np.uint8), d_r=rc.up(ranges.transpose(0, 2, 1)),
+                                d_e=rc.up(w.err_est(np.float32).T), d_dt=rc.up(dt))
     out = []
-    for call in (_single_calls, _one_call):
+    for run in (rc.single_calls, rc.one_call):
         b = capi.KfposBank(capi.MODEL_TOA, n, w.anchors, storage=MIXED, init_pos=w.init_positions())
-        out.append(call(b, d_r, d_e, d_dt))
+        out.append(run(FAM, b, inp))
         b.close()
     assert ((out[0][1] == ST_SKIPPED) == ~mask).all()
-    _same_bytes(out[1], out[0], "65 600 tags")
+    rc.same_bytes(out[1], out[0], NAMES, "65 600 tags")
 
 
 @pytest.mark.parametrize("name", ["A8 fixed p48", "A8 fixed f32", "A8 ml p48", "A5 ml mixed", "A8 fixed mixed coop"])
@@ -265,13 +204,13 @@ def test_a_tag_that_runs_nothing_keeps_every_stored_byte(name):
     if not has_gpu():
         pytest.skip("no GPU")
     import torch
-    inp, _ = _reference(name)
+    inp = _inputs(name)
     assert not inp.mask[:, 5].any()
     for chunk in (None, 7):
         b = inp.bank(chunk)
         before = b.get_tags([5])
         assert before[2][0] == 0                                 # fresh: not started
-        _one_call(b, inp.d_r, inp.d_e, inp.d_dt)
+        rc.one_call(FAM, b, inp)
         after = b.get_tags([5])
         for x, y, what in zip(before[:3], after[:3], ("x", "P", "flags")):
             assert x.tobytes() == y.tobytes(), (what, chunk)
@@ -286,7 +225,7 @@ def test_a_tag_that_runs_nothing_keeps_every_stored_byte(name):
         torch.cuda.synchronize()
         before = b.get_tags([5])
         assert before[2][0] & FL_STARTED and np.isfinite(before[0]).all() and before[1].any()
-        _one_call(b, inp.d_r, inp.d_e, inp.d_dt)
+        rc.one_call(FAM, b, inp)
         after = b.get_tags([5])
         for x, y, what in zip(before[:3], after[:3], ("x", "P", "flags")):
             assert x.tobytes() == y.tobytes(), (what, chunk, "stepped before")
@@ -317,7 +256,7 @@ def test_f64_storage_matches_the_oracle_after_every_slot_a_tag_ran(name):
     inp = Inputs(**ORACLE[name])
     T = inp.T
     b = inp.bank()
-    got = _one_call(b, inp.d_r, inp.d_e, inp.d_dt)
+    got = rc.one_call(FAM, b, inp)
     b.close()
     o = oracle_py.OracleBank(0, T, inp.anchors, ignore_worst=inp.ignore_worst, top_n=inp.top_n,
                              init_pos=inp.init if inp.fixed else None, n_threads=8)
@@ -362,7 +301,7 @@ def test_argument_errors_are_decided_before_anything_runs():
     A = 8
     inp = Inputs(A, MIXED, env=NO_COOP)
     b = inp.bank()
-    _one_call(b, inp.d_r, inp.d_e, inp.d_dt)                 # a bank with something in it
+    rc.one_call(FAM, b, inp)                 # a bank with something in it
     before = _snapshot(b)
     d, r, e = inp.d_dt, inp.d_r, inp.d_e
     refused = {"n_steps < 0": (-1, d, r, e), "dt_steps_dev missing": (9, None, r, e),

@@ -20,9 +20,7 @@ of the time per ranging period, in microseconds. Required: on the contiguous lay
     python tools/events_each_latency.py --out profiles/events_each_replay_latency.json [--rounds 7] [--commit HASH]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -31,16 +29,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from roskfpos_amd import capi, synth  # noqa: E402
 from roskfpos_amd.synth import Workload  # noqa: E402
+from replay_timing import alternate, commit_of, entry, finish  # noqa: E402
 
 T, A, K, G = 1 << 16, 8, 4, 4
 WARM, TIMED = 5, 20
 ABSENT_MM = -1
-
-
-def stats(us):
-    a = np.asarray(us)
-    return dict(n=int(a.size), median_us=float(np.median(a)), p10_us=float(np.percentile(a, 10)),
-                p90_us=float(np.percentile(a, 90)), min_us=float(a.min()), max_us=float(a.max()))
 
 
 class Replay:
@@ -130,36 +123,16 @@ class Replay:
         run(WARM * n, (WARM + TIMED) * n)
         return self.bank.timing_end(self.stream) * 1e3 / TIMED      # microseconds per ranging period
 
-    def compare(self, name, routes, sched, rounds):
+    def measure(self, name, routes, sched, rounds):
         first, second = routes
         self.once(first, sched)
         ref = self.bank.get_state() + (self.bank.get_latch(),)
         self.once(second, sched)
         got = self.bank.get_state() + (self.bank.get_latch(),)
         same = all(np.array_equal(g, r, equal_nan=True) for g, r in zip(got, ref))
-        us = {first: [], second: []}
-        for _ in range(rounds):
-            for route in routes:
-                us[route].append(self.once(route, sched))
-        entry = dict(layout=name, slots_per_period=int(sched[0].size // self.periods), participation=sched[4],
-                     same_state=bool(same))
-        entry[first], entry[second] = stats(us[first]), stats(us[second])
-        entry["second_wholly_below_first"] = bool(entry[second]["p90_us"] < entry[first]["p10_us"])
-        entry["ranges_overlap"] = not (entry[second]["p90_us"] < entry[first]["p10_us"] or
-                                       entry[first]["p90_us"] < entry[second]["p10_us"])
-        f, s = entry[first], entry[second]
-        print(f"{name}: {first} {f['median_us']:8.1f} us [{f['p10_us']:.1f} .. {f['p90_us']:.1f}]   "
-              f"{second} {s['median_us']:8.1f} us [{s['p10_us']:.1f} .. {s['p90_us']:.1f}]   per ranging period; "
-              f"same state: {same}", flush=True)
-        return entry
-
-
-def commit_of():
-    try:
-        return subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True,
-                              check=True).stdout.strip()
-    except Exception:
-        return None
+        us = alternate(routes, lambda route: self.once(route, sched), rounds)
+        return entry(name, first, second, us, layout=name, slots_per_period=int(sched[0].size // self.periods),
+                     participation=sched[4], same_state=bool(same))
 
 
 def main():
@@ -174,28 +147,23 @@ def main():
     layouts = []
     for name, grp in (("contiguous", (t // 64) % G), ("interleaved", t % G)):
         sched = rp.schedule(grp, G)
-        layouts.append(rp.compare(name, ("A", "B"), sched, a.rounds))
+        layouts.append(rp.measure(name, ("A", "B"), sched, a.rounds))
         del sched
     sched = rp.schedule(np.zeros(a.tags, dtype=np.int64), 1)
     assert bool((sched[1] >= 0).all())
     sched = sched + (sched[1][:, 0].cpu().numpy(),)       # the slots' shared dts, for kfpos_run_events_dev
-    sync = rp.compare("synchronous", ("C", "D"), sched, a.rounds)
+    sync = rp.measure("synchronous", ("C", "D"), sched, a.rounds)
     met = layouts[0]["second_wholly_below_first"] and layouts[0]["same_state"]
     res = dict(what="9-state event replay with a timeline per tag: single _dev calls with dt_dev on one stream (A) against "
                     "kfpos_run_events_each_dev (B), and kfpos_run_events_dev (C) against kfpos_run_events_each_dev (D) "
                     f"on a synchronous schedule; microseconds per ranging period of K = {K} IMU samples + 1 ranging "
                     f"epoch per tag, tags in G = {G} phase groups (kfpos_timing_begin / _end over {TIMED} periods "
                     f"after {WARM} of warm-up)",
-               command="python tools/events_each_latency.py " + " ".join(sys.argv[1:]), commit=a.commit or commit_of(),
+               command="python tools/events_each_latency.py " + " ".join(sys.argv[1:]), commit=a.commit or commit_of(ROOT),
                tags=a.tags, anchors=A, storage="MIXED", K=K, G=G, rounds=a.rounds, layouts=layouts, synchronous=sync,
                requirement="contiguous layout: B's 10th .. 90th percentile range lies wholly below A's",
                requirement_met=bool(met))
-    text = json.dumps(res, indent=1)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
-    return 0 if met else 1
+    return finish(res, a.out, met)
 
 
 if __name__ == "__main__":

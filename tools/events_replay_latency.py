@@ -14,9 +14,7 @@ the time per ranging period, in microseconds; per route the cost of one IMU even
     python tools/events_replay_latency.py --kernels-only      # one repetition of each, for a kernel trace
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -25,16 +23,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from roskfpos_amd import capi  # noqa: E402
 from roskfpos_amd.synth import Workload  # noqa: E402
+from replay_timing import alternate, commit_of, entry, finish  # noqa: E402
 
 T, A = 1 << 16, 8
 KS = (0, 1, 4, 9)
 WARM, TIMED = 5, 20
-
-
-def stats(us):
-    a = np.asarray(us)
-    return dict(n=int(a.size), median_us=float(np.median(a)), p10_us=float(np.percentile(a, 10)),
-                p90_us=float(np.percentile(a, 90)), min_us=float(a.min()), max_us=float(a.max()))
 
 
 class Replay:
@@ -94,14 +87,6 @@ class Replay:
         return self.bank.timing_end(self.stream) * 1e3 / TIMED      # microseconds per ranging period
 
 
-def commit_of():
-    try:
-        return subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True,
-                              check=True).stdout.strip()
-    except Exception:
-        return None
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -126,30 +111,19 @@ def main():
         rp.once("B", K, sched)
         got = rp.bank.get_state()
         same = all(np.array_equal(g, r, equal_nan=True) for g, r in zip(got, ref))
-        us = {"A": [], "B": []}
-        for _ in range(a.rounds):
-            for route in ("A", "B"):
-                us[route].append(rp.once(route, K, sched))
-        entry = dict(K=K, events_per_period=K + 1, same_state=bool(same), A=stats(us["A"]), B=stats(us["B"]))
-        entry["ranges_overlap"] = not (entry["B"]["p90_us"] < entry["A"]["p10_us"] or
-                                       entry["A"]["p90_us"] < entry["B"]["p10_us"])
-        per_k.append(entry)
-        print(f"K={K}: A {entry['A']['median_us']:8.1f} us [{entry['A']['p10_us']:.1f} .. {entry['A']['p90_us']:.1f}]   "
-              f"B {entry['B']['median_us']:8.1f} us [{entry['B']['p10_us']:.1f} .. {entry['B']['p90_us']:.1f}]   "
-              f"per ranging period; same state: {same}", flush=True)
+        us = alternate(("A", "B"), lambda route: rp.once(route, K, sched), a.rounds)
+        e = entry(f"K={K}", "A", "B", us, K=K, events_per_period=K + 1, same_state=bool(same))
+        del e["second_wholly_below_first"]           # not in this tool's record
+        per_k.append(e)
     base = {r: per_k[0][r]["median_us"] for r in ("A", "B")}
     imu_event = {r: {str(e["K"]): (e[r]["median_us"] - base[r]) / e["K"] for e in per_k if e["K"]} for r in ("A", "B")}
     res = dict(what="9-state event replay: single _dev calls on one stream (A) against kfpos_run_events_dev (B), "
                     "microseconds per ranging period of K IMU events + 1 ranging event (kfpos_timing_begin / _end over "
                     f"{TIMED} periods after {WARM} of warm-up)",
-               command="python tools/events_replay_latency.py " + " ".join(sys.argv[1:]), commit=a.commit or commit_of(),
-               tags=a.tags, anchors=A, storage="MIXED", rounds=a.rounds, per_K=per_k, us_per_imu_event=imu_event)
-    text = json.dumps(res, indent=1)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
+               command="python tools/events_replay_latency.py " + " ".join(sys.argv[1:]),
+               commit=a.commit or commit_of(ROOT), tags=a.tags, anchors=A, storage="MIXED", rounds=a.rounds, per_K=per_k, us_per_imu_event=imu_event)
+    return finish(res, a.out)
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

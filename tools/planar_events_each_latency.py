@@ -22,9 +22,7 @@ come out. Absent (tag, slot) pairs hold dt -1, NaN samples and -1 mm ranges.
     python tools/planar_events_each_latency.py --out profiles/planar_events_each_latency.json [--rounds 7] [--commit HASH]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -33,6 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from roskfpos_amd import capi, synth  # noqa: E402
 from roskfpos_amd.synth import Workload  # noqa: E402
+from replay_timing import alternate, commit_of, entry, finish  # noqa: E402
 
 T, A, G = 1 << 16, 8, 4
 TOA, PX4, IMU, MAG = capi.PLANAR_EVENT_TOA, capi.SENSOR_PX4FLOW, capi.SENSOR_IMU, capi.SENSOR_MAG
@@ -43,12 +42,6 @@ ABSENT_MM = -1
 CFG = dict(use_fixed_height=1, fixed_height=1.0, init_angle=0.3, px4_height=Workload.PX4_HEIGHT, px4_arm_p1=0.05,
            px4_arm_p2=-0.02, px4_cov_velocity=0.002, px4_cov_gyro_z=0.001, imu_use_fixed_cov_acc=0, imu_cov_acc=0.02,
            imu_use_fixed_cov_ang_vel_z=1, imu_cov_ang_vel_z=0.0005, mag_angle_offset=0.1, mag_cov=0.01)
-
-
-def stats(us):
-    a = np.asarray(us)
-    return dict(n=int(a.size), median_us=float(np.median(a)), p10_us=float(np.percentile(a, 10)),
-                p90_us=float(np.percentile(a, 90)), min_us=float(a.min()), max_us=float(a.max()))
 
 
 class Replay:
@@ -149,7 +142,7 @@ class Replay:
         run(WARM * n, (WARM + TIMED) * n)
         return self.bank.timing_end(self.stream) * 1e3 / TIMED      # microseconds per ranging period
 
-    def compare(self, name, routes, sched, rounds):
+    def measure(self, name, routes, sched, rounds):
         first, second = routes
         self.once(first, sched)
         ref = self.final()
@@ -158,30 +151,11 @@ class Replay:
         same = all(g.tobytes() == r.tobytes() for g, r in zip(got, ref))
         assert same, f"{name}: routes {first} and {second} leave different bytes behind"
         assert np.isfinite(ref[0]).all()
-        us = {first: [], second: []}
-        for _ in range(rounds):
-            for route in routes:
-                us[route].append(self.once(route, sched))
-        entry = dict(layout=name, slots_per_period=int(sched["kinds"].size // self.periods),
-                     participation=sched["share"], same_state=bool(same))
-        entry[first], entry[second] = stats(us[first]), stats(us[second])
-        entry["second_wholly_below_first"] = bool(entry[second]["p90_us"] < entry[first]["p10_us"])
-        entry["ranges_overlap"] = not (entry[second]["p90_us"] < entry[first]["p10_us"] or
-                                       entry[first]["p90_us"] < entry[second]["p10_us"])
-        entry["first_over_second"] = entry[first]["median_us"] / entry[second]["median_us"]
-        f, s = entry[first], entry[second]
-        print(f"{name}: {first} {f['median_us']:8.1f} us [{f['p10_us']:.1f} .. {f['p90_us']:.1f}]   "
-              f"{second} {s['median_us']:8.1f} us [{s['p10_us']:.1f} .. {s['p90_us']:.1f}]   per ranging period, "
-              f"{first} / {second} = {entry['first_over_second']:.2f}; same state: {same}", flush=True)
-        return entry
-
-
-def commit_of():
-    try:
-        return subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True,
-                              check=True).stdout.strip()
-    except Exception:
-        return None
+        us = alternate(routes, lambda route: self.once(route, sched), rounds)
+        e = entry(name, first, second, us, layout=name, slots_per_period=int(sched["kinds"].size // self.periods),
+                  participation=sched["share"], same_state=bool(same))
+        e["first_over_second"] = e[first]["median_us"] / e[second]["median_us"]
+        return e
 
 
 def main():
@@ -196,11 +170,11 @@ def main():
     layouts = []
     for name, grp in (("contiguous", (t // 64) % G), ("interleaved", t % G)):
         sched = rp.schedule(grp, G)
-        layouts.append(rp.compare(name, ("A", "B"), sched, a.rounds))
+        layouts.append(rp.measure(name, ("A", "B"), sched, a.rounds))
         del sched
     sched = rp.schedule(np.zeros(a.tags, dtype=np.int64), 1)
     assert bool((sched["d_dt"] >= 0).all())
-    sync = rp.compare("synchronous", ("C", "D"), sched, a.rounds)
+    sync = rp.measure("synchronous", ("C", "D"), sched, a.rounds)
     met = layouts[0]["second_wholly_below_first"] and layouts[0]["same_state"]
     res = dict(what="planar event replay with a timeline per tag: single _dev calls with dt_dev on one stream (A) against "
                     "kfpos_run_planar_events_each_dev (B), and kfpos_run_planar_events_dev (C) against "
@@ -208,16 +182,11 @@ def main():
                     "10 IMU + 2 PX4Flow + 1 magnetometer sample + 1 ranging epoch per tag, tags in "
                     f"G = {G} phase groups (kfpos_timing_begin / _end over {TIMED} periods after {WARM} of warm-up)",
                command="python tools/planar_events_each_latency.py " + " ".join(sys.argv[1:]),
-               commit=a.commit or commit_of(), tags=a.tags, anchors=A, storage="F64", G=G, rounds=a.rounds,
+               commit=a.commit or commit_of(ROOT), tags=a.tags, anchors=A, storage="F64", G=G, rounds=a.rounds,
                layouts=layouts, synchronous=sync,
                requirement="contiguous layout: B's 10th .. 90th percentile range lies wholly below A's",
                requirement_met=bool(met))
-    text = json.dumps(res, indent=1)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
-    return 0 if met else 1
+    return finish(res, a.out, met)
 
 
 if __name__ == "__main__":

@@ -17,9 +17,7 @@ of the time per ranging period, in microseconds, and the ratio of the medians.
     python tools/planar_events_replay_latency.py --kernels-only      # one repetition of each, for a kernel trace
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -28,6 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from roskfpos_amd import capi  # noqa: E402
 from roskfpos_amd.synth import Workload  # noqa: E402
+from replay_timing import alternate, commit_of, entry, finish  # noqa: E402
 
 T, A = 1 << 16, 8
 TOA, PX4, IMU, MAG = capi.PLANAR_EVENT_TOA, capi.SENSOR_PX4FLOW, capi.SENSOR_IMU, capi.SENSOR_MAG
@@ -37,12 +36,6 @@ WARM, TIMED = 5, 20
 CFG = dict(use_fixed_height=1, fixed_height=1.0, init_angle=0.3, px4_height=Workload.PX4_HEIGHT, px4_arm_p1=0.05,
            px4_arm_p2=-0.02, px4_cov_velocity=0.002, px4_cov_gyro_z=0.001, imu_use_fixed_cov_acc=0, imu_cov_acc=0.02,
            imu_use_fixed_cov_ang_vel_z=1, imu_cov_ang_vel_z=0.0005, mag_angle_offset=0.1, mag_cov=0.01)
-
-
-def stats(us):
-    a = np.asarray(us)
-    return dict(n=int(a.size), median_us=float(np.median(a)), p10_us=float(np.percentile(a, 10)),
-                p90_us=float(np.percentile(a, 90)), min_us=float(a.min()), max_us=float(a.max()))
 
 
 class Replay:
@@ -112,14 +105,6 @@ class Replay:
         return self.bank.get_state() + (self.bank.get_latch(), self.bank.get_height())
 
 
-def commit_of():
-    try:
-        return subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True,
-                              check=True).stdout.strip()
-    except Exception:
-        return None
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -140,35 +125,24 @@ def main():
             rp.bank.close()
             continue
         same = all(g.tobytes() == r.tobytes() for g, r in zip(got, ref))
-        us = {"A": [], "B": []}
-        for _ in range(a.rounds):
-            for route in ("A", "B"):
-                us[route].append(rp.once(route))
+        us = alternate(("A", "B"), rp.once, a.rounds)
         rp.bank.close()
         counts = {k: period.count(v) for k, v in (("ranging", TOA), ("imu", IMU), ("px4flow", PX4), ("mag", MAG))}
-        entry = dict(period=name, events_per_period=len(period), events=counts, same_state=bool(same),
-                     A=stats(us["A"]), B=stats(us["B"]))
-        entry["ranges_overlap"] = not (entry["B"]["p90_us"] < entry["A"]["p10_us"] or
-                                       entry["A"]["p90_us"] < entry["B"]["p10_us"])
-        entry["A_over_B"] = entry["A"]["median_us"] / entry["B"]["median_us"]
-        per_period.append(entry)
-        print(f"{name:8s}: A {entry['A']['median_us']:8.1f} us [{entry['A']['p10_us']:.1f} .. {entry['A']['p90_us']:.1f}]   "
-              f"B {entry['B']['median_us']:8.1f} us [{entry['B']['p10_us']:.1f} .. {entry['B']['p90_us']:.1f}]   "
-              f"per ranging period, A / B = {entry['A_over_B']:.2f}; same state: {same}", flush=True)
+        e = entry(f"{name:8s}", "A", "B", us, period=name, events_per_period=len(period), events=counts,
+                  same_state=bool(same))
+        del e["second_wholly_below_first"]           # not in this tool's record
+        e["A_over_B"] = e["A"]["median_us"] / e["B"]["median_us"]
+        per_period.append(e)
     if a.kernels_only:
         return
     res = dict(what="planar event replay: single _dev calls on one stream (A) against kfpos_run_planar_events_dev (B), "
                     "microseconds per ranging period (kfpos_timing_begin / _end over "
                     f"{TIMED} periods after {WARM} of warm-up)",
                command="python tools/planar_events_replay_latency.py " + " ".join(sys.argv[1:]),
-               commit=a.commit or commit_of(), tags=a.tags, anchors=A, storage="F64", rounds=a.rounds,
+               commit=a.commit or commit_of(ROOT), tags=a.tags, anchors=A, storage="F64", rounds=a.rounds,
                per_period=per_period)
-    text = json.dumps(res, indent=1)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
+    return finish(res, a.out)
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

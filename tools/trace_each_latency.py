@@ -19,9 +19,7 @@ spread (exit status 1 if it is at any participation of the 65 536-tag bank; the 
     python tools/trace_each_latency.py --out profiles/trace_each_latency.json [--rounds 7] [--commit HASH]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -30,17 +28,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from roskfpos_amd import capi, synth  # noqa: E402
 from roskfpos_amd.synth import Workload  # noqa: E402
+from replay_timing import alternate, commit_of, finish, stats  # noqa: E402
 
 T, A = 1 << 16, 8
 GROUPS = (1, 2, 10)
 WARM, TIMED = 40, 400       # slots; both are multiples of every G
 ABSENT_MM = -1
-
-
-def stats(us):
-    a = np.asarray(us)
-    return dict(n=int(a.size), median_us=float(np.median(a)), p10_us=float(np.percentile(a, 10)),
-                p90_us=float(np.percentile(a, 90)), min_us=float(a.min()), max_us=float(a.max()))
 
 
 class Replay:
@@ -106,16 +99,13 @@ class Replay:
         run(WARM, WARM + TIMED)
         return b.timing_end(self.stream) * 1e3 / TIMED      # microseconds per slot
 
-    def compare(self, name, routes, sched, rounds):
+    def measure(self, name, routes, sched, rounds):
         states = []
         for route in routes:
             self.once(route, sched)
             states.append(self.bank.get_state())
         same = all(g.tobytes() == r.tobytes() for st in states[1:] for g, r in zip(st, states[0]))
-        us = {route: [] for route in routes}
-        for _ in range(rounds):
-            for route in routes:
-                us[route].append(self.once(route, sched))
+        us = alternate(routes, lambda route: self.once(route, sched), rounds)
         entry = dict(layout=name, tags=self.T, participation=sched[2], same_state=bool(same))
         for route in routes:
             entry[route] = stats(us[route])
@@ -129,14 +119,6 @@ class Replay:
             f"{r} {entry[r]['median_us']:7.2f} us [{entry[r]['p10_us']:.2f} .. {entry[r]['p90_us']:.2f}]" for r in routes) +
             f"   per slot; same state: {same}", flush=True)
         return entry
-
-
-def commit_of():
-    try:
-        return subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True,
-                              check=True).stdout.strip()
-    except Exception:
-        return None
 
 
 def main():
@@ -155,7 +137,7 @@ def main():
                       (("contiguous", (t // 64) % G), ("interleaved", t % G))
             for name, grp in layouts:
                 sched = rp.schedule(grp, G)
-                entry = rp.compare(name, ("A", "B", "C") if G == 1 else ("A", "B"), sched, a.rounds)
+                entry = rp.measure(name, ("A", "B", "C") if G == 1 else ("A", "B"), sched, a.rounds)
                 entry["groups"] = G
                 runs.append(entry)
                 del sched
@@ -167,17 +149,12 @@ def main():
                     "stream (A) against kfpos_run_trace_each_dev (B), and at full participation kfpos_run_trace_dev "
                     "with a shared dt (C); microseconds per slot, tags in G TDMA phase groups of one ranging period "
                     f"(kfpos_timing_begin / _end over {TIMED} slots after {WARM} of warm-up)",
-               command="python tools/trace_each_latency.py " + " ".join(sys.argv[1:]), commit=a.commit or commit_of(),
+               command="python tools/trace_each_latency.py " + " ".join(sys.argv[1:]), commit=a.commit or commit_of(ROOT),
                anchors=A, storage="MIXED", rounds=a.rounds, warm_slots=WARM, timed_slots=TIMED, runs=runs,
                claim=f"{a.tags[0]} tags, every participation and layout: B's median is not above A's by more than A's "
                      "own 10th .. 90th percentile spread",
                claim_holds=bool(met))
-    text = json.dumps(res, indent=1)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
-    return 0 if met else 1
+    return finish(res, a.out, met)
 
 
 if __name__ == "__main__":
