@@ -782,6 +782,11 @@ int kfpos_comm_backend_version(void);
 const char *kfpos_last_error(void);  /* thread-local detail of the last error (HIP failures, rejected configurations, calls out of sequence) */
 const char *kfpos_strerror(int code);
 int kfpos_version(void);
+/* The solve counts at which the lanes of a wavefront of the 9-state kernel meet to hand the tail of the gain iteration
+ * to pairs of lanes, for KFPOS_PAIR9_MEET=first,dense_until (read at kfpos_create; results do not depend on it): the
+ * kernel's own schedule function on the host. out[0 .. return value) ascending, the last one 20; at most 20 entries.
+ * Outside 1 <= first <= dense_until <= 20 (what kfpos_create refuses too), or out == NULL: returns -1. No GPU needed. */
+int kfpos_pair9_meet_points(int32_t first, int32_t dense_until, int32_t *out);
 /* name / duration helpers for benchmarks: time the last n enqueued step kernels with HIP events on the
  * stream they were launched on. kfpos_timing_begin records, kfpos_timing_end synchronises and returns ms. */
 int kfpos_timing_begin(kfpos_handle *h, void *stream);

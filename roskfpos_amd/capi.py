@@ -33,7 +33,7 @@ EXPORTS = [
     "kfpos_step_toa_imu_dev", "kfpos_get_pose_dev", "kfpos_run_trace_dev", "kfpos_run_events_dev",
     "kfpos_run_events_each_dev", "kfpos_run_planar_events_dev", "kfpos_run_planar_events_each_dev",
     "kfpos_run_trace_each_dev", "kfpos_last_error",
-    "kfpos_strerror", "kfpos_version", "kfpos_timing_begin", "kfpos_timing_end",
+    "kfpos_strerror", "kfpos_version", "kfpos_pair9_meet_points", "kfpos_timing_begin", "kfpos_timing_end",
     "kfpos_set_planar", "kfpos_step_sensor", "kfpos_step_sensor_dev", "kfpos_get_height", "kfpos_set_height",
     "kfpos_latch_dim", "kfpos_get_latch", "kfpos_set_latch",
     "kfpos_reset_tags", "kfpos_get_tags", "kfpos_set_tags",
@@ -206,6 +206,7 @@ def load():
     L.kfpos_last_error.restype = C.c_char_p
     L.kfpos_strerror.restype = C.c_char_p
     sig("kfpos_strerror", [C.c_int])
+    sig("kfpos_pair9_meet_points", [i32, i32, C.POINTER(i32)])
     _lib = L
     return L
 

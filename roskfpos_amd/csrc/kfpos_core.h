@@ -271,6 +271,9 @@ struct Params {
                                                 individually (LDS); non-null = the tail of the gain iteration runs two
                                                 lanes per tag (iekf9_pairs) */
     bool pair9 = false; /* the same for a kernel whose pairs read the anchors from the kernel arguments (iekf9_pairs_held) */
+    int pair9_first = 8, pair9_dense_until = 8; /* ... and where its lanes meet to look for the hand-over: after pair9_first
+                                                   solves, then after every solve up to pair9_dense_until, then after
+                                                   every 4 (iekf9_next_meet); wave-uniform */
 };
 
 /* ------------------------------------------------------------------ 3x3 helpers */

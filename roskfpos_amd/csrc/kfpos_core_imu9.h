@@ -872,6 +872,14 @@ KFPOS_FN void iekf9_pairs_held(uint64_t m, const double xhat[9], const double *b
  * 8-anchor step kernels that have the registers to hold what a pair trip reads (k_step_imu9 says which); every other
  * caller compiles the text it always compiled -- the event kernels, which never form pairs at run time, sit at the top
  * of the register file and spill inside their loops when that text changes, even when it only goes away. */
+/* Where the lanes of a wavefront meet to see whether the pairs can take over: the solve count of the meeting after the
+ * one at `stop` -- one solve on while stop < dense_until, four from there, never beyond max_steps. (first, dense_until)
+ * = (8, 8) is 8, 12, 16, 20; (8, 10) is 8, 9, 10, 14, 18, 20 (Params::pair9_first / pair9_dense_until). */
+KFPOS_FN int iekf9_next_meet(int stop, int dense_until, int max_steps) {
+    const int next = stop + (stop < dense_until ? 1 : 4);
+    return next < max_steps ? next : max_steps;
+}
+
 template <bool DIAG, bool ALLIMU, bool RANGING, bool ACC0 = false, bool HOLD = true, bool SETTLE = false,
           bool TAIL = false, class SC>
 KFPOS_FN void iekf9_info(const double xhat[9], const double *binv, int binv_stride, SC &sc, const Params &pr,
@@ -893,8 +901,17 @@ KFPOS_FN void iekf9_info(const double xhat[9], const double *binv, int binv_stri
 #if defined(__HIP_DEVICE_COMPILE__)
     /* with pairs the lanes meet again after 8 solves, then after every 4: by then (BASELINE configs[2] trace: after 8
      * in 97 % of the wavefronts) at most half of them are still iterating. Looking after every pass would cost the
-     * per-lane loop more than the pairs give back (measured: 1.2 us per epoch for a ballot and a branch per trip). */
-    if (pairs) stop = 8 < max_steps ? 8 : max_steps;
+     * per-lane loop more than the pairs give back (measured: 1.2 us per epoch for a ballot and a branch per trip).
+     * TAIL: the meeting points are the launch's (iekf9_next_meet; wave-uniform, kfpos_create decides; default 8, 9, 10,
+     * then every 4): a meeting after s solves finds the lanes whose final count is at least s, and on the bench trace
+     * 45 % of the wavefronts still have more than 32 of them at 8 and at most 32 at 9 or 10 -- they need not run per lane
+     * until 12. A meeting at 7 costs more than the 5 % of wavefronts that could use it give back (measured: a meeting
+     * is ~80 quad-cycles; profiles/HISTORY.md, "Where the lanes meet"). Every other caller keeps the constants in its
+     * text. */
+    if (pairs) {
+        if constexpr (TAIL) stop = pr.pair9_first < max_steps ? pr.pair9_first : max_steps;
+        else stop = 8 < max_steps ? 8 : max_steps;
+    }
 #endif
     Iekf9Parked pk;
     if constexpr (HOLD) iekf9_fetch<false, DIAG, true>(binv, binv_stride, imu, pk);
@@ -919,7 +936,8 @@ KFPOS_FN void iekf9_info(const double xhat[9], const double *binv, int binv_stri
                     else iekf9_pairs<DIAG, ACC0>(m, xhat, binv, binv_stride, sc, pr.pair_anchor_tab, imu, max_steps, tol, it, o);
                     break;
                 }
-                stop = stop + 4 < max_steps ? stop + 4 : max_steps;
+                if constexpr (TAIL) stop = iekf9_next_meet(stop, pr.pair9_dense_until, max_steps);
+                else stop = stop + 4 < max_steps ? stop + 4 : max_steps;
                 continue;
             }
         }

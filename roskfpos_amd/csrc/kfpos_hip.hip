@@ -35,6 +35,8 @@ void fill_args(const kfpos_handle *h, KArgs &a) {
     a.top_n = h->cfg.top_n;
     a.ml_variant = h->cfg.model == KFPOS_MODEL_ML ? h->cfg.ml_variant : 0;
     a.pair9 = h->pair9 ? 1 : 0;
+    a.pair9_first = (short)h->pair9_first;
+    a.pair9_dense_until = (short)h->pair9_dense_until;
     a.imu9_diag = h->imu9_diag ? 1 : 0;
     a.use_init_pos = h->cfg.use_init_pos;
     a.use_fixed_height = h->planar.use_fixed_height;
@@ -152,6 +154,20 @@ size_t small_bank_limit() { /* elements of the range matrix (n_tags x max_anchor
     const char *e = getenv("KFPOS_SMALL_BANK_ELEMS");
     return e ? (size_t)atol(e) : 4096;
 }
+
+/* The meeting points of the 9-state pairs' tail (iekf9_next_meet): KFPOS_PAIR9_MEET=first,dense_until, unset or empty =
+ * the default (8,10: after 8, 9 and 10 solves, then every 4; 8,8 = the schedule before this one: 8, then every 4; the
+ * counters of profiles/imu9_pairs_meet_pmc.json chose it). false: not two integers with 1 <= first <= dense_until <= 20 (the cap of the gain iteration). */
+constexpr int PAIR9_MEET_FIRST = 8, PAIR9_MEET_DENSE_UNTIL = 10, PAIR9_MEET_MAX = 20;
+bool pair9_meet(int *first, int *dense_until) {
+    *first = PAIR9_MEET_FIRST;
+    *dense_until = PAIR9_MEET_DENSE_UNTIL;
+    const char *e = getenv("KFPOS_PAIR9_MEET");
+    if (!e || !e[0]) return true;
+    char rest = 0;
+    if (std::sscanf(e, "%d,%d%c", first, dense_until, &rest) != 2) return false;
+    return 1 <= *first && *first <= *dense_until && *dense_until <= PAIR9_MEET_MAX;
+}
 } // namespace
 
 extern "C" {
@@ -170,6 +186,16 @@ const char *kfpos_strerror(int code) {
     }
 }
 int kfpos_version(void) { return KFPOS_VERSION; }
+int kfpos_pair9_meet_points(int32_t first, int32_t dense_until, int32_t *out) {
+    if (!out || first < 1 || first > dense_until || dense_until > PAIR9_MEET_MAX) return -1;
+    int n = 0;
+    int stop = first;
+    for (;;) { /* as iekf9_info walks it with max_steps = 20 */
+        out[n++] = stop;
+        if (stop >= PAIR9_MEET_MAX) return n;
+        stop = iekf9_next_meet(stop, dense_until, PAIR9_MEET_MAX);
+    }
+}
 
 int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
     if (!cfg || !out) return KFPOS_ERR_ARG;
@@ -197,6 +223,9 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
         (cfg->model == KFPOS_MODEL_ML && cfg->ignore_worst) ||
         (cfg->model == KFPOS_MODEL_PLANAR && (cfg->top_n || cfg->ignore_worst)))
         return bad("ignore_worst exists for the 6-state filter only, top_n for the 6-state filter and the ML estimator");
+    int meet_first, meet_dense_until;
+    if (!pair9_meet(&meet_first, &meet_dense_until))
+        return bad("KFPOS_PAIR9_MEET must be first,dense_until with 1 <= first <= dense_until <= 20");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) {
         g_err = "no HIP device";
@@ -234,6 +263,9 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
         const char *np = getenv("KFPOS_PAIR9");
         h->pair9 = np && np[0] ? np[0] == '1'
                                : (cfg->storage == KFPOS_STORE_MIXED || cfg->storage == KFPOS_STORE_P48);
+        /* where the lanes of a wavefront meet to look for the hand-over: KFPOS_PAIR9_MEET (validated above) */
+        h->pair9_first = meet_first;
+        h->pair9_dense_until = meet_dense_until;
         const char *nd = getenv("KFPOS_IMU9_DIAG");
         h->imu9_diag = !(nd && nd[0] == '0');
         const char *nc = getenv("KFPOS_NO_COOP");

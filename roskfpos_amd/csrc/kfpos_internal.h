@@ -49,6 +49,7 @@ struct kfpos_handle {
     bool force_generic; /* KFPOS_GENERIC_KERNEL=1: always the LDS-staged kernel (A/B measurements, tests) */
     bool two_waves;     /* n_tags / 64 exceeds the device's SIMD count (KFPOS_ONE_WAVE_BUILD=1: never) */
     bool pair9;         /* 9-state bank: iekf9_pairs for the tail of the gain iteration; bit-identical either way. Default: on in KFPOS_STORE_MIXED and KFPOS_STORE_P48, whose pair trips read registers only (2.8 % fewer cycles per epoch), off in the other two; KFPOS_PAIR9=0 / =1 overrides (profiles/HISTORY.md, "The pairs' tail") */
+    int pair9_first, pair9_dense_until; /* ... and where the lanes of a wavefront meet to look for the hand-over (iekf9_next_meet): KFPOS_PAIR9_MEET=first,dense_until, 1 <= first <= dense_until <= 20, default 8,10; 8,8 = after 8 solves, then every 4 (profiles/HISTORY.md, "Where the lanes meet") */
     bool imu9_diag;     /* 9-state bank: wavefronts with diagonal accelerometer covariances take the diagonal form of the gain iteration (bit-identical); KFPOS_IMU9_DIAG=0 disables */
     bool coop;          /* small plain 6-state bank: one tag per 8 lanes (k_step_toa6_coop); KFPOS_NO_COOP=1 disables */
     double anchors[KFPOS_MAX_ANCHORS * 3];

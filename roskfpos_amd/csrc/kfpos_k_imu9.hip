@@ -19,6 +19,13 @@ __device__ inline void forget(double &v) { asm volatile("" : "=v"(v)); }
 /* RANGING = false: the IMU-only call (MODE_IMU_ONLY), a kernel of its own */
 template <typename REAL, typename MREAL, int AS, bool RANGING = true>
 __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
+    /* Four bytes of padding, executed once per launch. The text that reads KArgs::pair9_first / pair9_dense_until moved
+     * every loop of this kernel by 4 bytes modulo 8, and with the same instructions in every trip loop the wavefronts
+     * then took 0.55 % (MIXED) / 0.45 % (P48) more cycles per epoch than with this instruction in front, at the same
+     * schedule: where a loop lies modulo 8 bytes is worth as much as the schedule (profiles/HISTORY.md, "Where the
+     * lanes meet"). Whoever changes the instruction count in front of the loops measures both phases again. */
+    if constexpr (AS == 8 && RANGING && sizeof(MREAL) == 4 && !std::is_same<REAL, float>::value) /* = TAIL, below */
+        __builtin_amdgcn_s_setprio(0); /* (the priority a wavefront starts with: does nothing) */
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
     const size_t t = (size_t)blockIdx.x * WAVE + lane;
@@ -74,8 +81,11 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const KArgs a) {
     /* The Gauss-Newton solves in ml_estimate's peeled text (step_imu9_state). The same two 8-anchor instantiations as
      * above, short of registers, spill inside the epoch loop with it and keep the unpeeled text. */
     constexpr bool PEEL = AS != 8 || AHEAD;
-    if constexpr (TAIL) pr.pair9 = a.pair9 != 0;
-    else if constexpr (AS == 8 && RANGING) { /* the anchor table once more, where lanes can index it one by one */
+    if constexpr (TAIL) {
+        pr.pair9 = a.pair9 != 0;
+        pr.pair9_first = a.pair9_first;
+        pr.pair9_dense_until = a.pair9_dense_until;
+    } else if constexpr (AS == 8 && RANGING) { /* the anchor table once more, where lanes can index it one by one */
         if (a.pair9) {
             double *tab = lds + 78 * WAVE;
 #pragma unroll

@@ -59,6 +59,10 @@ struct KArgs {
     int imu9_diag;    /* 9-state kernel: a wavefront whose accelerometer covariances are all diagonal runs the diagonal form of the gain iteration's pass (same bits; KFPOS_IMU9_DIAG=0: never) */
     /* planar filter configuration (kfpos_planar_config) */
     int use_fixed_height, imu_fixed_cov_acc, imu_fixed_cov_w;
+    /* pair9's meeting points (Params::pair9_first / pair9_dense_until; KFPOS_PAIR9_MEET=first,dense_until at kfpos_create,
+     * both 1 .. 20). Two 16-bit fields HERE, in the four bytes that were padding in front of the doubles: no other field
+     * moves, so no other kernel's argument loads do */
+    short pair9_first, pair9_dense_until;
     double px4_height, px4_arm_p1, px4_arm_p2, px4_cov_vel, px4_cov_gyro_z;
     double imu_cov_acc, imu_cov_w, mag_offset, mag_cov;
     double *platch;   /* [15][T] planar filter: latched PX4Flow (5), IMU (8), magnetometer (2) samples */

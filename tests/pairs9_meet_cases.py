@@ -1,0 +1,153 @@
+"""What tests/test_pairs9_meet_gpu.py and tests/test_pairs9_meet_emu.py share: the 12-epoch trace on which the lanes of a
+9-state wavefront meet in every way the schedule of iekf9_next_meet distinguishes, the scenarios as they are read off the
+solve counts ((status >> 8) & 0xFF), the seed chosen with the oracle on the CPU -- and, run as a program, the child process
+that replays the trace under ONE setting of KFPOS_PAIR9_MEET / KFPOS_PAIR9 (the parent sets the environment) and writes
+every byte it produced to an .npz:
+
+    python tests/pairs9_meet_cases.py OUT.npz [SEED]
+
+The scenarios, in the kernel's terms: a lane with a final count g runs g + 1 passes (the last finds it converged), so the
+meeting after s solves finds the lanes with g >= s. "first at s": more than 32 lanes at every meeting before s, at most 32
+(and somebody) at s. The trace: synth.Workload from a fixed start, whose first epochs converge in a few solves, with the
+epochs' dt stretched (x 1.2 from the third epoch, x 1.4 and x 3 for the last two) so that the later ones keep more and more
+lanes iterating: within 12 epochs one wavefront goes from "nobody left at 7" to "more than 32 lanes beyond 11". MARGIN
+lanes are kept clear on either side of every threshold the seed is chosen by, so that a solve count that differs by one
+on a lane (KFPOS_STORE_P48 against the oracle) does not move a wavefront into another scenario."""
+import functools
+import os
+import sys
+
+import numpy as np
+
+A, S = 8, 12
+SPLIT = (5, 7)
+DT_SCALE = np.array([1, 1, 1.2, 1.2, 1.2, 1.2, 1.2, 1.2, 1.2, 1.2, 1.4, 3.0])
+MARGIN = 2
+SHAPES = ((64, 2), (128, 2), (101, 2), (64, 3), (128, 3), (101, 3))   # (tags, storage: 2 = mixed, 3 = p48)
+NAN_TAG, NAN_T = 5, 64
+SETTINGS = {"default": {}, "7,10": {"KFPOS_PAIR9_MEET": "7,10"}, "8,8": {"KFPOS_PAIR9_MEET": "8,8"},
+            "1,20": {"KFPOS_PAIR9_MEET": "1,20"}, "no pairs": {"KFPOS_PAIR9": "0"}}   # default: 8,10
+SCENARIOS = ("first at 7", "first at 8", "first at 9 or 10", "more than 32 until at least 11", "at most 32 by 6",
+             "nobody left at 7")
+
+
+def dts():
+    from test_imu9_epoch_loop_gpu import _dts
+    return _dts(S) * DT_SCALE
+
+
+def gain_iters(status):
+    return (np.asarray(status).astype(np.uint32) >> 8) & 0xFF
+
+
+def scenarios(g, margin=0):
+    """g: [epoch][64] solve counts of one full wavefront -> {scenario: [epochs]}. Pairs are formed only where every lane
+    runs the iteration (a count > 0 on every lane: a lane without an update leaves the step early). margin: lanes kept
+    clear of 32 on either side of every threshold looked at."""
+    left = np.stack([(g >= s).sum(1) for s in range(21)], 1)       # [epoch][s]: whom a meeting after s solves finds
+    all_in = (g > 0).all(1)
+    many, few = 33 + margin, 32 - margin                            # "more than 32" / "at most 32", margin lanes clear
+
+    def first_at(s, by=None):
+        by = by or s
+        return all_in & (left[:, s - 1] >= many) & (left[:, by] <= few) & (left[:, by] > 0)
+
+    return {
+        "first at 7": np.flatnonzero(first_at(7)),
+        "first at 8": np.flatnonzero(first_at(8)),
+        "first at 9 or 10": np.flatnonzero(first_at(9, 10)),   # more than 32 at 8, at most 32 by 10
+        "more than 32 until at least 11": np.flatnonzero(all_in & (left[:, 10] >= many)),
+        "at most 32 by 6": np.flatnonzero(all_in & (left[:, 6] <= few) & (left[:, 7] > 0)),
+        "nobody left at 7": np.flatnonzero(all_in & (left[:, 7] == 0)),
+    }
+
+
+def oracle_run(T, seed):
+    """the trace through the oracle alone, f32 measurements as the two storage modes hold them ->
+    (poses [S][3][T], status [S][T])"""
+    import oracle_py
+    from roskfpos_amd.synth import Workload
+    from test_imu9_epoch_loop_gpu import _trace
+    w = Workload(T, A, seed=seed)
+    tr = _trace(w, S, 2, "cpu")
+    o = oracle_py.OracleBank(1, T, w.anchors, init_pos=w.init_positions(), n_threads=8)
+    err, cov = w.err_est(np.float32).astype(np.float64), tr["cov_host"].astype(np.float64)
+    poses, stats = [], []
+    for s, dt in enumerate(dts()):
+        o.step_imu(w.accel(s, np.float32).astype(np.float64), cov, 0.0)
+        stats.append(np.asarray(o.step_toa(tr["r_host"][s], err, dt)).astype(np.uint32))
+        poses.append(o.get_state()[0][:, :3].T.copy())
+    return np.stack(poses), np.stack(stats)
+
+
+@functools.lru_cache(maxsize=None)
+def seed():
+    """the first workload seed for which the ORACLE sees every scenario in the first wavefront (tags 0 .. 63: a tag's trace
+    does not depend on how many tags the workload has, so the seed serves every shape), MARGIN lanes clear of every
+    threshold"""
+    for sd in range(1, 41):
+        if all(len(v) for v in scenarios(gain_iters(oracle_run(64, sd)[1]), MARGIN).values()):
+            return sd
+    raise AssertionError("no seed in 1 .. 40 for which the oracle sees every meeting scenario in one wavefront")
+
+
+# ---- the child process: one setting, every shape
+
+def _replay(T, storage, sd):
+    """-> {name: array} for one shape: the 12 epochs as one launch, as 5 + 7, and as single calls (whose status words
+    carry every epoch's solve counts)"""
+    from roskfpos_amd import capi
+    from roskfpos_amd.synth import Workload
+    from test_imu9_epoch_loop_gpu import _fused, _trace
+    from test_pairs9_tail_gpu import _single_calls
+    w = Workload(T, A, seed=sd)
+    tr = _trace(w, S, storage, "cuda:0")
+    d = dts()
+    out = {}
+
+    def bank():
+        return capi.KfposBank(capi.MODEL_TOA_IMU, T, w.anchors, storage=storage, init_pos=w.init_positions())
+
+    def keep(name, res):
+        for part, a in zip(("poses", "status", "x", "P", "flags", "latch"), res):
+            out[f"{T}/{storage}/{name}/{part}"] = np.ascontiguousarray(a)
+
+    b = bank()
+    keep("one launch", _fused(b, tr, S, d, T, A))
+    b.close()
+    b = bank()
+    first = _fused(b, tr, SPLIT[0], d, T, A)
+    second = _fused(b, tr, SPLIT[1], d, T, A, s0=SPLIT[0])
+    keep("5 + 7", (np.concatenate([first[0], second[0]]),) + second[1:])
+    b.close()
+    b = bank()
+    keep("single calls", _single_calls(b, tr, d, T, n=S))
+    b.close()
+    if (T, storage) in ((NAN_T, 2), (NAN_T, 3)):      # a NaN wave-mate: 5 epochs, the position of one tag made NaN, 7 epochs
+        b = bank()
+        _fused(b, tr, SPLIT[0], d, T, A)
+        x, P, fl = b.get_state()
+        x[NAN_TAG, :3] = np.nan
+        b.set_state(x, P, fl)
+        keep("nan, one launch", _fused(b, tr, SPLIT[1], d, T, A, s0=SPLIT[0]))
+        b2 = bank()                                    # ... and the same 7 epochs as single calls, from the same state
+        _fused(b2, tr, SPLIT[0], d, T, A)
+        b2.set_state(x, P, fl)
+        keep("nan, single calls", _single_calls(b2, tr, d, T, s0=SPLIT[0], n=SPLIT[1]))
+        b2.close()
+        b.close()
+    return out
+
+
+def main(path, sd=None):
+    import conftest  # noqa: F401  (the import paths of the suite)
+    sd = seed() if sd is None else sd
+    out = {"seed": np.array(sd)}
+    for T, storage in SHAPES:
+        out.update(_replay(T, storage, sd))
+    np.savez(path, **out)
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else None)
