@@ -24,6 +24,27 @@ MAX_ANCHORS = 64
 ST_UPDATE_SKIPPED, ST_ML_FALLBACK, ST_FEW_RANGES, ST_ML_INIT, ST_NOT_STARTED, ST_NONFINITE = 1, 2, 4, 8, 16, 32
 ST_SKIPPED = 64
 
+
+def st_flags(s):
+    """the ST_* bits of status words (numpy)"""
+    return np.asarray(s).astype(np.uint32) & 0xFF
+
+
+def st_gain_iters(s):
+    """KFPOS_ST_GAIN_ITERS"""
+    return (np.asarray(s).astype(np.uint32) >> 8) & 0xFF
+
+
+def st_ml_iters(s):
+    """KFPOS_ST_ML_ITERS"""
+    return (np.asarray(s).astype(np.uint32) >> 16) & 0xFF
+
+
+def st_ignored(s):
+    """KFPOS_ST_IGNORED: -1 where no range was left out"""
+    return ((np.asarray(s).astype(np.uint32) >> 24) & 0xFF).astype(np.int32) - 1
+
+
 # every symbol include/kfpos.h declares
 EXPORTS = [
     "kfpos_create", "kfpos_destroy", "kfpos_init", "kfpos_set_anchors", "kfpos_set_init_positions",

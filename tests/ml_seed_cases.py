@@ -11,11 +11,13 @@ import functools
 
 import numpy as np
 
+import step_checks as sc
+from roskfpos_amd.capi import ST_FEW_RANGES, ST_ML_FALLBACK, ST_NONFINITE, ST_UPDATE_SKIPPED, st_flags
+from roskfpos_amd.capi import st_ml_iters as ml_iters
 from roskfpos_amd.synth import Workload
 
 A, S = 8, 7
-DTS = np.array([0.03 + 0.01 * (s % 5) for s in range(S)])   # a dt of its own for every epoch
-ST_UPDATE_SKIPPED, ST_ML_FALLBACK, ST_FEW_RANGES, ST_NONFINITE = 0x01, 0x02, 0x04, 0x20
+DTS = sc.dts(S)   # a dt of its own for every epoch
 
 CENTRE = np.array([5.0, 5.0, 1.0])
 OFFSETS = np.array([[4, 4, 2], [-4, -4, 2], [-4, 4, -2], [4, -4, -2],        # norm 6
@@ -32,31 +34,37 @@ SPECIAL = (FEW, EXACT, ZERO_ERR, NAN_ERR) + tuple(GARBAGE)
 LANES = 37         # the lanes of the first wavefront that every bank size of the tests has
 
 
-def ml_iters(status):
-    return (np.asarray(status).astype(np.uint32) >> 16) & 0xFF
-
-
-def oracle_status_comparable(model, T):
-    """[S][T]: the status words the oracle and the kernels agree on. As weights_selects.oracle_status_comparable, the
-    9-state oracle reports the tag with a NaN errorEstimation on a used range with other words than the kernels. And
-    the exact fit of epoch 0 is exact for the kernels' step p - Hs^-1 g only (g = 0 leaves p where it is: 2 iterations);
+def oracle_status_comparable(model, T, exact_fit=True):
+    """[S][T]: the status words the oracle and the kernels agree on. The 9-state oracle reports the tag with a NaN
+    errorEstimation on a used range (NAN_ERR, here and in weights_selects.py) with other words than the kernels, update
+    skipped against iterated to the cap, as it always did. exact_fit: the trace holds this module's exact fit. The fit
+    of epoch 0 is exact for the kernels' step p - Hs^-1 g only (g = 0 leaves p where it is: 2 iterations);
     the reference's solve(Hs, Hs p - g) returns p to rounding, its next cost is 1e-30 instead of 0, and it counts a
     third iteration -- at the same position to 1e-15 m, which the position bounds check."""
     ok = np.ones((S, T), dtype=bool)
     if model == 1:
         ok[:, NAN_ERR] = False
-    ok[0, EXACT] = False
+    if exact_fit:
+        ok[0, EXACT] = False
     return ok
 
 
-def inputs(T, real=np.float64, seed=None):
-    """(workload, fixed starts [T][3], ranges [S][T][A] int32, errorEstimation [T][A] float64 holding values of `real`)"""
-    assert T > max(SPECIAL)
+def inputs(T, real=np.float64, seed=None, cases=None, anchors=ANCHORS):
+    """(workload, fixed starts [T][3], ranges [S][T][A] int32, errorEstimation [T][A] float64 holding values of `real`).
+    What weights_selects.py sets otherwise (its INPUTS): seed, None = the one _seed() chooses with the oracle;
+    cases(init, r, err) puts the special tags in, None = this module's; anchors, None = the synthetic room's"""
     w = Workload(T, A, seed=_seed() if seed is None else seed)
-    w.anchors = ANCHORS.copy()
+    if anchors is not None:
+        w.anchors = anchors.copy()
     init = w.init_positions().copy()
     r = np.stack([w.ranges_mm(s) for s in range(S)])
     err = w.err_est().copy()
+    (cases or _cases)(init, r, err)
+    return w, init, r, err.astype(real).astype(np.float64)
+
+
+def _cases(init, r, err):
+    assert len(init) > max(SPECIAL)
     r[:, FEW, 3:] = -1
     init[EXACT] = CENTRE
     r[0, EXACT] = EXACT_MM
@@ -65,7 +73,6 @@ def inputs(T, real=np.float64, seed=None):
     for lane, junk in GARBAGE.items():
         r[:, lane, 1] = -1
         err[lane, 1] = junk
-    return w, init, r, err.astype(real).astype(np.float64)
 
 
 def slow_next_to_quick(iters):
@@ -79,21 +86,14 @@ def slow_next_to_quick(iters):
 def _seed():
     """the first workload seed for which the ORACLE (9-state and 6-state, on 8-byte and on 4-byte measurements) sees, in
     the first wavefront, a lane with 1 or 2 Gauss-Newton iterations next to a lane with at least 5"""
-    import oracle_py
-    for seed in range(1, 17):
-        ok = True
+    def occurs(seed):
         for model, real in ((1, np.float64), (1, np.float32), (0, np.float64)):
             w, init, r, err = inputs(LANES, real, seed=seed)
-            o = oracle_py.OracleBank(model, LANES, w.anchors, init_pos=init, n_threads=8)
-            its = []
-            for s in range(S):
-                if model == 1:
-                    o.step_imu(w.accel(s, real).astype(np.float64), w.accel_cov(real).astype(np.float64), 0.0)
-                its.append(ml_iters(o.step_toa(r[s], err, DTS[s])))
-            ok = ok and len(slow_next_to_quick(np.stack(its))) > 0
-        if ok:
-            return seed
-    raise AssertionError("no seed in 1 .. 16 for which the oracle sees a slow lane next to a quick one")
+            st = sc.oracle_run(w, r, err, DTS, model=model, real=real, init=init)[1]
+            if not len(slow_next_to_quick(ml_iters(st))):
+                return False
+        return True
+    return sc.first_seed(range(1, 17), occurs, "a slow lane next to a quick one")
 
 
 def assert_cases_occur(model, r, err, init, status):
@@ -106,7 +106,7 @@ def assert_cases_occur(model, r, err, init, status):
     # the exact fit: distances in whole millimetres from the tag's start, and 2 iterations (step, cost 0, 0 / 0)
     d = np.sqrt(((ANCHORS - init[EXACT]) ** 2).sum(1))
     assert np.array_equal(d * 1000.0, r[0, EXACT].astype(np.float64))
-    assert it[0, EXACT] == 2 and not (st[0, EXACT] & 0xFF), (it[0, EXACT], st[0, EXACT])
+    assert it[0, EXACT] == 2 and not st_flags(st[0, EXACT]), (it[0, EXACT], st[0, EXACT])
     # a slow lane next to a quick one in the first wavefront
     assert len(slow_next_to_quick(it)) > 0, it[:, :LANES]
     # errorEstimation 0 on a used range: the reference throws
@@ -124,4 +124,4 @@ def assert_cases_occur(model, r, err, init, status):
         assert (r[:, lane, 1] <= 0).all() and (np.isnan(junk) and np.isnan(err[lane, 1]) or err[lane, 1] == junk)
         assert (it[:, lane] >= 2).all() and not (st[:, lane] & (ST_UPDATE_SKIPPED | ST_NONFINITE)).any(), lane
     ordinary = np.setdiff1d(np.arange(st.shape[1]), SPECIAL)
-    assert not (st[:, ordinary] & 0xFF).any() and (it[:, ordinary] >= 2).all()
+    assert not st_flags(st[:, ordinary]).any() and (it[:, ordinary] >= 2).all()

@@ -19,8 +19,13 @@ import sys
 
 import numpy as np
 
+import conftest  # noqa: F401  (the import paths of the suite, also where this file runs as a program)
+import step_checks as sc
+from roskfpos_amd.capi import st_gain_iters as gain_iters  # noqa: F401  (the tests read the solve counts with it)
+from roskfpos_amd.synth import Workload
+
 A, S = 8, 12
-SPLIT = (5, 7)
+SPLIT = 5          # launches of 5 and 7 epochs
 DT_SCALE = np.array([1, 1, 1.2, 1.2, 1.2, 1.2, 1.2, 1.2, 1.2, 1.2, 1.4, 3.0])
 MARGIN = 2
 SHAPES = ((64, 2), (128, 2), (101, 2), (64, 3), (128, 3), (101, 3))   # (tags, storage: 2 = mixed, 3 = p48)
@@ -32,12 +37,7 @@ SCENARIOS = ("first at 7", "first at 8", "first at 9 or 10", "more than 32 until
 
 
 def dts():
-    from test_imu9_epoch_loop_gpu import _dts
-    return _dts(S) * DT_SCALE
-
-
-def gain_iters(status):
-    return (np.asarray(status).astype(np.uint32) >> 8) & 0xFF
+    return sc.dts(S) * DT_SCALE
 
 
 def scenarios(g, margin=0):
@@ -65,19 +65,10 @@ def scenarios(g, margin=0):
 def oracle_run(T, seed):
     """the trace through the oracle alone, f32 measurements as the two storage modes hold them ->
     (poses [S][3][T], status [S][T])"""
-    import oracle_py
-    from roskfpos_amd.synth import Workload
-    from test_imu9_epoch_loop_gpu import _trace
     w = Workload(T, A, seed=seed)
-    tr = _trace(w, S, 2, "cpu")
-    o = oracle_py.OracleBank(1, T, w.anchors, init_pos=w.init_positions(), n_threads=8)
-    err, cov = w.err_est(np.float32).astype(np.float64), tr["cov_host"].astype(np.float64)
-    poses, stats = [], []
-    for s, dt in enumerate(dts()):
-        o.step_imu(w.accel(s, np.float32).astype(np.float64), cov, 0.0)
-        stats.append(np.asarray(o.step_toa(tr["r_host"][s], err, dt)).astype(np.uint32))
-        poses.append(o.get_state()[0][:, :3].T.copy())
-    return np.stack(poses), np.stack(stats)
+    r = sc.Trace(w, S, 2, "cpu", gaps=True).r_host
+    poses, status = sc.oracle_run(w, r, w.err_est(), dts(), real=np.float32, init=w.init_positions())[:2]
+    return poses.transpose(0, 2, 1), status
 
 
 @functools.lru_cache(maxsize=None)
@@ -85,62 +76,47 @@ def seed():
     """the first workload seed for which the ORACLE sees every scenario in the first wavefront (tags 0 .. 63: a tag's trace
     does not depend on how many tags the workload has, so the seed serves every shape), MARGIN lanes clear of every
     threshold"""
-    for sd in range(1, 41):
-        if all(len(v) for v in scenarios(gain_iters(oracle_run(64, sd)[1]), MARGIN).values()):
-            return sd
-    raise AssertionError("no seed in 1 .. 40 for which the oracle sees every meeting scenario in one wavefront")
+    return sc.first_seed(range(1, 41), lambda sd: all(len(v) for v in scenarios(gain_iters(oracle_run(64, sd)[1]),
+                                                                              MARGIN).values()),
+                         "every meeting scenario in one wavefront")
 
 
 # ---- the child process: one setting, every shape
 
 def _replay(T, storage, sd):
     """-> {name: array} for one shape: the 12 epochs as one launch, as 5 + 7, and as single calls (whose status words
-    carry every epoch's solve counts)"""
-    from roskfpos_amd import capi
-    from roskfpos_amd.synth import Workload
-    from test_imu9_epoch_loop_gpu import _fused, _trace
-    from test_pairs9_tail_gpu import _single_calls
+    carry every epoch's solve counts). The banks keep the setting this process was started under."""
     w = Workload(T, A, seed=sd)
-    tr = _trace(w, S, storage, "cuda:0")
+    tr = sc.Trace(w, S, storage, gaps=True)
     d = dts()
     out = {}
 
     def bank():
-        return capi.KfposBank(capi.MODEL_TOA_IMU, T, w.anchors, storage=storage, init_pos=w.init_positions())
+        return sc.bank(w, T, storage, pairs=os.environ.get("KFPOS_PAIR9"), meet=os.environ.get("KFPOS_PAIR9_MEET"))
 
     def keep(name, res):
-        for part, a in zip(("poses", "status", "x", "P", "flags", "latch"), res):
+        for part, a in zip(sc.Run._fields, res):
             out[f"{T}/{storage}/{name}/{part}"] = np.ascontiguousarray(a)
 
-    b = bank()
-    keep("one launch", _fused(b, tr, S, d, T, A))
-    b.close()
-    b = bank()
-    first = _fused(b, tr, SPLIT[0], d, T, A)
-    second = _fused(b, tr, SPLIT[1], d, T, A, s0=SPLIT[0])
-    keep("5 + 7", (np.concatenate([first[0], second[0]]),) + second[1:])
-    b.close()
-    b = bank()
-    keep("single calls", _single_calls(b, tr, d, T, n=S))
-    b.close()
-    if (T, storage) in ((NAN_T, 2), (NAN_T, 3)):      # a NaN wave-mate: 5 epochs, the position of one tag made NaN, 7 epochs
+    for name, run in (("one launch", sc.fused), ("5 + 7", functools.partial(sc.fused_split, split=SPLIT)),
+                      ("single calls", sc.single_calls)):
         b = bank()
-        _fused(b, tr, SPLIT[0], d, T, A)
-        x, P, fl = b.get_state()
-        x[NAN_TAG, :3] = np.nan
-        b.set_state(x, P, fl)
-        keep("nan, one launch", _fused(b, tr, SPLIT[1], d, T, A, s0=SPLIT[0]))
-        b2 = bank()                                    # ... and the same 7 epochs as single calls, from the same state
-        _fused(b2, tr, SPLIT[0], d, T, A)
-        b2.set_state(x, P, fl)
-        keep("nan, single calls", _single_calls(b2, tr, d, T, s0=SPLIT[0], n=SPLIT[1]))
-        b2.close()
+        keep(name, run(b, tr, d, S))
         b.close()
+    if (T, storage) in ((NAN_T, 2), (NAN_T, 3)):      # a NaN wave-mate: 5 epochs, the position of one tag made NaN, 7 epochs
+        for name, run in (("nan, one launch", sc.fused), ("nan, single calls", sc.single_calls)):
+            b = bank()
+            sc.fused(b, tr, d, SPLIT)
+            if name == "nan, one launch":
+                x, P, fl = b.get_state()
+                x[NAN_TAG, :3] = np.nan
+            b.set_state(x, P, fl)                      # (the single calls start from the launch's state)
+            keep(name, run(b, tr, d, S - SPLIT, SPLIT))
+            b.close()
     return out
 
 
 def main(path, sd=None):
-    import conftest  # noqa: F401  (the import paths of the suite)
     sd = seed() if sd is None else sd
     out = {"seed": np.array(sd)}
     for T, storage in SHAPES:
@@ -149,5 +125,4 @@ def main(path, sd=None):
 
 
 if __name__ == "__main__":
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else None)

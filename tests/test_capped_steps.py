@@ -16,6 +16,7 @@ import pytest
 
 import oracle_py
 from conftest import has_gpu
+from roskfpos_amd import capi
 from roskfpos_amd.synth import Workload, anchors_xyz
 from test_random_traces import _Emu
 
@@ -40,7 +41,7 @@ def _baseline_run(make_kernel, T, S, seed, tag0, storage_real=np.float64):
         assert np.array_equal(so, sk), f"status words, epoch {s}"
         xo, _ = orc.get_state()
         d = np.abs(xo[:, :3] - xk[:, :3]).max(1)
-        capped = ((so >> 8) & 0xFF) == CAP
+        capped = capi.st_gain_iters(so) == CAP
         n_capped += int(capped.sum())
         worst_capped = max(worst_capped, float(d[capped].max(initial=0.0)))
         worst_other = max(worst_other, float(d[~capped].max(initial=0.0)))
@@ -135,7 +136,7 @@ def _rough_run(make_kernel, seed, A, T=64, S=40):
         assert np.isfinite(xo).all() and np.isfinite(xk).all()
         run_kernel = np.maximum(run_kernel, np.abs(xk[:, :3] - xo[:, :3]).max(1))
         run_sens = np.maximum(run_sens, np.abs(xs[:, :3] - xo[:, :3]).max(1))
-        n_capped += int((((so >> 8) & 0xFF) == CAP).sum())
+        n_capped += int((capi.st_gain_iters(so) == CAP).sum())
     # No tag and no step is left out. A capped step on a diverging iteration multiplies ANY difference by ~2.5 per trip,
     # 1e5 per step (measured, iterate by iterate, against the dense form): on these traces most tags end METRES away
     # from the oracle -- and so does the oracle itself when its real-valued inputs (errorEstimation, acceleration, dt)

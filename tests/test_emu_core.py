@@ -10,6 +10,7 @@ import pytest
 
 from cases import CASES, CASE_BY_NAME, drive, rms_and_max
 from impls import EmuImpl, EmuStaticImpl, EmuStaticLdsImpl, OracleImpl
+from roskfpos_amd import capi
 
 # Bar from BASELINE.json: <= 1e-6 m RMS. Everything except the one documented case sits near 1e-12.
 TOL_DEFAULT_RMS, TOL_DEFAULT_MAX = 1e-9, 1e-8
@@ -55,8 +56,8 @@ def test_iteration_counts_are_in_the_surveyed_range():
     # ~2.6 ML solves and ~2 gain iterations per step at 8 anchors (6-state)
     case = CASE_BY_NAME["toa6_A8_fixed"]
     _, _, st = drive(case, EmuImpl, record=True)
-    gain = (st >> 8) & 0xFF
-    ml = (st >> 16) & 0xFF
+    gain = capi.st_gain_iters(st)
+    ml = capi.st_ml_iters(st)
     assert 1.5 < gain[10:].mean() < 3.5 and 1.5 < ml[10:].mean() < 4.5
 
 

@@ -18,15 +18,16 @@ import functools
 import numpy as np
 import pytest
 
+import step_checks as steps
 from conftest import has_gpu
+from roskfpos_amd import capi
 from roskfpos_amd.synth import Workload
-from test_imu9_epoch_loop_gpu import _bank, _dts, _fused, _per_epoch, _same
 
 pytestmark = pytest.mark.gpu
 
 A, K = 8, 7
-FL_HAS_IMU = np.uint32(2)
-UPDATE_SKIPPED, FEW_RANGES, ML_INIT, NONFINITE = 0x01, 0x04, 0x08, 0x20
+UPDATE_SKIPPED, FEW_RANGES, ML_INIT, NONFINITE = (capi.ST_UPDATE_SKIPPED, capi.ST_FEW_RANGES, capi.ST_ML_INIT,
+                                                    capi.ST_NONFINITE)
 E9 = [0, 1, 2, 6, 7, 8]
 # (RMS, max) in metres against the oracle, status words compared: tests/test_gpu_parity.py
 TOL = {0: (1e-9, 1e-8, "words"), 2: (1e-9, 1e-8, "words"), 3: (1e-7, 1e-6, "flags"), 1: (5e-6, None, None)}
@@ -41,7 +42,7 @@ class Scenario:
         self.w = Workload(T, A)
         self.pre = {"started": 6, "nan_state": 6, "latched_replay": 1}.get(name, 0)
         self.S = self.pre + K
-        self.dts = _dts(self.S)
+        self.dts = steps.dts(self.S)
         self.init = name != "nan_starts"
         self.accel = name != "latched_replay"     # False: MODE_TOA epochs that re-fuse the latched sample
         self.r = np.stack([self.w.ranges_mm(s) for s in range(self.S)])
@@ -55,17 +56,12 @@ class Scenario:
             self.err[ZERO_ERR] = 0.0
 
     def trace(self, storage, dev):
-        import torch
-        real = np.float64 if storage == 0 else np.float32
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        w, S = self.w, self.S
-        return dict(r=up(self.r.transpose(0, 2, 1)), e=up(self.err.astype(real).T), c=up(w.accel_cov(real).T),
-                    a=up(np.stack([w.accel(s, real) for s in range(S)]).transpose(0, 2, 1)))
+        return steps.Trace(self.w, self.S, storage, dev, r=self.r, err=self.err)
 
     def edit(self, x, P, fl):
         if self.name == "latched_replay":
-            assert (fl & FL_HAS_IMU).all()
-            fl[self.bare] &= ~FL_HAS_IMU
+            assert (fl & steps.FL_HAS_IMU).all()
+            fl[self.bare] &= ~steps.FL_HAS_IMU
         if self.name == "nan_state":
             x[BAD, :3] = np.nan
         return x, P, fl
@@ -93,40 +89,34 @@ def _invertible(P, dt):
 def _oracle(name, T, f32):
     """the scenario on the CPU, once per (scenario, T, measurement width): poses [K][T][3] and status words [K][T] of
     the K epochs, and whether B was invertible at the head of each of them [K][T]"""
-    import oracle_py
-    sc = Scenario(name, T)
-    w = sc.w
-    real = np.float32 if f32 else np.float64
-    o = oracle_py.OracleBank(1, T, w.anchors, init_pos=w.init_positions() if sc.init else None, n_threads=8)
-    err, cov = sc.err.astype(real).astype(np.float64), w.accel_cov(real).astype(np.float64)
-    poses, stats, inv = [], [], []
-    for s in range(sc.S):
-        if s == sc.pre and sc.name == "nan_state":
+    sn = Scenario(name, T)
+    inv = []
+
+    def edit(o, s):
+        if s == sn.pre and name == "nan_state":
             x, P = o.get_state()
             x[BAD, :3] = np.nan
             o.set_state(x, P)
-        if s >= sc.pre:
-            inv.append(_invertible(o.get_state()[1], sc.dts[s]))
-        if s < sc.pre or sc.accel:
-            o.step_imu(w.accel(s, real).astype(np.float64), cov, 0.0)
-        st = o.step_toa(sc.r[s], err, sc.dts[s])
-        if s >= sc.pre:
-            poses.append(o.get_state()[0][:, :3].copy())
-            stats.append(st.copy())
-    return np.stack(poses), np.stack(stats), np.stack(inv)
+        if s >= sn.pre:
+            inv.append(_invertible(o.get_state()[1], sn.dts[s]))
+
+    poses, stats = steps.oracle_run(sn.w, sn.r, sn.err, sn.dts, real=np.float32 if f32 else np.float64,
+                                 init=sn.w.init_positions() if sn.init else None,
+                                 accel=[s < sn.pre or sn.accel for s in range(sn.S)], edit=edit)[:2]
+    return poses[sn.pre:], stats[sn.pre:], np.stack(inv)
 
 
 def _start(sc, tr, storage, chunk):
-    b = _bank(sc.w, sc.T, storage, chunk=chunk, init=sc.init)
+    b = steps.bank(sc.w, sc.T, storage, chunk=chunk, init=sc.init)
     if sc.pre:
-        _per_epoch(b, tr, sc.pre, sc.dts, sc.T)
+        steps.single_calls(b, tr, sc.dts, sc.pre, poses=False)
     b.set_state(*sc.edit(*b.get_state()))     # (every scenario goes through the same round trip)
     return b
 
 
 def _occurs(sc, st, poses, inv):
     """the scenario really happened: st = the kernel's status words of the K epochs [K][T], poses [K][3][T]"""
-    T, fl, name = sc.T, st & 0xFF, sc.name
+    T, fl, name = sc.T, capi.st_flags(st), sc.name
     if name == "started":
         assert (fl == 0).all() and np.isfinite(poses).all()
     elif name == "nan_starts":
@@ -164,44 +154,44 @@ def test_one_launch_equals_three_plus_four_equals_seven_and_the_oracle(T, storag
 
     # seven launches of one epoch through the single-epoch entry points: the status words of every epoch
     b = _start(sc, tr, storage, None)
-    ref = _per_epoch(b, tr, K, dts, T, accel=sc.accel, s0=s0)
+    ref = steps.single_calls(b, tr, dts, K, s0, sc.accel, poses=False)
     if name == "err_zero":
-        assert not np.array_equal(ref[3][ZERO_ERR], np.zeros((9, 9)))     # its covariance is predicted all the same
+        assert not np.array_equal(ref.P[ZERO_ERR], np.zeros((9, 9)))     # its covariance is predicted all the same
     b.close()
     # ... and through the trace entry point, which also writes the poses
     b = _start(sc, tr, storage, 1)
-    single = _fused(b, tr, K, dts, T, A, accel=sc.accel, s0=s0)
+    single = steps.fused(b, tr, dts, K, s0, sc.accel)
     b.close()
-    _same(single, (single[0], ref[1][-1]) + ref[2:], "seven launches of one epoch")
+    steps.same(single, ref.last(single.poses), "seven launches of one epoch")
     # one launch of seven
     b = _start(sc, tr, storage, 25)
-    one = _fused(b, tr, K, dts, T, A, accel=sc.accel, s0=s0)
+    one = steps.fused(b, tr, dts, K, s0, sc.accel)
     b.close()
-    _same(one, single, "one launch of seven epochs")
+    steps.same(one, single, "one launch of seven epochs")
     # 3 + 4
     b = _start(sc, tr, storage, 25)
-    first = _fused(b, tr, 3, dts, T, A, accel=sc.accel, s0=s0)
-    assert np.array_equal(first[1], ref[1][2]), "status words after three epochs"
-    second = _fused(b, tr, 4, dts, T, A, accel=sc.accel, s0=s0 + 3)
+    first = steps.fused(b, tr, dts, 3, s0, sc.accel)
+    assert np.array_equal(first.status, ref.status[2]), "status words after three epochs"
+    second = steps.fused(b, tr, dts, 4, s0 + 3, sc.accel)
     b.close()
-    _same((np.concatenate([first[0], second[0]]),) + second[1:], single, "launches of three and four epochs")
+    steps.same(second._replace(poses=np.concatenate([first.poses, second.poses])), single,
+               "launches of three and four epochs")
 
     poses_o, stats_o, inv = _oracle(name, T, storage != 0)
-    _occurs(sc, ref[1], single[0], inv)
+    _occurs(sc, ref.status, single.poses, inv)
     if name == "nan_state":      # its bytes do not reach anybody else: the same run without it
         plain = Scenario("started", T)
         b = _start(plain, tr, storage, 25)
-        clean = _fused(b, tr, K, dts, T, A, s0=s0)
+        clean = steps.fused(b, tr, dts, K, s0)
         b.close()
         keep = np.arange(T) != BAD
-        _same((one[0][:, :, keep],) + tuple(v[keep] for v in one[1:]),
-              (clean[0][:, :, keep],) + tuple(v[keep] for v in clean[1:]), "the tags next to the NaN one")
-        assert one[1][BAD] & NONFINITE
+        steps.same(one.only(keep), clean.only(keep), "the tags next to the NaN one")
+        assert one.status[BAD] & NONFINITE
 
     # the oracle: the poses of the K epochs (latched_replay: the oracle has a sample on every tag -- the latched ones)
     rms_bar, max_bar, words = TOL[storage]
     keep = ~sc.bare & ((np.arange(T) != BAD) | (name != "nan_state"))
-    got, want = single[0].transpose(0, 2, 1)[:, keep], poses_o[:, keep]
+    got, want = single.poses.transpose(0, 2, 1)[:, keep], poses_o[:, keep]
     assert np.array_equal(np.isnan(got), np.isnan(want))
     d = np.nan_to_num(got - want)
     n = max(1, int(np.isfinite(want).all(axis=2).sum()))
@@ -209,6 +199,6 @@ def test_one_launch_equals_three_plus_four_equals_seven_and_the_oracle(T, storag
     print(f"{name} T={T} storage={storage}: {rms:.3e} m RMS, {mx:.3e} m max against the oracle over {K} epochs")
     assert rms <= rms_bar and (max_bar is None or mx <= max_bar), (rms, mx)
     if words == "words":
-        assert np.array_equal(ref[1][:, keep], stats_o[:, keep])
+        assert np.array_equal(ref.status[:, keep], stats_o[:, keep])
     elif words == "flags":
-        assert np.array_equal(ref[1][:, keep] & 0xFF, stats_o[:, keep] & 0xFF)
+        assert np.array_equal(capi.st_flags(ref.status[:, keep]), capi.st_flags(stats_o[:, keep]))

@@ -6,27 +6,19 @@ one iterating lane asks for it. Every comparison here is bit for bit -- the pose
 words and latch -- except the last test, which holds the fused launch against the oracle.
 
 T = 37 is one ragged wavefront, T = 128 two full ones; storage 2 = mixed (the bench configuration), 3 = p48."""
+import functools
+
 import numpy as np
 import pytest
 
+import step_checks as sc
 from conftest import has_gpu
+from roskfpos_amd import capi
 from roskfpos_amd.synth import Workload
-from test_imu9_epoch_loop_gpu import _bank, _dts, _fused, _per_epoch, _same, _trace
 
 pytestmark = pytest.mark.gpu
 
 A = 8
-FL_HAS_IMU = np.uint32(2)
-ST_NONFINITE = 0x20
-
-
-def _gain_iters(status):
-    return (np.asarray(status).astype(np.uint32) >> 8) & 0xFF
-
-
-def _only(out, keep):
-    """the rows of a (trajectory, status, x, P, flags, latch) tuple that belong to the tags in `keep`"""
-    return (out[0][:, :, keep], out[1][keep], out[2][keep], out[3][keep], out[4][keep], out[5][keep])
 
 
 @pytest.mark.parametrize("storage", [2, 3])
@@ -37,56 +29,59 @@ def test_a_wavefront_in_which_only_some_lanes_hold_a_sample(T, storage):
         pytest.skip("no GPU")
     S = 8
     w = Workload(T, A)
-    dts = _dts(S)
-    tr = _trace(w, S, storage, "cuda:0")
+    dts = sc.dts(S)
+    tr = sc.Trace(w, S, storage, gaps=True)
     bare = np.arange(T) % 3 == 1
 
     def bank(partly, chunk=None, diag=None):
-        b = _bank(w, T, storage, chunk=chunk, diag=diag)
-        _per_epoch(b, tr, 1, dts, T)      # one fused epoch: every tag latches its sample
+        b = sc.bank(w, T, storage, chunk=chunk, diag=diag)
+        sc.single_calls(b, tr, dts, 1, poses=False)      # one fused epoch: every tag latches its sample
         x, P, fl = b.get_state()
-        assert (fl & FL_HAS_IMU).all()
+        assert (fl & sc.FL_HAS_IMU).all()
         if partly:
-            fl[bare] &= ~FL_HAS_IMU
+            fl[bare] &= ~sc.FL_HAS_IMU
         b.set_state(x, P, fl)             # (both kinds of bank go through the same round trip)
         return b
 
     b = bank(True)
-    ref = _per_epoch(b, tr, S - 1, dts, T, accel=False, s0=1)
+    ref = sc.single_calls(b, tr, dts, S - 1, s0=1, accel=False, poses=False)
     b.close()
     out = {}
     for name, partly, chunk, diag in (("launch per epoch", True, 1, None), ("fused", True, 25, None),
                                       ("fused, full form", True, 25, 0), ("everybody latched", False, 25, None)):
         b = bank(partly, chunk=chunk, diag=diag)
-        out[name] = _fused(b, tr, S - 1, dts, T, A, accel=False, s0=1)
+        out[name] = sc.fused(b, tr, dts, S - 1, s0=1, accel=False)
         b.close()
-    poses = out["launch per epoch"][0]
+    poses = out["launch per epoch"].poses
     for name in ("launch per epoch", "fused", "fused, full form"):
-        _same(out[name], (poses, ref[1][-1]) + ref[2:], name)
-    assert not (out["fused"][4][bare] & FL_HAS_IMU).any() and (out["fused"][4][~bare] & FL_HAS_IMU).all()
+        sc.same(out[name], ref.last(poses), name)
+    fl = out["fused"].flags
+    assert not (fl[bare] & sc.FL_HAS_IMU).any() and (fl[~bare] & sc.FL_HAS_IMU).all()
     # the same bank with a sample on every lane takes the fast form: the lanes the two share cannot tell
-    _same(_only(out["everybody latched"], ~bare), _only(out["fused"], ~bare), "latched lanes, fast against per-lane form")
-    assert not np.array_equal(out["everybody latched"][2][bare], out["fused"][2][bare])   # (the sample does reach the filter)
+    sc.same(out["everybody latched"].only(~bare), out["fused"].only(~bare), "latched lanes, fast against per-lane form")
+    assert not np.array_equal(out["everybody latched"].x[bare], out["fused"].x[bare])   # (the sample does reach the filter)
+
+
+def _mixed(g, T):
+    """g: [S][T] gain iterations -> the (epoch, wavefront) pairs with a capped step (20) next to one that converged within 3"""
+    return [(s, wv) for s in range(len(g)) for wv in range((T + 63) // 64)
+            if (g[s, 64 * wv:64 * (wv + 1)] == 20).any() and (g[s, 64 * wv:64 * (wv + 1)] <= 3).any()]
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_mixed(T, S, seed):
+    w = Workload(T, A, seed=seed)
+    r = sc.Trace(w, S, 2, "cpu", gaps=True).r_host
+    return _mixed(capi.st_gain_iters(sc.oracle_run(w, r, w.err_est(), sc.dts(S), real=np.float32,
+                                                   init=w.init_positions())[1]), T)
 
 
 def _seed_with_mixed_trip_counts(T, S):
     """the first workload seed for which the oracle sees a wavefront and an epoch with a capped step (20 gain iterations)
     next to one that converged within three -> (seed, epoch, wavefront)"""
-    import oracle_py
-    for seed in range(1, 9):
-        w = Workload(T, A, seed=seed)
-        tr = _trace(w, S, 2, "cpu")
-        o = oracle_py.OracleBank(1, T, w.anchors, init_pos=w.init_positions(), n_threads=8)
-        err, cov = w.err_est(np.float32).astype(np.float64), tr["cov_host"].astype(np.float64)
-        dts = _dts(S)
-        for s in range(S):
-            o.step_imu(w.accel(s, np.float32).astype(np.float64), cov, 0.0)
-            g = _gain_iters(o.step_toa(tr["r_host"][s], err, dts[s]))
-            for wv in range((T + 63) // 64):
-                lanes = g[64 * wv:64 * (wv + 1)]
-                if (lanes == 20).any() and (lanes <= 3).any():
-                    return seed, s, wv
-    return None
+    seed = sc.first_seed(range(1, 9), lambda sd: _oracle_mixed(T, S, sd),
+                         "a capped and a quickly converged step in one wavefront")
+    return (seed,) + _oracle_mixed(T, S, seed)[0]
 
 
 @pytest.mark.parametrize("storage", [2, 3])
@@ -95,28 +90,24 @@ def test_lanes_of_one_wavefront_that_leave_the_loop_at_different_trips(T, storag
     if not has_gpu():
         pytest.skip("no GPU")
     S = 12
-    found = _seed_with_mixed_trip_counts(T, S)
-    assert found is not None, "no seed with a capped and a quickly converged step in one wavefront"
-    seed = found[0]
+    seed, epoch, wavefront = _seed_with_mixed_trip_counts(T, S)
     w = Workload(T, A, seed=seed)
-    dts = _dts(S)
-    tr = _trace(w, S, storage, "cuda:0")
-    b = _bank(w, T, storage)
-    ref = _per_epoch(b, tr, S, dts, T)
+    dts = sc.dts(S)
+    tr = sc.Trace(w, S, storage, gaps=True)
+    b = sc.bank(w, T, storage)
+    ref = sc.single_calls(b, tr, dts, S, poses=False)
     b.close()
-    g = _gain_iters(ref[1])
-    mixed = [(s, wv) for s in range(S) for wv in range((T + 63) // 64)
-             if (g[s, 64 * wv:64 * (wv + 1)] == 20).any() and (g[s, 64 * wv:64 * (wv + 1)] <= 3).any()]
-    print(f"T={T} storage={storage}: seed {seed} (oracle: epoch {found[1]}, wavefront {found[2]}); "
+    mixed = _mixed(capi.st_gain_iters(ref.status), T)
+    print(f"T={T} storage={storage}: seed {seed} (oracle: epoch {epoch}, wavefront {wavefront}); "
           f"the kernel: {len(mixed)} (epoch, wavefront) pairs with gain_iters == 20 next to <= 3")
     assert mixed, "the exit masks were not exercised"
     poses = None
     for chunk in (1, 5, 25):
-        b = _bank(w, T, storage, chunk=chunk)
-        got = _fused(b, tr, S, dts, T, A)
+        b = sc.bank(w, T, storage, chunk=chunk)
+        got = sc.fused(b, tr, dts, S)
         b.close()
-        poses = got[0] if poses is None else poses
-        _same(got, (poses, ref[1][-1]) + ref[2:], f"chunk {chunk}")
+        poses = got.poses if poses is None else poses
+        sc.same(got, ref.last(poses), f"chunk {chunk}")
 
 
 @pytest.mark.parametrize("storage", [2, 3])
@@ -127,23 +118,24 @@ def test_a_non_finite_wave_mate_changes_nobody_else(T, storage):
         pytest.skip("no GPU")
     S, S0, bad = 12, 6, 5
     w = Workload(T, A)
-    dts = _dts(S)
-    tr = _trace(w, S, storage, "cuda:0")
+    dts = sc.dts(S)
+    tr = sc.Trace(w, S, storage, gaps=True)
     out = {}
     for name in ("plain", "with it"):
-        b = _bank(w, T, storage, chunk=25)
-        _fused(b, tr, S0, dts, T, A)      # past the fixed start: the covariance is invertible, the information form runs
+        b = sc.bank(w, T, storage, chunk=25)
+        sc.fused(b, tr, dts, S0)      # past the fixed start: the covariance is invertible, the information form runs
         x, P, fl = b.get_state()
         if name == "with it":
             x[bad, :3] = np.nan
         b.set_state(x, P, fl)
-        out[name] = _fused(b, tr, S - S0, dts, T, A, s0=S0)
+        out[name] = sc.fused(b, tr, dts, S - S0, s0=S0)
         b.close()
     others = np.arange(T) != bad
-    assert out["with it"][1][bad] & ST_NONFINITE and np.isnan(out["with it"][0][:, :, bad]).all()
-    assert np.isfinite(out["plain"][0]).all() and not (out["plain"][1] & ST_NONFINITE).any()
-    assert (_gain_iters(out["plain"][1][:64]) < 20).any()     # (its wave-mates do leave the loop while it iterates)
-    _same(_only(out["with it"], others), _only(out["plain"], others), "the other tags")
+    plain, with_it = out["plain"], out["with it"]
+    assert with_it.status[bad] & capi.ST_NONFINITE and np.isnan(with_it.poses[:, :, bad]).all()
+    assert np.isfinite(plain.poses).all() and not (plain.status & capi.ST_NONFINITE).any()
+    assert (capi.st_gain_iters(plain.status[:64]) < 20).any()     # (its wave-mates do leave the loop while it iterates)
+    sc.same(with_it.only(others), plain.only(others), "the other tags")
 
 
 @pytest.mark.parametrize("T", [37, 128])
@@ -152,21 +144,14 @@ def test_fused_launches_match_the_oracle(T):
     oracle does not round its covariance the way p48 does)"""
     if not has_gpu():
         pytest.skip("no GPU")
-    import oracle_py
-    from roskfpos_amd import capi
     S, storage = 40, capi.STORE_MIXED
     w = Workload(T, A)
-    dts = _dts(S)
-    tr = _trace(w, S, storage, "cuda:0")
-    b = _bank(w, T, storage)
-    got = _fused(b, tr, S, dts, T, A)
+    dts = sc.dts(S)
+    tr = sc.Trace(w, S, storage, gaps=True)
+    b = sc.bank(w, T, storage)
+    got = sc.fused(b, tr, dts, S)
     b.close()
-    o = oracle_py.OracleBank(1, T, w.anchors, init_pos=w.init_positions(), n_threads=8)
-    err, cov = w.err_est(np.float32).astype(np.float64), tr["cov_host"].astype(np.float64)
-    for s in range(S):
-        o.step_imu(w.accel(s, np.float32).astype(np.float64), cov, 0.0)
-        o.step_toa(tr["r_host"][s], err, dts[s])
-    xo, _ = o.get_state()
-    rms = float(np.sqrt(((got[2][:, :3] - xo[:, :3]) ** 2).sum(1).mean()))
+    xo = sc.oracle_run(w, tr.r_host, w.err_est(), dts, real=np.float32, init=w.init_positions())[2]
+    rms = float(np.sqrt(((got.x[:, :3] - xo[:, :3]) ** 2).sum(1).mean()))
     print(f"T={T}: RMS position difference vs oracle over {S} epochs with a dt per epoch: {rms:.3e} m")
     assert rms <= 1e-6, rms

@@ -16,34 +16,28 @@ words; p48 <= 1e-7 m / 1e-6 m, equal flags)."""
 import numpy as np
 import pytest
 
+import ml_seed_cases as mc
+import step_checks as sc
 import weights_selects as ws
 from conftest import has_gpu
-from test_imu9_epoch_loop_gpu import _dts, _fused
-from test_pairs9_tail_gpu import _bank, _fused_split, _same_bits, _single_calls
+from roskfpos_amd import capi
 
 pytestmark = pytest.mark.gpu
 
 A, S = ws.A, ws.S
 
 
-def _trace(w, r, err, dev):
-    import torch
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    cov = w.accel_cov(np.float32)
-    return dict(r=up(r.transpose(0, 2, 1)), e=up(err.astype(np.float32).T), c=up(cov.T),
-                a=up(np.stack([w.accel(s, np.float32) for s in range(S)]).transpose(0, 2, 1)), r_host=r, cov_host=cov)
-
-
 def _runs(w, T, storage, tr, dts, pairs):
+    """pairs: the default (KFPOS_PAIR9 unset) or KFPOS_PAIR9=0"""
     out = {}
     for run in ("single calls", "one launch", "3 + 4"):
-        b = _bank(w, T, storage, pairs, chunk=25)
+        b = sc.bank(w, T, storage, pairs=sc.UNSET if pairs else 0, chunk=25)
         if run == "single calls":
-            out[run] = _single_calls(b, tr, dts, T, n=S)
+            out[run] = sc.single_calls(b, tr, dts, S)
         elif run == "one launch":
-            out[run] = _fused(b, tr, S, dts, T, A)
+            out[run] = sc.fused(b, tr, dts, S)
         else:
-            out[run] = _fused_split(b, tr, dts, T, split=(3, 4))
+            out[run] = sc.fused_split(b, tr, dts, S, split=3)
         b.close()
     return out
 
@@ -53,45 +47,37 @@ def _runs(w, T, storage, tr, dts, pairs):
 def test_every_side_of_the_selects_same_bits_however_launched_and_within_the_oracle_bounds(T, storage):
     if not has_gpu():
         pytest.skip("no GPU")
-    import oracle_py
-    w, r, err = ws.inputs(T, np.float32)
-    dts = _dts(S)
-    tr = _trace(w, r, err, "cuda:0")
+    w, init, r, err = mc.inputs(T, np.float32, **ws.INPUTS)
+    dts = sc.dts(S)
+    tr = sc.Trace(w, S, storage, r=r, err=err)
     with_pairs, without = _runs(w, T, storage, tr, dts, True), _runs(w, T, storage, tr, dts, False)
     single = with_pairs["single calls"]
-    ws.assert_inputs_reach_the_branches(1, w, r, err, single[1], np.float32, dts)
-    as_fused = (single[0], single[1][-1]) + single[2:]
+    ws.assert_inputs_reach_the_branches(1, w, r, err, single.status, np.float32, dts)
     for run in ("one launch", "3 + 4"):
-        _same_bits(with_pairs[run], as_fused, (T, storage, run, "against single calls"))
-        _same_bits(without[run], with_pairs[run], (T, storage, run, "KFPOS_PAIR9=0 against the default"))
-    _same_bits(without["single calls"], single, (T, storage, "single calls, KFPOS_PAIR9=0 against the default"))
+        sc.same(with_pairs[run], single.last(), (T, storage, run, "against single calls"))
+        sc.same(without[run], with_pairs[run], (T, storage, run, "KFPOS_PAIR9=0 against the default"))
+    sc.same(without["single calls"], single, (T, storage, "single calls, KFPOS_PAIR9=0 against the default"))
 
     # a garbage slot changes nobody's bytes
     clean = err.copy()
     for lane in ws.GARBAGE:
         clean[lane, 1] = np.float32(w.err_est()[lane, 1])
-    b = _bank(w, T, storage, True, chunk=25)
-    _same_bits(_fused(b, _trace(w, r, clean, "cuda:0"), S, dts, T, A), with_pairs["one launch"],
-               (T, storage, "garbage slots against ordinary values"))
+    b = sc.bank(w, T, storage, chunk=25)
+    sc.same(sc.fused(b, sc.Trace(w, S, storage, r=r, err=clean), dts, S), with_pairs["one launch"],
+            (T, storage, "garbage slots against ordinary values"))
     b.close()
 
-    o = oracle_py.OracleBank(1, T, w.anchors, init_pos=w.init_positions(), n_threads=8)
-    cov = tr["cov_host"].astype(np.float64)
-    poses, stats = [], []
-    for s in range(S):
-        o.step_imu(w.accel(s, np.float32).astype(np.float64), cov, 0.0)
-        stats.append(np.asarray(o.step_toa(r[s], err, dts[s])).astype(np.uint32))
-        poses.append(o.get_state()[0][:, :3].T.copy())
-    poses, theirs, mine = np.stack(poses), np.stack(stats), single[1].astype(np.uint32)
+    poses, theirs = sc.oracle_run(w, r, err, dts, real=np.float32, init=init)[:2]
+    poses, mine = poses.transpose(0, 2, 1), single.status.astype(np.uint32)
     ok = np.isfinite(poses).all(1)
-    assert np.array_equal(ok, np.isfinite(single[0]).all(1))
-    d = np.sqrt((((single[0] - poses) ** 2).sum(1))[ok])
+    assert np.array_equal(ok, np.isfinite(single.poses).all(1))
+    d = np.sqrt((((single.poses - poses) ** 2).sum(1))[ok])
     rms, mx = float(np.sqrt((d ** 2).mean())), float(d.max())
     print(f"T={T} storage={storage}: RMS {rms:.3e} m, max {mx:.3e} m against the oracle over {S} epochs")
-    cmp = ws.oracle_status_comparable(1, T)
+    cmp = mc.oracle_status_comparable(1, T, exact_fit=False)
     if storage == 2:
         assert rms <= 1e-9 and mx <= 1e-8, (rms, mx)
-        assert np.array_equal(mine[:, cmp], theirs[:, cmp])
+        assert np.array_equal(mine[cmp], theirs[cmp])
     else:
         assert rms <= 1e-7 and mx <= 1e-6, (rms, mx)
-        assert np.array_equal(mine[:, cmp] & 0xFF, theirs[:, cmp] & 0xFF)
+        assert np.array_equal(capi.st_flags(mine[cmp]), capi.st_flags(theirs[cmp]))

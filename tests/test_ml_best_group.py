@@ -14,6 +14,7 @@ import pytest
 
 import oracle_py
 from conftest import has_gpu
+from roskfpos_amd import capi
 from roskfpos_amd.synth import Workload, anchors_xyz
 
 BEST = 2
@@ -54,9 +55,9 @@ def test_oracle_best_group_is_the_argmin_over_four_subsets():
                     win = i
             assert np.array_equal(pb[t], res[win][1]) and np.allclose(cb[t], res[win][2], rtol=1e-13, atol=0)
             left_out = -1 if len(present) == 4 else (4, 3, 2, 1, 0)[win]
-            assert ((int(st[t]) >> 24) & 0xFF) - 1 == left_out
-            assert (st[t] >> 16) & 0xFF == min(res[win][3], 255)
-            assert (st[t] >> 8) & 0xFF == min(max(x[3] for x in res), 255)
+            assert capi.st_ignored(st[t]) == left_out
+            assert capi.st_ml_iters(st[t]) == min(res[win][3], 255)
+            assert capi.st_gain_iters(st[t]) == min(max(x[3] for x in res), 255)
 
 
 def test_oracle_tie_goes_to_the_later_group_and_six_ranges_are_refused():
@@ -77,7 +78,7 @@ def test_oracle_tie_goes_to_the_later_group_and_six_ranges_are_refused():
     assert traces[0] == traces[1] == min(traces) and traces[2] > traces[0]
     b = oracle_py.OracleBank(oracle_py.MODEL_ML, 1, anc, init_pos=seed, ml_variant=BEST)
     st = b.step_toa(r, err, 0.05)
-    assert ((int(st[0]) >> 24) & 0xFF) - 1 == 3          # "without range 3": the later of the tied pair
+    assert capi.st_ignored(st[0]) == 3          # "without range 3": the later of the tied pair
     six = oracle_py.OracleBank(oracle_py.MODEL_ML, 2, anchors_xyz(6), init_pos=np.ones((2, 3)), ml_variant=BEST)
     st = six.step_toa(Workload(2, 6).ranges_mm(0), np.full((2, 6), 0.0025), 0.05)
     assert np.all(st & 1)       # undefined in the reference: reported, nothing estimated
@@ -85,7 +86,7 @@ def test_oracle_tie_goes_to_the_later_group_and_six_ranges_are_refused():
 
 def _judge(sk, so, pk, po, ck, co):
     assert np.array_equal(sk & 0xFF, so & 0xFF)
-    passes = ((so >> 8) & 0xFF).astype(int)          # the most passes any group of the tag took
+    passes = capi.st_gain_iters(so).astype(int)          # the most passes any group of the tag took
     few = (so & 4) != 0
     tame = passes <= 15
     assert np.array_equal(sk[tame], so[tame])        # winner, its passes, the most passes: identical
@@ -132,7 +133,7 @@ def test_kernel_body_resolves_the_exact_tie_like_the_reference():
         L.kfe_set_ml_variant(h, BEST)
         se = np.zeros(1, dtype=np.uint32)
         L.kfe_step_toa(h, np.ascontiguousarray(r), np.full((1, 5), 0.0025), np.array([0.05]), 1, se.ctypes.data)
-        assert ((int(se[0]) >> 24) & 0xFF) - 1 == 3
+        assert capi.st_ignored(se[0]) == 3
         L.kfe_destroy(h)
 
 

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import oracle_py
+from roskfpos_amd import capi
 from roskfpos_amd.synth import Workload
 
 
@@ -46,7 +47,7 @@ def _judge_epoch(sk, so, pk, po, ck, co, f32_inputs=False):
       > 30       : a chaotic walk through the interior anchors; two correct implementations end metres apart and
                    take different pass counts. Only finiteness is compared. Returns the number of such tags."""
     assert np.array_equal(sk & 0xFF, so & 0xFF)                       # flags: few ranges, skipped, ...
-    passes = np.maximum((so >> 16) & 0xFF, (so >> 8) & 0xFF).astype(int)
+    passes = np.maximum(capi.st_ml_iters(so), capi.st_gain_iters(so)).astype(int)
     few = (so & 4) != 0
     tame, middle, wild = passes <= 15, (passes > 15) & (passes <= 30), passes > 30
     same = (sk >> 8) == (so >> 8)

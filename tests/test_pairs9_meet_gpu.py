@@ -23,13 +23,13 @@ import numpy as np
 import pytest
 
 import pairs9_meet_cases as pm
+import step_checks as sc
 from conftest import has_gpu
+from roskfpos_amd import capi
+from roskfpos_amd.capi import ST_FEW_RANGES, ST_NONFINITE
 
 pytestmark = pytest.mark.gpu
 
-PARTS = ("poses", "status", "x", "P", "flags", "latch")
-ST_FEW_RANGES = 0x04
-ST_NONFINITE = 0x20
 CHILD_LIMIT = 240   # seconds for the five children together; they take about ten
 
 
@@ -60,19 +60,14 @@ def _results():
         return res
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+def _run(setting, T, storage, run):
+    res = _results()[setting]
+    return sc.Run(*(res[f"{T}/{storage}/{run}/{part}"] for part in sc.Run._fields))
 
 
-def _same_bytes(T, storage, run, parts=PARTS):
-    res = _results()
-    ref = res["no pairs"]
+def _same_bytes(T, storage, run):
     for setting in pm.SETTINGS:
-        for part in parts:
-            key = f"{T}/{storage}/{run}/{part}"
-            got, want = res[setting][key], ref[key]
-            assert got.shape == want.shape and got.dtype == want.dtype, (setting, key)
-            assert np.array_equal(_bits(got), _bits(want)), (setting, key)
+        sc.same(_run(setting, T, storage, run), _run("no pairs", T, storage, run), (setting, T, storage, run))
 
 
 @pytest.mark.parametrize("T,storage", pm.SHAPES)
@@ -98,13 +93,9 @@ def test_every_schedule_leaves_the_same_bytes_and_every_meeting_scenario_occurs(
     for run in ("one launch", "5 + 7", "single calls"):
         _same_bytes(T, storage, run)
     # ... and the three ways of running the epochs agree with each other (status: a launch reports its last epoch's)
-    one, split, single = (res["default"], f"{T}/{storage}/one launch/"), (res["default"], f"{T}/{storage}/5 + 7/"), \
-        (res["default"], f"{T}/{storage}/single calls/")
-    for part in PARTS:
-        a, b, c = one[0][one[1] + part], split[0][split[1] + part], single[0][single[1] + part]
-        if part == "status":
-            c = c[-1]
-        assert np.array_equal(_bits(a), _bits(b)) and np.array_equal(_bits(a), _bits(c)), part
+    one = _run("default", T, storage, "one launch")
+    sc.same(one, _run("default", T, storage, "5 + 7"), "one launch against 5 + 7")
+    sc.same(one, _run("default", T, storage, "single calls").last(), "one launch against single calls")
 
 
 @pytest.mark.parametrize("storage", [2, 3])
@@ -148,4 +139,4 @@ def test_the_default_schedule_matches_the_oracle(storage):
         assert np.array_equal(mine, theirs)
     else:
         assert rms <= 1e-7 and mx <= 1e-6, (rms, mx)
-        assert np.array_equal(mine & 0xFF, theirs & 0xFF)
+        assert np.array_equal(capi.st_flags(mine), capi.st_flags(theirs))

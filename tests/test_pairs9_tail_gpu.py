@@ -20,22 +20,16 @@ import functools
 import numpy as np
 import pytest
 
+import step_checks as sc
 from conftest import has_gpu
-from replay_checks import env
+from roskfpos_amd import capi
+from roskfpos_amd.capi import st_gain_iters as _gain_iters
 from roskfpos_amd.synth import Workload
-from test_imu9_epoch_loop_gpu import _dts, _fused, _per_epoch, _trace
 
 pytestmark = pytest.mark.gpu
 
 A, S = 8, 30
-SPLIT = (7, 23)
-FL_HAS_IMU = np.uint32(2)
-ST_FEW_RANGES = 0x04
-ST_NONFINITE = 0x20
-
-
-def _gain_iters(status):
-    return (np.asarray(status).astype(np.uint32) >> 8) & 0xFF
+SPLIT = 7          # fused launches of 7 epochs and the rest
 
 
 def _scenarios(g):
@@ -57,66 +51,20 @@ def _scenarios(g):
 def _seed():
     """the first workload seed for which the ORACLE sees every scenario in the first wavefront (tags 0 .. 63: a tag's
     trace does not depend on how many tags the workload has, so the seed serves every shape)"""
-    import oracle_py
-    for seed in range(1, 9):
+    def occurs(seed):
         w = Workload(64, A, seed=seed)
-        tr = _trace(w, S, 2, "cpu")
-        o = oracle_py.OracleBank(1, 64, w.anchors, init_pos=w.init_positions(), n_threads=8)
-        err, cov = w.err_est(np.float32).astype(np.float64), tr["cov_host"].astype(np.float64)
-        dts = _dts(S)
-        g = []
-        for s in range(S):
-            o.step_imu(w.accel(s, np.float32).astype(np.float64), cov, 0.0)
-            g.append(_gain_iters(o.step_toa(tr["r_host"][s], err, dts[s])))
-        if all(len(v) for v in _scenarios(np.stack(g)).values()):
-            return seed
-    raise AssertionError("no seed in 1 .. 8 for which the oracle sees every pair scenario in one wavefront")
+        r = sc.Trace(w, S, 2, "cpu", gaps=True).r_host
+        st = sc.oracle_run(w, r, w.err_est(), sc.dts(S), real=np.float32, init=w.init_positions())[1]
+        return all(len(v) for v in _scenarios(_gain_iters(st)).values())
+    return sc.first_seed(range(1, 9), occurs, "every pair scenario in one wavefront")
 
 
-def _bank(w, T, storage, pairs, chunk=None, diag=None):
-    from roskfpos_amd import capi
-    with env(KFPOS_PAIR9=None if pairs else 0, KFPOS_TRACE_CHUNK_STEPS=chunk, KFPOS_IMU9_DIAG=diag):   # None: unset
-        return capi.KfposBank(capi.MODEL_TOA_IMU, T, w.anchors, storage=storage, init_pos=w.init_positions())
+def _bank(w, T, storage, pairs, **kw):
+    """pairs: the default (KFPOS_PAIR9 unset) or KFPOS_PAIR9=0"""
+    return sc.bank(w, T, storage, pairs=sc.UNSET if pairs else 0, **kw)
 
 
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint8).reshape(-1)
-
-
-def _same_bits(got, ref, what):
-    for k, name in enumerate(("pose of every epoch", "status", "x", "P", "flags", "latch")):
-        if got[k] is None and ref[k] is None:
-            continue
-        assert got[k].shape == ref[k].shape and got[k].dtype == ref[k].dtype, (what, name)
-        assert np.array_equal(_bits(got[k]), _bits(ref[k])), (what, name)
-
-
-def _single_calls(b, tr, dts, T, accel=True, s0=0, n=S):
-    """n single-epoch calls with the pose read after each -> (poses, status of every epoch, x, P, flags, latch)"""
-    import torch
-    st = torch.zeros(T, dtype=torch.int32, device=tr["r"].device)
-    stream = torch.cuda.current_stream().cuda_stream
-    poses, stats = [], []
-    for s in range(s0, s0 + n):
-        if accel:
-            b.step_toa_imu_dev(tr["r"][s], tr["e"], tr["a"][s], tr["c"], dts[s], status=st, stream=stream)
-        else:
-            b.step_toa_dev(tr["r"][s], tr["e"], dts[s], status=st, stream=stream)
-        stats.append(st.cpu().numpy().copy())
-        poses.append(b.get_state()[0][:, :3].T.copy())
-    x, P, fl = b.get_state()
-    return (np.stack(poses), np.stack(stats), x, P, fl, b.get_latch())
-
-
-def _fused_split(b, tr, dts, T, accel=True, s0=0, split=SPLIT):
-    """the same epochs as fused launches of split[0] + split[1] -> (poses, last status, x, P, flags, latch)"""
-    first = _fused(b, tr, split[0], dts, T, A, accel=accel, s0=s0)
-    second = _fused(b, tr, split[1], dts, T, A, accel=accel, s0=s0 + split[0])
-    return (np.concatenate([first[0], second[0]]),) + second[1:]
-
-
-def _both_ways(w, T, storage, tr, dts, prepare=None, accel=True, s0=0, n=S, split=SPLIT, diag=None):
+def _both_ways(w, T, storage, tr, dts, prepare=None, accel=True, s0=0, n=S, diag=None):
     """{(pairs, run): result}: the four banks of a comparison. prepare(bank) brings a fresh bank to its starting state."""
     out = {}
     for pairs in (False, True):
@@ -124,17 +72,16 @@ def _both_ways(w, T, storage, tr, dts, prepare=None, accel=True, s0=0, n=S, spli
             b = _bank(w, T, storage, pairs, chunk=25, diag=diag)
             if prepare:
                 prepare(b)
-            out[pairs, run] = (_single_calls(b, tr, dts, T, accel, s0, n) if run == "single calls"
-                               else _fused_split(b, tr, dts, T, accel, s0, split))
+            out[pairs, run] = (sc.single_calls(b, tr, dts, n, s0, accel) if run == "single calls"
+                               else sc.fused_split(b, tr, dts, n, s0, accel, split=SPLIT))
             b.close()
     return out
 
 
 def _check_invisible(out, what):
-    _same_bits(out[True, "single calls"], out[False, "single calls"], (what, "single calls, pairs against none"))
-    _same_bits(out[True, "fused"], out[False, "fused"], (what, "fused launches, pairs against none"))
-    single, fused = out[True, "single calls"], out[True, "fused"]
-    _same_bits(fused, (single[0], single[1][-1]) + single[2:], (what, "pairs: fused against single calls"))
+    sc.same(out[True, "single calls"], out[False, "single calls"], (what, "single calls, pairs against none"))
+    sc.same(out[True, "fused"], out[False, "fused"], (what, "fused launches, pairs against none"))
+    sc.same(out[True, "fused"], out[True, "single calls"].last(), (what, "pairs: fused against single calls"))
 
 
 def _full_wavefronts(T):
@@ -149,20 +96,21 @@ def test_the_tail_is_invisible_and_every_hand_over_scenario_occurs(T, storage):
     if not has_gpu():
         pytest.skip("no GPU")
     w = Workload(T, A, seed=_seed())
-    dts = _dts(S)
-    tr = _trace(w, S, storage, "cuda:0")
+    dts = sc.dts(S)
+    tr = sc.Trace(w, S, storage, gaps=True)
     out = _both_ways(w, T, storage, tr, dts)
-    g = _gain_iters(out[True, "single calls"][1])
+    st = out[True, "single calls"].status
+    g = _gain_iters(st)
     seen = {}
     for wv in _full_wavefronts(T):
         for name, epochs in _scenarios(g[:, 64 * wv:64 * wv + 64]).items():
             seen[name] = seen.get(name, 0) + len(epochs)
     print(f"T={T} storage={storage} seed={_seed()}: wavefront-epochs per scenario: {seen}")
     assert all(seen.values()), seen
-    assert (tr["r_host"][2, ::7, 1] == -1).all() and (g[2, ::7] > 0).all()      # an absent range: the tag still updates
-    st = out[True, "single calls"][1]
+    assert (tr.r_host[2, ::7, 1] == -1).all() and (g[2, ::7] > 0).all()      # an absent range: the tag still updates
     # fewer than four ranges: flagged, and the tag still iterates on what it has (next to wave-mates with all eight)
-    assert (st[4, 1::9] & ST_FEW_RANGES).all() and not (st[4, 0::9] & ST_FEW_RANGES).any() and (g[4] > 0).all()
+    few = st[4] & capi.ST_FEW_RANGES
+    assert few[1::9].all() and not few[0::9].any() and (g[4] > 0).all()
     if T == 101:   # the ragged wavefront iterates too (and never forms pairs: nothing to assert but its bits)
         assert (g[:, 64:] >= 8).any()
     _check_invisible(out, f"T={T} storage={storage}")
@@ -176,24 +124,24 @@ def test_a_partly_latched_wavefront_runs_the_per_lane_form_in_pairs(T, storage):
     if not has_gpu():
         pytest.skip("no GPU")
     w = Workload(T, A, seed=_seed())
-    dts = _dts(S)
-    tr = _trace(w, S, storage, "cuda:0")
+    dts = sc.dts(S)
+    tr = sc.Trace(w, S, storage, gaps=True)
     bare = np.arange(T) % 3 == 1
 
     def prepare(b):
-        _per_epoch(b, tr, 1, dts, T)      # one fused epoch: every tag latches its sample
+        sc.single_calls(b, tr, dts, 1, poses=False)      # one fused epoch: every tag latches its sample
         x, P, fl = b.get_state()
-        assert (fl & FL_HAS_IMU).all()
-        fl[bare] &= ~FL_HAS_IMU
+        assert (fl & sc.FL_HAS_IMU).all()
+        fl[bare] &= ~sc.FL_HAS_IMU
         b.set_state(x, P, fl)
 
-    out = _both_ways(w, T, storage, tr, dts, prepare=prepare, accel=False, s0=1, n=S - 1, split=(7, S - 8))
-    g = _gain_iters(out[True, "single calls"][1])
+    out = _both_ways(w, T, storage, tr, dts, prepare=prepare, accel=False, s0=1, n=S - 1)
+    g = _gain_iters(out[True, "single calls"].status)
     formed = sum(len(_scenarios(g[:, 64 * wv:64 * wv + 64])["at most 32 at 8"]) for wv in _full_wavefronts(T))
     print(f"T={T} storage={storage}: {formed} wavefront-epochs handed over at 8")
     assert formed > 0
-    fl = out[True, "fused"][4]
-    assert not (fl[bare] & FL_HAS_IMU).any() and (fl[~bare] & FL_HAS_IMU).all()
+    fl = out[True, "fused"].flags
+    assert not (fl[bare] & sc.FL_HAS_IMU).any() and (fl[~bare] & sc.FL_HAS_IMU).all()
     _check_invisible(out, f"partly latched, T={T} storage={storage}")
 
 
@@ -203,17 +151,17 @@ def test_a_lane_with_a_full_accelerometer_covariance_sends_its_wavefront_to_the_
         pytest.skip("no GPU")
     T = 128
     w = Workload(T, A, seed=_seed())
-    dts = _dts(S)
+    dts = sc.dts(S)
     cov = w.accel_cov().copy()
     cov[5, 1] = cov[5, 3] = 1e-3          # lane 5 of the first wavefront: an off-diagonal of 1e-3 m^2/s^4
-    tr = _trace(w, S, storage, "cuda:0", cov=cov)
+    tr = sc.Trace(w, S, storage, cov=cov, gaps=True)
     out = _both_ways(w, T, storage, tr, dts)
-    g = _gain_iters(out[True, "single calls"][1])
+    g = _gain_iters(out[True, "single calls"].status)
     assert len(_scenarios(g[:, :64])["at most 32 at 8"]) > 0 and len(_scenarios(g[:, 64:])["at most 32 at 8"]) > 0
     _check_invisible(out, f"one lane not diagonal, storage={storage}")
     # ... and the full form on every wavefront (KFPOS_IMU9_DIAG=0) computes the same as the default's choice
     forced = _both_ways(w, T, storage, tr, dts, diag=0)
-    _same_bits(forced[True, "fused"], out[True, "fused"], "pairs: KFPOS_IMU9_DIAG=0 against the default")
+    sc.same(forced[True, "fused"], out[True, "fused"], "pairs: KFPOS_IMU9_DIAG=0 against the default")
 
 
 @pytest.mark.parametrize("storage", [2, 3])
@@ -224,21 +172,21 @@ def test_a_nan_state_among_finite_wave_mates(storage):
         pytest.skip("no GPU")
     T, S0, bad = 64, 8, 5
     w = Workload(T, A, seed=_seed())
-    dts = _dts(S)
-    tr = _trace(w, S, storage, "cuda:0")
+    dts = sc.dts(S)
+    tr = sc.Trace(w, S, storage, gaps=True)
 
     def prepare(b):
-        _fused(b, tr, S0, dts, T, A)      # past the fixed start: the information form runs
+        sc.fused(b, tr, dts, S0)      # past the fixed start: the information form runs
         x, P, fl = b.get_state()
         x[bad, :3] = np.nan
         b.set_state(x, P, fl)
 
-    out = _both_ways(w, T, storage, tr, dts, prepare=prepare, s0=S0, n=S - S0, split=(7, S - S0 - 7))
-    st = out[True, "single calls"][1]
-    g = _gain_iters(st)
-    assert (st[:, bad] & ST_NONFINITE).all() and np.isnan(out[True, "single calls"][0][:, :, bad]).all()
+    out = _both_ways(w, T, storage, tr, dts, prepare=prepare, s0=S0, n=S - S0)
+    single = out[True, "single calls"]
+    g = _gain_iters(single.status)
+    assert (single.status[:, bad] & capi.ST_NONFINITE).all() and np.isnan(single.poses[:, :, bad]).all()
     others = np.arange(T) != bad
-    assert np.isfinite(out[True, "single calls"][0][:, :, others]).all()
+    assert np.isfinite(single.poses[:, :, others]).all()
     handed = [s for s in range(S - S0) if (g[s] > 0).all() and (g[s] >= 8).sum() <= 32 and g[s, bad] == 20]
     print(f"storage={storage}: {len(handed)} epochs in which the NaN tag went through a hand-over at 8")
     assert handed
@@ -252,28 +200,21 @@ def test_the_tail_matches_the_oracle(storage):
     where a stop decision sits on its threshold)"""
     if not has_gpu():
         pytest.skip("no GPU")
-    import oracle_py
     T = 128
     w = Workload(T, A, seed=_seed())
-    dts = _dts(S)
-    tr = _trace(w, S, storage, "cuda:0")
+    dts = sc.dts(S)
+    tr = sc.Trace(w, S, storage, gaps=True)
     b = _bank(w, T, storage, True)
-    got = _single_calls(b, tr, dts, T)
+    got = sc.single_calls(b, tr, dts, S)
     b.close()
-    o = oracle_py.OracleBank(1, T, w.anchors, init_pos=w.init_positions(), n_threads=8)
-    err, cov = w.err_est(np.float32).astype(np.float64), tr["cov_host"].astype(np.float64)
-    poses, stats = [], []
-    for s in range(S):
-        o.step_imu(w.accel(s, np.float32).astype(np.float64), cov, 0.0)
-        stats.append(np.asarray(o.step_toa(tr["r_host"][s], err, dts[s])).astype(np.uint32))
-        poses.append(o.get_state()[0][:, :3].T.copy())
-    d = np.sqrt(((got[0] - np.stack(poses)) ** 2).sum(1))
+    poses, theirs = sc.oracle_run(w, tr.r_host, w.err_est(), dts, real=np.float32, init=w.init_positions())[:2]
+    d = np.sqrt(((got.poses - poses.transpose(0, 2, 1)) ** 2).sum(1))
     rms, mx = float(np.sqrt((d ** 2).mean())), float(d.max())
     print(f"storage={storage}: RMS {rms:.3e} m, max {mx:.3e} m against the oracle over {S} epochs")
-    mine, theirs = got[1].astype(np.uint32), np.stack(stats)
+    mine = got.status.astype(np.uint32)
     if storage == 2:
         assert rms <= 1e-9 and mx <= 1e-8, (rms, mx)
         assert np.array_equal(mine, theirs)
     else:
         assert rms <= 1e-7 and mx <= 1e-6, (rms, mx)
-        assert np.array_equal(mine & 0xFF, theirs & 0xFF)
+        assert np.array_equal(capi.st_flags(mine), capi.st_flags(theirs))

@@ -8,6 +8,7 @@ from hypothesis import HealthCheck, given, settings, strategies as st
 import oracle_py
 from impls import emu_lib
 from planar import CFG, PlanarEmu, PlanarOracle
+from roskfpos_amd import capi
 from roskfpos_amd.synth import Workload, anchors_xyz
 
 import ctypes as C
@@ -76,7 +77,7 @@ def _tame(status, gain_cap):
     within 30 passes and the IEKF did not run into its iteration cap. A GN walk of 100+ passes or an IEKF that
     diverges (reference behaviour, reproduced) is a chaotic map: the last bit of any intermediate decides where it
     ends, so two correct implementations differ by metres there."""
-    ok = (((status >> 16) & 0xFF) <= 30) & (((status >> 8) & 0xFF) < gain_cap)
+    ok = (capi.st_ml_iters(status) <= 30) & (capi.st_gain_iters(status) < gain_cap)
     # an update (not an initialisation) the oracle skipped: exactly singular J' W J in the per-epoch ML solve -- anchors
     # and estimate on one line of this symmetric synthetic room -- which the kernels do not detect (kfpos_core.h)
     return ok & ~(((status & 0xFF) == 1))

@@ -12,6 +12,7 @@ import functools
 import numpy as np
 import pytest
 
+import ml_seed_cases as mc
 import weights_selects as ws
 from cases import Case, rms_and_max
 from impls import EmuImpl, EmuStaticImpl, OracleImpl
@@ -25,7 +26,7 @@ def _oracle(model):
 
 
 def _run(model, impl):
-    w, r, err = ws.inputs(T)
+    w, _, r, err = mc.inputs(T, **ws.INPUTS)
     f = impl(Case("weights_selects", model, ws.A, T=T, S=ws.S), w, w.init_positions())
     cov = w.accel_cov()
     pos, st = [], []
@@ -43,14 +44,14 @@ def _run(model, impl):
 def test_every_side_of_the_selects_against_the_oracle(model, impl):
     pos_o, st_o, (x_o, P_o) = _oracle(model)
     pos, st, (x, P) = _run(model, impl)
-    w, r, err = ws.inputs(T)
+    w, _, r, err = mc.inputs(T, **ws.INPUTS)
     ws.assert_inputs_reach_the_branches(model, w, r, err, st)
     rms, mx, same_nan = rms_and_max(pos, pos_o)
     print(f"model {model}: RMS {rms:.3e} m, max {mx:.3e} m against the oracle over {ws.S} epochs of {T} tags")
     assert same_nan
     assert rms <= 1e-9 and mx <= 1e-8, (rms, mx)
-    cmp = ws.oracle_status_comparable(model, T)
-    assert np.array_equal(st[:, cmp], st_o[:, cmp]), np.argwhere(st != st_o)
+    cmp = mc.oracle_status_comparable(model, T, exact_fit=False)
+    assert np.array_equal(st[cmp], st_o[cmp]), np.argwhere(st != st_o)
     ok = np.isfinite(x_o).all(1) & np.isfinite(P_o).all((1, 2))
     assert np.array_equal(ok, np.isfinite(x).all(1) & np.isfinite(P).all((1, 2)))
     assert np.abs(P_o[ok] - P[ok]).max() <= 1e-9 * np.abs(P_o[ok]).max()
@@ -60,7 +61,7 @@ def test_every_side_of_the_selects_against_the_oracle(model, impl):
 def test_a_garbage_slot_changes_no_bytes(model):
     """what an absent range's errorEstimation slot holds reaches no result: the run equals, byte for byte, the run in
     which those slots hold the ordinary value -- the tag's own bytes and every other tag's"""
-    w, r, err = ws.inputs(T)
+    w, _, r, err = mc.inputs(T, **ws.INPUTS)
     clean = err.copy()
     for lane in ws.GARBAGE:
         clean[lane, 1] = w.err_est()[lane, 1]

@@ -6,40 +6,27 @@ A tag's synthetic trace depends on its index only, so the same lanes serve every
 per tag for the whole trace (the entry points take it with stride 0), so a scenario is a tag."""
 import numpy as np
 
-from roskfpos_amd.synth import Workload
-
-A, S = 8, 7
-ST_UPDATE_SKIPPED, ST_FEW_RANGES, ST_NONFINITE = 0x01, 0x04, 0x20
+from ml_seed_cases import A, NAN_ERR, S
+from roskfpos_amd.capi import (ST_FEW_RANGES, ST_ML_FALLBACK, ST_NONFINITE, ST_UPDATE_SKIPPED, st_flags,
+                               st_gain_iters)
+from roskfpos_amd.synth import SEED
 
 # lane -> what the errorEstimation slot of its ABSENT range (anchor 1, absent in every epoch) holds
 GARBAGE = {3: np.nan, 7: 0.0, 11: np.inf, 13: -3.0}
 ZERO_ERR = 17      # a USED range (anchor 3) with errorEstimation exactly 0: the update is skipped, e_ML is NaN
 BETWEEN = 19       # errorEstimations from 5e-4 to 1 m^2 around e_ML (about 1e-2): both sides of the select in one tag
 FEW = 23           # two ranges in epochs 2 and 5, three in epoch 4
-# a USED range (anchor 5) with errorEstimation NaN: weights and ML position are NaN and the zero test does not fire. The
-# 9-state filter goes on with e_ML NaN (and a NaN state: the oracle reports such a tag with other status words than the
-# kernels, update skipped against iterated to the cap, as it always did: oracle_status_comparable); the 6-state filter
-# falls back to the predicted position, whose e_ML is finite
-NAN_ERR = 29
-ST_ML_FALLBACK = 0x02
+# NAN_ERR (ml_seed_cases.py's lane): a USED range (anchor 5) with errorEstimation NaN: weights and ML position are NaN
+# and the zero test does not fire. The 9-state filter goes on with e_ML NaN (and a NaN state: the oracle reports such a
+# tag with other status words than the kernels: ml_seed_cases.oracle_status_comparable); the 6-state filter falls back
+# to the predicted position, whose e_ML is finite
 SPREAD = (5e-4, 0.5, 1e-3, 1.0, 2e-3, 0.25, 2.5e-3, 0.1)
 SPECIAL = tuple(GARBAGE) + (ZERO_ERR, BETWEEN, FEW, NAN_ERR)
 
 
-def oracle_status_comparable(model, T):
-    """the lanes whose status words the oracle and the kernels agree on"""
-    ok = np.ones(T, dtype=bool)
-    if model == 1:
-        ok[NAN_ERR] = False
-    return ok
-
-
-def inputs(T, real=np.float64, seed=None):
-    """(workload, ranges [S][T][A] int32, errorEstimation [T][A] float64 holding values of `real`)"""
-    assert T > max(SPECIAL)
-    w = Workload(T, A) if seed is None else Workload(T, A, seed=seed)
-    r = np.stack([w.ranges_mm(s) for s in range(S)])
-    err = w.err_est().copy()
+def cases(init, r, err):
+    """ml_seed_cases.inputs(T, real, **INPUTS): this module's special tags, in the synthetic room, on its usual seed"""
+    assert len(init) > max(SPECIAL)
     for lane, junk in GARBAGE.items():
         r[:, lane, 1] = -1
         err[lane, 1] = junk
@@ -50,7 +37,9 @@ def inputs(T, real=np.float64, seed=None):
     r[5, FEW, 2:] = -1
     r[4, FEW, 3:] = 0
     err[NAN_ERR, 5] = np.nan
-    return w, r, err.astype(real).astype(np.float64)
+
+
+INPUTS = dict(seed=SEED, cases=cases, anchors=None)
 
 
 def e_ml_of(model, w, r, err, lane, real=np.float64, dts=None):
@@ -80,7 +69,7 @@ def e_ml_of(model, w, r, err, lane, real=np.float64, dts=None):
 def assert_inputs_reach_the_branches(model, w, r, err, status, real=np.float64, dts=None):
     """status: [S][T] status words of the implementation under test. Fails when an input stopped reaching its case."""
     st = np.asarray(status).astype(np.uint32)
-    gains = (st >> 8) & 0xFF
+    gains = st_gain_iters(st)
     for lane, junk in GARBAGE.items():   # absent in every epoch, the slot holds the junk, the tag updates all the same
         assert (r[:, lane, 1] <= 0).all() and (np.isnan(junk) and np.isnan(err[lane, 1]) or err[lane, 1] == junk)
         assert (gains[:, lane] > 0).all() and not (st[:, lane] & (ST_UPDATE_SKIPPED | ST_NONFINITE)).any(), lane
@@ -99,4 +88,4 @@ def assert_inputs_reach_the_branches(model, w, r, err, status, real=np.float64, 
         assert (st[:, NAN_ERR] & ST_ML_FALLBACK).all()
     assert not (st[:, NAN_ERR] & ST_UPDATE_SKIPPED).any()
     ordinary = np.setdiff1d(np.arange(st.shape[1]), SPECIAL)
-    assert not (st[:, ordinary] & 0xFF).any() and (gains[:, ordinary] > 0).all()
+    assert not st_flags(st[:, ordinary]).any() and (gains[:, ordinary] > 0).all()
