@@ -159,6 +159,48 @@ int kfpos_set_anchors(kfpos_handle *h, const double *xyz, const int32_t *ids, in
  * Only before the first step and only with use_init_pos = 1. */
 int kfpos_set_init_positions(kfpos_handle *h, const double *xyz);
 
+/* ---- anchor cells: one bank, one launch, an anchor table per block of KFPOS_CELL_TAGS rows ----
+ * A bank of many rooms: rows [64 b, 64 b + 64) form block b (the last block may be partial), and every block ranges
+ * against the table of the cell cell_of_block[b]. xyz: [n_cells][n_anchors][3] doubles, metres; cell_of_block:
+ * [(n_tags + 63) / 64] entries, each in [0, n_cells). n_anchors is ONE count for the handle, 1 .. max_anchors; a cell with
+ * fewer anchors pads its table with zeros, as kfpos_set_anchors pads, and sends no range (<= 0) in those columns. A tag
+ * that roams to another room moves to a row of a block of that room: kfpos_get_tags -> kfpos_set_tags ->
+ * kfpos_reset_tags. KFPOS_VERSION is unchanged: detect the feature by symbol.
+ *
+ * What it computes. Take a handle R with the same kfpos_config, created under KFPOS_NO_COOP=1, on which
+ * kfpos_set_anchors(table of cell c, NULL, n_anchors) was called. After the same calls with the same inputs every status
+ * word, every trajectory row and every stored byte (state, covariance in the handle's storage encoding, flags, latch)
+ * of every row of every block assigned to cell c is bit-identical in this handle and in R.
+ *
+ * Honoured by every whole-bank ranging round: kfpos_step_toa, kfpos_step_toa_imu, their _dev forms, whole-bank slot
+ * rounds (KFPOS_SLOT_RANGES_D16 included), the mapped-block path of small banks, and kfpos_run_trace_dev, which stays
+ * FUSED: up to KFPOS_TRACE_CHUNK_STEPS epochs per launch, as without cells. Unaffected (they read no anchor): IMU-only
+ * rounds, the pose calls, the lifecycle calls, the state accessors, the pose gather.
+ * Refused on a handle with cells, with KFPOS_ERR_MODEL and a kfpos_last_error() that says why:
+ *   kfpos_step_*_rows and kfpos_slot_submit_rows -- the compact work bank of a row list mixes rows of different cells in
+ *     one wavefront, and the anchors are wave-uniform;
+ *   kfpos_run_events_dev, kfpos_run_events_each_dev and kfpos_run_trace_each_dev -- their kernels read the one table of
+ *     the kernel arguments; no cells form of them is built yet.
+ *
+ * Errors, all found on the host before anything is written (after an error nothing has changed, and the kernels never see
+ * an unchecked cell index): KFPOS_ERR_ARG for a NULL pointer, n_cells < 1, n_anchors outside 1 .. max_anchors, or a cell
+ * index outside [0, n_cells) -- kfpos_last_error() names the first offending block. KFPOS_ERR_MODEL on KFPOS_MODEL_ML and
+ * KFPOS_MODEL_PLANAR: no cells kernel is built for them. KFPOS_ERR_STATE on a handle that runs the 8-lanes-per-tag kernel
+ * (small plain 6-state banks) and has already stepped: that kernel sums in another order. Such a handle that has NOT
+ * stepped leaves that kernel for good with its first kfpos_set_anchor_cells and from then on behaves like one created
+ * under KFPOS_NO_COOP=1 -- also after a later kfpos_set_anchors.
+ *
+ * The call may be repeated at any time -- to remap blocks, move anchors, change n_cells -- and takes effect for the calls
+ * made after it. It is a configuration call, the table lives in device memory: it first waits for everything the slots
+ * have in flight and for the handle's device (hipDeviceSynchronize). kfpos_set_anchors afterwards returns the handle to
+ * one table. A bank of more than 65 536 tags runs the one-wavefront build of its kernel while it has cells: the same
+ * bits, slower. */
+#define KFPOS_CELL_TAGS 64   /* rows per block: rows [64 b, 64 b + 64) form block b; the last block may be partial */
+int kfpos_set_anchor_cells(kfpos_handle *h, int32_t n_cells, int32_t n_anchors,
+                           const double *xyz,             /* [n_cells][n_anchors][3], metres */
+                           const int32_t *cell_of_block); /* [(n_tags + 63) / 64], each in [0, n_cells) */
+int kfpos_anchor_cells(const kfpos_handle *h);            /* cells in force, 0 = one table (kfpos_set_anchors) */
+
 /* KFPOS_MODEL_PLANAR: what KalmanFilter::init() loads. Before the first step; every tag starts at
  * fixed_height / init_angle. KFPOS_ERR_MODEL on other models. */
 int kfpos_set_planar(kfpos_handle *h, const kfpos_planar_config *cfg);

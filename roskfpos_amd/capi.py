@@ -21,6 +21,7 @@ _SENSOR_WIDTH = {1: 5, 2: 24, 3: 3, 4: 1}
 STORE_F64, STORE_F32, STORE_MIXED, STORE_P48 = 0, 1, 2, 3
 ML_NORMAL, ML_IGNORE_N, ML_BEST = 0, 1, 2
 MAX_ANCHORS = 64
+CELL_TAGS = 64  # KFPOS_CELL_TAGS: rows per block of a bank with anchor cells
 ST_UPDATE_SKIPPED, ST_ML_FALLBACK, ST_FEW_RANGES, ST_ML_INIT, ST_NOT_STARTED, ST_NONFINITE = 1, 2, 4, 8, 16, 32
 ST_SKIPPED = 64
 
@@ -48,6 +49,7 @@ def st_ignored(s):
 # every symbol include/kfpos.h declares
 EXPORTS = [
     "kfpos_create", "kfpos_destroy", "kfpos_init", "kfpos_set_anchors", "kfpos_set_init_positions",
+    "kfpos_set_anchor_cells", "kfpos_anchor_cells",
     "kfpos_real_size", "kfpos_step_toa", "kfpos_step_imu", "kfpos_step_toa_imu", "kfpos_get_pose",
     "kfpos_get_pose_each", "kfpos_get_predicted",
     "kfpos_state_dim", "kfpos_get_state", "kfpos_set_state", "kfpos_step_toa_dev", "kfpos_step_imu_dev",
@@ -158,6 +160,8 @@ def load():
     sig("kfpos_init", [vp])
     sig("kfpos_set_anchors", [vp, vp, vp, i32])
     sig("kfpos_set_init_positions", [vp, vp])
+    sig("kfpos_set_anchor_cells", [vp, i32, i32, vp, vp])
+    sig("kfpos_anchor_cells", [vp])
     sig("kfpos_real_size", [vp])
     sig("kfpos_state_dim", [vp])
     sig("kfpos_step_toa", [vp, vp, vp, vp, i32, vp])
@@ -298,6 +302,29 @@ class KfposBank:
             self.close()
         except Exception:
             pass
+
+    # ---- anchor cells: an anchor table per block of CELL_TAGS rows, one launch for all of them ----
+    def set_anchor_cells(self, tables, cell_of_block):
+        """kfpos_set_anchor_cells: tables (n_cells, n_anchors, 3) in metres, n_anchors <= max_anchors; cell_of_block
+        ((T + 63) // 64,): the cell of rows [64 b, 64 b + 64). Whole-bank ranging rounds then range every block against
+        its cell's table, bit for bit what a bank with that one table computes for those rows; row-list steps and the
+        event / per-tag replays refuse such a bank (KfposError). May be repeated; set_anchors() returns to one table."""
+        t = np.ascontiguousarray(tables, dtype=np.float64)
+        m = np.ascontiguousarray(cell_of_block, dtype=np.int32)
+        assert t.ndim == 3 and t.shape[2] == 3, t.shape
+        assert m.shape == ((self.T + CELL_TAGS - 1) // CELL_TAGS,), m.shape
+        self._chk(self.lib.kfpos_set_anchor_cells(self._h, t.shape[0], t.shape[1], t.ctypes.data, m.ctypes.data))
+
+    @property
+    def anchor_cells(self):
+        """cells in force; 0 = one table for the whole bank"""
+        return int(self.lib.kfpos_anchor_cells(self._h))
+
+    def set_anchors(self, anchors):
+        """kfpos_set_anchors: one table (n_anchors, 3) for the whole bank (a bank with cells returns to one table)"""
+        a = np.ascontiguousarray(anchors, dtype=np.float64)
+        assert a.ndim == 2 and a.shape[1] == 3, a.shape
+        self._chk(self.lib.kfpos_set_anchors(self._h, a.ctypes.data, None, a.shape[0]))
 
     # ---- host-buffer API ------------------------------------------------------
     def _dt(self, dt):

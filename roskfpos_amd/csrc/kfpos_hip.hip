@@ -85,12 +85,50 @@ step_kernel_t step_kernel(const kfpos_handle *h, const kfpos_plan::Plan &p) {
     return h->full ? kfpos_k::toa6_full_kernel(st, p.as, p.heur) : kfpos_k::toa6_sym_kernel(st, p.as, p.heur, p.two_waves);
 }
 
+
+/* ---- anchor cells: the ranging round of a handle with cells (kfpos_set_anchor_cells) ----
+ * The plan of the same handle without the 8-lanes-per-tag kernel and without the two-wavefront build: the cells kernels
+ * are the one-tag-per-lane, one-wavefront forms (kfpos_launch_plan.h is not told about cells) */
+kfpos_plan::Plan cells_plan(const kfpos_handle *h) {
+    kfpos_plan::Inputs in = plan_inputs(h);
+    in.coop = false;
+    in.two_waves = false;
+    return kfpos_plan::plan(in, kfpos_plan::STEP_RANGING);
+}
+kfpos_k::cells_kernel_t cells_kernel(const kfpos_handle *h, const kfpos_plan::Plan &p) {
+    const int st = h->cfg.storage;
+    if (h->cfg.model == KFPOS_MODEL_TOA_IMU) return kfpos_k::cells_imu9_kernel(st, p.as);
+    return h->full ? kfpos_k::cells_toa6_full_kernel(st, p.as, p.heur) : kfpos_k::cells_toa6_sym_kernel(st, p.as, p.heur);
+}
+int launch_cells(kfpos_handle *h, const KArgs &a, hipStream_t s) {
+    if (a.T != h->cfg.n_tags) { /* (every row-list call refuses a handle with cells before it gets here) */
+        g_err = "a handle with anchor cells steps the whole bank only";
+        return KFPOS_ERR_STATE;
+    }
+    const kfpos_plan::Plan p = cells_plan(h);
+    kfpos_k::CellArgs c;
+    c.k = a;
+    c.cell_xyz = h->d_cell_xyz;
+    c.cell_of_block = h->d_cell_of_block;
+    c.cell_stride = 3 * h->cfg.max_anchors;
+    hipLaunchKernelGGL(cells_kernel(h, p), dim3(p.groups(a.T)), dim3(WAVE), p.bytes(), s, c);
+    HIPCHK(hipGetLastError());
+    h->stepped = true;
+    return KFPOS_OK;
+}
+
 } // namespace
+
+int cells_refusal(const char *who, const char *why) {
+    g_err = std::string(who) + " is not defined for a handle with anchor cells (kfpos_set_anchor_cells): " + why;
+    return KFPOS_ERR_MODEL;
+}
 
 /* a.T tags: the whole bank, or the n tags of a work bank (row-list steps). WHICH kernel runs is a property of the handle
  * and of what the call feeds (a planar bank's a.mode is 0 or the sensor kind), never of a.T -- the plan is not told it: a
  * row-list step computes bit for bit what the whole-bank call does */
 int launch_step(kfpos_handle *h, const KArgs &a, hipStream_t s) {
+    if (h->n_cells > 0 && a.mode != MODE_IMU_ONLY) return launch_cells(h, a, s);
     const bool planar = h->cfg.model == KFPOS_MODEL_PLANAR;
     const kfpos_plan::Plan p = kfpos_plan::plan(plan_inputs(h), planar ? (a.mode != 0 ? kfpos_plan::STEP_SENSOR : kfpos_plan::STEP_RANGING)
                                                                        : (a.mode == MODE_IMU_ONLY ? kfpos_plan::STEP_IMU_ONLY : kfpos_plan::STEP_RANGING));
@@ -370,7 +408,7 @@ int kfpos_destroy(kfpos_handle *h) {
     if (!h) return KFPOS_ERR_ARG;
     void *ptrs[] = {h->d_pos, h->d_vel, h->d_P, h->d_imu_acc, h->d_imu_cov, h->d_flags, h->d_ranges,
                     h->d_err, h->d_accel, h->d_cov, h->d_dt, h->d_out, h->d_status, h->d_latch, h->d_sensor,
-                    h->d_stage, h->d_work};
+                    h->d_stage, h->d_work, h->d_cell_xyz, h->d_cell_of_block};
     DevScope dev_(h->cfg.device);
     (void)hipDeviceSynchronize(); /* nothing of this handle may still be in flight (streaming slots) */
     for (void *p : ptrs)
@@ -415,8 +453,67 @@ int kfpos_set_anchors(kfpos_handle *h, const double *xyz, const int32_t *ids, in
     std::memcpy(h->anchors, xyz, sizeof(double) * 3 * n_anchors);
     h->A = n_anchors;
     h->have_anchors = true;
+    h->n_cells = 0; /* back to one table (a handle that left the 8-lanes-per-tag kernel for cells does not return to it) */
     return KFPOS_OK;
 }
+
+int kfpos_set_anchor_cells(kfpos_handle *h, int32_t n_cells, int32_t n_anchors, const double *xyz, const int32_t *cell_of_block) {
+    g_err.clear();
+    if (!h || !xyz || !cell_of_block || n_cells < 1 || n_anchors < 1 || n_anchors > h->cfg.max_anchors) return KFPOS_ERR_ARG;
+    if (h->cfg.model != KFPOS_MODEL_TOA && h->cfg.model != KFPOS_MODEL_TOA_IMU) {
+        g_err = "kfpos_set_anchor_cells: no cells kernel is built for KFPOS_MODEL_ML and KFPOS_MODEL_PLANAR";
+        return KFPOS_ERR_MODEL;
+    }
+    const size_t n_blocks = ((size_t)h->cfg.n_tags + KFPOS_CELL_TAGS - 1) / KFPOS_CELL_TAGS;
+    for (size_t b = 0; b < n_blocks; ++b)
+        if (cell_of_block[b] < 0 || cell_of_block[b] >= n_cells) {
+            g_err = "kfpos_set_anchor_cells: cell_of_block[" + std::to_string(b) + "] = " + std::to_string(cell_of_block[b]) +
+                    " is outside [0, " + std::to_string(n_cells) + ")";
+            return KFPOS_ERR_ARG;
+        }
+    if (h->coop && h->stepped) {
+        g_err = "kfpos_set_anchor_cells: this handle runs the 8-lanes-per-tag kernel, which sums in another order than the "
+                "cells kernels, and has already stepped (call it before the first step, or create the handle under KFPOS_NO_COOP=1)";
+        return KFPOS_ERR_STATE;
+    }
+    DevScope dev_(h->cfg.device);
+    /* a configuration call: nothing that still reads the table in force may be in flight */
+    const int rc = drain_slots(h);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    /* a cells kernel whose plan takes more than 64 KB of LDS is allowed it here, as kfpos_create allows the others theirs */
+    const kfpos_plan::Plan p = cells_plan(h);
+    if (p.bytes() > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void *)cells_kernel(h, p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.bytes()));
+    const size_t stride = 3 * (size_t)h->cfg.max_anchors;
+    double *tab = h->d_cell_xyz;
+    int32_t *map = h->d_cell_of_block;
+    if ((size_t)n_cells > h->cell_cap) HIPCHK(hipMalloc((void **)&tab, (size_t)n_cells * stride * sizeof(double)));
+    if (!map && hipMalloc((void **)&map, n_blocks * sizeof(int32_t)) != hipSuccess) {
+        if (tab != h->d_cell_xyz) (void)hipFree(tab);
+        g_err = "hipMalloc(cell_of_block) failed";
+        return KFPOS_ERR_HIP;
+    }
+    if (tab != h->d_cell_xyz) {
+        if (h->d_cell_xyz) (void)hipFree(h->d_cell_xyz);
+        h->d_cell_xyz = tab;
+        h->cell_cap = (size_t)n_cells;
+    }
+    h->d_cell_of_block = map;
+    /* the table as the kernels read it: n_anchors rows per cell, zeros up to max_anchors */
+    std::vector<double> padded((size_t)n_cells * stride, 0.0);
+    for (size_t c = 0; c < (size_t)n_cells; ++c)
+        std::memcpy(&padded[c * stride], xyz + c * 3 * (size_t)n_anchors, sizeof(double) * 3 * (size_t)n_anchors);
+    HIPCHK(hipMemcpy(h->d_cell_xyz, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_cell_of_block, cell_of_block, n_blocks * sizeof(int32_t), hipMemcpyHostToDevice));
+    std::memset(h->anchors, 0, sizeof(h->anchors)); /* (KArgs::anchors: no kernel of a handle with cells reads it) */
+    h->A = n_anchors;
+    h->have_anchors = true;
+    h->n_cells = n_cells;
+    h->coop = false; /* (not stepped, or never was: see above) */
+    return KFPOS_OK;
+}
+int kfpos_anchor_cells(const kfpos_handle *h) { return h ? h->n_cells : 0; }
 
 int kfpos_set_init_positions(kfpos_handle *h, const double *xyz) {
     g_err.clear();
@@ -591,6 +688,7 @@ static int round_host(kfpos_handle *h, const char *who, int kind, int32_t sensor
                       int32_t n, const RoundIn &src, const double *dt, int32_t dt_len, uint32_t *status) {
     g_err.clear();
     if (!h) return KFPOS_ERR_ARG;
+    if (listed && h->n_cells > 0) return cells_refusal(who, CELLS_NO_ROWS);
     const Round r = round_check(h, kind, sensor_kind, false);
     if (r.answer == KFPOS_ERR_ARG) return KFPOS_ERR_ARG;
     int rc = listed ? rows_check(h, who, rows, n) : KFPOS_OK;

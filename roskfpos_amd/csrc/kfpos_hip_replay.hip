@@ -243,6 +243,7 @@ int kfpos_run_events_dev(kfpos_handle *h, int32_t n_events, const uint8_t *kinds
     int lead; /* ranging events ahead of the call's first sample */
     int rc = check_events9("kfpos_run_events_dev", h, n_events, kinds, range_mm, err_est, accel, cov, &lead);
     if (rc != KFPOS_OK) return rc;
+    if (h->n_cells > 0) return cells_refusal("kfpos_run_events_dev", CELLS_NO_REPLAY);
     DevScope dev_(h->cfg.device);
     const hipStream_t s = (hipStream_t)stream;
     /* They re-fuse what the handle held latched, with THAT sample's covariance: the ranging path, which reads the latch. */
@@ -278,6 +279,7 @@ int kfpos_run_events_each_dev(kfpos_handle *h, int32_t n_events, const uint8_t *
     int first_imu;
     int rc = check_events9("kfpos_run_events_each_dev", h, n_events, kinds, range_mm, err_est, accel, cov, &first_imu);
     if (rc != KFPOS_OK) return rc;
+    if (h->n_cells > 0) return cells_refusal("kfpos_run_events_each_dev", CELLS_NO_REPLAY);
     DevScope dev_(h->cfg.device);
     /* No "lead" split as in kfpos_run_events_dev: which tags have ranging events ahead of their first sample is in
      * dt_events_dev, which the host never reads. The kernel switches whiteners per lane instead -- the latched
@@ -312,6 +314,7 @@ int kfpos_run_trace_each_dev(kfpos_handle *h, int32_t n_steps, const double *dt_
     if (!dt_steps_dev || !range_mm || !err_est) return KFPOS_ERR_ARG;
     if (h->cfg.model != KFPOS_MODEL_TOA) return KFPOS_ERR_MODEL;
     if (!h->have_anchors) return no_anchors();
+    if (h->n_cells > 0) return cells_refusal("kfpos_run_trace_each_dev", CELLS_NO_REPLAY);
     DevScope dev_(h->cfg.device);
     const size_t T = h->cfg.n_tags, r = h->msz;
     const hipStream_t s = (hipStream_t)stream;

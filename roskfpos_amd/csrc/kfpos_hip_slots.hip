@@ -382,6 +382,7 @@ int kfpos_slot_wait(kfpos_handle *h, int32_t slot) {
 int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t n, double dt_shared) {
     g_err.clear();
     if (!h || slot < 0 || slot >= KFPOS_N_SLOTS) return KFPOS_ERR_ARG;
+    if (h->n_cells > 0) return cells_refusal("kfpos_slot_submit_rows", CELLS_NO_ROWS); /* (nothing of the slot has changed) */
     DevScope dev_(h->cfg.device);
     d16_close(h, slot, false, KFPOS_OK); /* an open slot sent as a row list: its D16 round is abandoned */
     if (flags & KFPOS_SLOT_RANGES_D16) {

@@ -53,6 +53,14 @@ struct kfpos_handle {
     bool imu9_diag;     /* 9-state bank: wavefronts with diagonal accelerometer covariances take the diagonal form of the gain iteration (bit-identical); KFPOS_IMU9_DIAG=0 disables */
     bool coop;          /* small plain 6-state bank: one tag per 8 lanes (k_step_toa6_coop); KFPOS_NO_COOP=1 disables */
     double anchors[KFPOS_MAX_ANCHORS * 3];
+    /* anchor cells (kfpos_set_anchor_cells): n_cells > 0 = every block of KFPOS_CELL_TAGS rows ranges against the table
+     * of its cell, and ranging rounds run the cells kernels (kfpos_k_cells*.hip). d_cell_xyz: [n_cells][max_anchors][3],
+     * zeros behind the A rows set (room for cell_cap cells); d_cell_of_block: [(n_tags + 63) / 64], validated by the host.
+     * Both stay allocated when kfpos_set_anchors returns the handle to one table (n_cells = 0). */
+    int n_cells = 0;
+    size_t cell_cap = 0;
+    double *d_cell_xyz = nullptr;
+    int32_t *d_cell_of_block = nullptr;
     /* device state */
     double *d_pos = nullptr;
     double *d_vel = nullptr;

@@ -26,7 +26,7 @@
  *    shuffle and no barrier (the exception: the 8-lanes-per-tag kernel of small banks, kfpos_k_coop.hip).
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
- * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
+ * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_cells6s / kfpos_k_cells6f / kfpos_k_cells9 (ranging rounds of a bank with anchor cells: an anchor table per block of 64 rows), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
  * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_k_d16 (the decoder of KFPOS_SLOT_RANGES_D16 rounds), kfpos_hip (host side + C ABI; it and kfpos_hip_replay turn a Plan of kfpos_launch_plan.h into a kernel and launch it, and hold no LDS size or kernel form of their own), kfpos_hip_state (the state side of the C ABI: whole-bank accessors, per-tag lifecycle, pose for a row list), kfpos_hip_slots (the streaming slots of the C ABI, kfpos_slot_*), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
@@ -190,6 +190,22 @@ struct PevEachArgs {
 static_assert(sizeof(PevEachArgs) <= 4096, "kernel arguments are limited to 4 KB");
 typedef void (*planar_events_each_kernel_t)(const PevEachArgs);
 
+/* Ranging rounds of a bank with anchor cells (kfpos_set_anchor_cells; kfpos_k_cells6s.hip / kfpos_k_cells6f.hip,
+ * kfpos_k_cells9.hip): a block of its own around an unchanged KArgs once more. Rows [64 b, 64 b + 64) are workgroup b of
+ * the launch and range against cell cell_of_block[b], whose table starts at cell_xyz + cell_of_block[b] * cell_stride:
+ * k.A rows of xyz, zeros up to max_anchors rows (cell_stride = 3 * max_anchors doubles: a kernel with a compile-time
+ * anchor count reads that many rows whatever k.A is, and finds the zeros kfpos_set_anchors pads with). k.anchors is not
+ * read. The host has checked every entry of cell_of_block against the number of cells. */
+struct CellArgs {
+    KArgs k;
+    const double *cell_xyz;       /* DEVICE, [n_cells][max_anchors][3] */
+    const int32_t *cell_of_block; /* DEVICE, [(T + 63) / 64] */
+    int32_t cell_stride;          /* doubles from one cell's table to the next */
+};
+static_assert(sizeof(CellArgs) <= 4096, "kernel arguments are limited to 4 KB");
+static_assert(KFPOS_CELL_TAGS == kfpos_plan::LANES, "a cell is assigned per workgroup: one wavefront, one tag per lane");
+typedef void (*cells_kernel_t)(const CellArgs);
+
 /* ---- selectors: each is defined in the translation unit that instantiates the kernels it hands out ----
  * st = KFPOS_STORE_*; as = anchor-count specialisation (8: epoch in registers; -8 / -16: compile-time loops over an
  * LDS-resident epoch; 0: run-time loop); heur: 0 = no outlier heuristic, 1 = top-N only, 2 = leave-one-out */
@@ -199,6 +215,9 @@ step_kernel_t toa6_coop_kernel(int st);                                    /* kf
 trace_each_kernel_t toa6_each_sym_kernel(int st, int as, int heur);        /* kfpos_k_toa6eachs.hip */
 trace_each_kernel_t toa6_each_full_kernel(int st, int as, int heur);       /* kfpos_k_toa6eachf.hip */
 step_kernel_t imu9_kernel(int st, int as, bool ranging);                   /* kfpos_k_imu9.hip */
+cells_kernel_t cells_toa6_sym_kernel(int st, int as, int heur);            /* kfpos_k_cells6s.hip */
+cells_kernel_t cells_toa6_full_kernel(int st, int as, int heur);           /* kfpos_k_cells6f.hip */
+cells_kernel_t cells_imu9_kernel(int st, int as);                          /* kfpos_k_cells9.hip: as = 8 or 0 */
 events_kernel_t imu9_events_kernel(int st, int as);                        /* kfpos_k_imu9ev.hip: as = 8 or 0 */
 events_each_kernel_t imu9_events_each_kernel(int st, int as);              /* kfpos_k_imu9each.hip: as = 8 or 0 */
 planar_events_kernel_t planar_events_kernel(int st, int as);               /* kfpos_k_planarev.hip: as = -8 or 0 */
@@ -275,6 +294,10 @@ KFPOS_HIDDEN int round_refusal(int answer); /* KFPOS_ERR_MODEL / _STATE as the c
 /* fill_args + the round's part of the argument block (latch = 1) */
 KFPOS_HIDDEN void round_args(const kfpos_handle *h, const Round &r, const RoundIn &in, const double *dt, double dt_shared,
                              uint32_t *status, double *traj, kfpos_k::KArgs &a);
+/* a call that cannot honour anchor cells, on a handle that has them: KFPOS_ERR_MODEL, and the text says why */
+KFPOS_HIDDEN int cells_refusal(const char *who, const char *why);
+constexpr const char *CELLS_NO_ROWS = "the compact work bank of a row list mixes rows of different cells in one wavefront, and the anchors are wave-uniform";
+constexpr const char *CELLS_NO_REPLAY = "its kernel reads the one anchor table of the kernel arguments, and no cells form of it is built";
 KFPOS_HIDDEN int drain_slots(kfpos_handle *h); /* kfpos_hip_slots.hip: wait for whatever the slots still have in flight */
 /* row-list rounds, synchronous and streaming: the list's check (rows inside the bank, none twice), room for n listed tags
  * in the work block, and gather -> step -> scatter on stream s (a: round_args with the inputs at [.][n]) */
