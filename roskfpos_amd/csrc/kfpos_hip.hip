@@ -107,7 +107,7 @@ int launch_cells(kfpos_handle *h, const KArgs &a, hipStream_t s) {
     }
     const kfpos_plan::Plan p = cells_plan(h);
     kfpos_k::CellArgs c;
-    c.k = a;
+    static_cast<KArgs &>(c) = a;
     c.cell_xyz = h->d_cell_xyz;
     c.cell_of_block = h->d_cell_of_block;
     c.cell_stride = 3 * h->cfg.max_anchors;

@@ -1,11 +1,11 @@
 /*
- * kfpos_k_cells6f.hip -- k_cells_toa6, full covariance layout: banks with anchor cells and ML initialisation
+ * kfpos_k_cells6f.hip -- k_step_toa6 around CellArgs, full covariance layout: banks with anchor cells and ML initialisation
  */
 #include "kfpos_kernels.h"
 
 namespace {
 
-#include "kfpos_k_cells6.inc"
+#include "kfpos_k_toa6.inc"
 
 } // namespace
 

@@ -1,11 +1,11 @@
 /*
- * kfpos_k_cells6s.hip -- k_cells_toa6, symmetric (packed) covariance layout: banks with anchor cells and a fixed start
+ * kfpos_k_cells6s.hip -- k_step_toa6 around CellArgs, symmetric (packed) covariance layout: banks with anchor cells and a fixed start
  */
 #include "kfpos_kernels.h"
 
 namespace {
 
-#include "kfpos_k_cells6.inc"
+#include "kfpos_k_toa6.inc"
 
 } // namespace
 

@@ -1,5 +1,6 @@
 /* kfpos_k_toa6.inc -- the 6-state step kernels (KalmanFilterTOA.cpp:70-156), included by kfpos_k_toa6s.hip (symmetric
- * covariance layout: fixed start) and kfpos_k_toa6f.hip (full layout: ML initialisation), which instantiate one half each */
+ * covariance layout: fixed start) and kfpos_k_toa6f.hip (full layout: ML initialisation), which instantiate one half each,
+ * and by kfpos_k_cells6s.hip / kfpos_k_cells6f.hip, which instantiate the same halves around CellArgs (anchor cells) */
 /* ------------------------------------------------------------------ 6-state step kernel */
 /* amdgpu_waves_per_eu(1, 2): never trade registers for a third wave per SIMD -- the LDS-resident 16-anchor variant
  * fits in 137-150 VGPRs when asked to (e.g. when pinned to two waves), and then runs 3-11 % slower than with the ~250 it
@@ -10,15 +11,22 @@
  * holds (two planes): the 16-anchor kernels re-form their offsets at the end of the launch instead of holding them across
  * the step (`ts` below), which leaves every instantiation at 251-253 registers, and `make check` verifies the occupancy of
  * every kernel that is meant to share a SIMD (tools/check_scratch.py --min-occupancy). */
-template <bool SYMM, typename REAL, typename MREAL, int AS, int HEUR = 2>
-__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_step_toa6(const KArgs a) {
+/* ARGS: the argument block. KArgs: the anchor table is KArgs::anchors. CellArgs (a bank with anchor cells,
+ * kfpos_set_anchor_cells; kfpos_k_cells6s.hip / kfpos_k_cells6f.hip instantiate these): the table of the workgroup's
+ * cell -- the one line below that asks. step_toa6, the staging helpers and the order of every load and store are the
+ * same text, so a block of cell c computes bit for bit what its rows compute with cell c's table in KArgs::anchors.
+ * The parameter is the block itself and is named wherever a field is read: behind a reference to it, or inside a
+ * function that both forms call, every KArgs instantiation came out with other code. */
+template <bool SYMM, typename REAL, typename MREAL, int AS, int HEUR = 2, class ARGS = KArgs>
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_step_toa6(const ARGS a) {
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
     const size_t t = (size_t)blockIdx.x * WAVE + lane;
     if (t >= (size_t)a.T) return;
     const size_t T = a.T;
     const uint32_t t32 = (uint32_t)t;
-    const Params pr = make_params(a);
+    Params pr = make_params(a);
+    if constexpr (cells_block<ARGS>) pr.anchors = cell_anchors(a);
     constexpr int NA = AS > 0 ? AS : 1;
     /* The Gauss-Newton solves in ml_estimate's peeled text (step_toa6's PEEL). The 8-anchor LDS form with both
      * heuristics -- up to 65 solves around one inlined solver -- spills inside its loops with it and keeps the
@@ -157,23 +165,20 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
     if (a.status) a.status[t] = s;
 }
 
+/* k_step_toa6 around one argument block, as a family of toa6_table (kfpos_kernels.h) */
+template <class ARGS>
+struct StepToa6 {
+    template <bool SYMM, typename REAL, typename MREAL, int AS, int HEUR>
+    static constexpr auto kernel() -> void (*)(const ARGS) { return k_step_toa6<SYMM, REAL, MREAL, AS, HEUR, ARGS>; }
+};
+/* the table, and in front of it the two-wavefront build, which only the plain step has */
 template <bool SYMM, typename REAL, typename MREAL>
 step_kernel_t toa6_kernel(int as, int heur, bool two_waves = false) {
-    /* heur: 0 = the bank has no outlier heuristic (BASELINE configs 2 and 4), 1 = top-N only (config 5), 2 = leave-one-out
-     * (with or without top-N). 0 and 1 get instantiations with no leave-one-out loop compiled in: 13 % faster at 8 anchors */
     if constexpr (SYMM) {
         if (as == 8 && heur == 0 && two_waves) return k_step_toa6_w2<REAL, MREAL>;
-        if (as == 8) return heur ? k_step_toa6<true, REAL, MREAL, 8> : k_step_toa6<true, REAL, MREAL, 8, 0>;
-    } else {
-        /* non-symmetric layout (ML initialisation): its SVD path needs the registers a resident epoch would take
-         * (148-180 bytes/lane of scratch otherwise), so the 8-anchor epoch goes to LDS, loops still compile-time */
-        if (as == 8) {
-            if (!heur) return k_step_toa6<false, REAL, MREAL, -8, 0>;
-            /* (leave-one-out with the 48-bit covariance: the host never asks -- kfpos_create -- and the instantiation
-             * is not built: it would access scratch memory inside its epoch loop) */
-            if constexpr (!std::is_same<REAL, p48>::value) return k_step_toa6<false, REAL, MREAL, -8>;
-        }
     }
-    if (as == -16) return heur == 1 ? k_step_toa6<SYMM, REAL, MREAL, -16, 1> : k_step_toa6<SYMM, REAL, MREAL, -16>;
-    return heur ? k_step_toa6<SYMM, REAL, MREAL, 0> : k_step_toa6<SYMM, REAL, MREAL, 0, 0>;
+    return toa6_table<StepToa6<KArgs>, SYMM, REAL, MREAL>(as, heur);
 }
+template <bool SYMM, typename REAL, typename MREAL>
+kfpos_k::cells_kernel_t cells_toa6_kernel(int as, int heur) { return toa6_table<StepToa6<CellArgs>, SYMM, REAL, MREAL>(as, heur); }
+

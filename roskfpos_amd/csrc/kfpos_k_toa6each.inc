@@ -110,19 +110,10 @@ __global__ __launch_bounds__(WAVE) void k_trace_toa6_each(const kfpos_k::TraceEa
     a.flags[ts] = fl0 | FL_STARTED;
 }
 
-/* the table of toa6_kernel (kfpos_k_toa6.inc) without the two-wavefront build. Combinations that run the AS = 0 form
- * because their own would touch scratch memory inside the slot loop (make check): DESIGN.md section 6 lists them */
+/* k_trace_toa6_each as a family of toa6_table (kfpos_kernels.h) */
+struct TraceToa6Each {
+    template <bool SYMM, typename REAL, typename MREAL, int AS, int HEUR>
+    static constexpr kfpos_k::trace_each_kernel_t kernel() { return k_trace_toa6_each<SYMM, REAL, MREAL, AS, HEUR>; }
+};
 template <bool SYMM, typename REAL, typename MREAL>
-kfpos_k::trace_each_kernel_t toa6_each_kernel(int as, int heur) {
-    if constexpr (SYMM) {
-        if (as == 8) return heur ? k_trace_toa6_each<true, REAL, MREAL, 8> : k_trace_toa6_each<true, REAL, MREAL, 8, 0>;
-    } else {
-        if (as == 8) {
-            if (!heur) return k_trace_toa6_each<false, REAL, MREAL, -8, 0>;
-            /* (leave-one-out with the 48-bit covariance on the full layout: never built, as in toa6_kernel) */
-            if constexpr (!std::is_same<REAL, p48>::value) return k_trace_toa6_each<false, REAL, MREAL, -8>;
-        }
-    }
-    if (as == -16) return heur == 1 ? k_trace_toa6_each<SYMM, REAL, MREAL, -16, 1> : k_trace_toa6_each<SYMM, REAL, MREAL, -16>;
-    return heur ? k_trace_toa6_each<SYMM, REAL, MREAL, 0> : k_trace_toa6_each<SYMM, REAL, MREAL, 0, 0>;
-}
+kfpos_k::trace_each_kernel_t toa6_each_kernel(int as, int heur) { return toa6_table<TraceToa6Each, SYMM, REAL, MREAL>(as, heur); }

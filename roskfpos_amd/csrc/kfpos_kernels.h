@@ -26,7 +26,7 @@
  *    shuffle and no barrier (the exception: the 8-lanes-per-tag kernel of small banks, kfpos_k_coop.hip).
  *
  * Translation units (one code object each, built in parallel): kfpos_k_toa6s / kfpos_k_toa6f (6-state filter, symmetric /
- * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_cells6s / kfpos_k_cells6f / kfpos_k_cells9 (ranging rounds of a bank with anchor cells: an anchor table per block of 64 rows), kfpos_k_imu9 (9-state), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
+ * full covariance layout), kfpos_k_toa6eachs / kfpos_k_toa6eachf (6-state, ranging slots with a timeline per tag, the same two layouts), kfpos_k_coop (6-state, 8 lanes per tag), kfpos_k_cells6s / kfpos_k_cells6f / kfpos_k_cells9 (ranging rounds of a bank with anchor cells, an anchor table per block of 64 rows: the step kernels of kfpos_k_toa6.inc / kfpos_k_imu9.inc once more, around CellArgs), kfpos_k_imu9 (9-state; its text is kfpos_k_imu9.inc), kfpos_k_imu9ev (9-state, event schedules), kfpos_k_imu9each (9-state, event schedules with a timeline per tag), kfpos_k_planarev (8-state planar filter, event schedules), kfpos_k_planareach (8-state planar filter, event schedules with a timeline per tag), kfpos_k_misc (8-state planar
  * filter, standalone ML estimator, getPose for the bank and for a list of tags, layout turns), kfpos_k_tags (per-tag gather / scatter / reset, the work bank of row-list steps), kfpos_k_d16 (the decoder of KFPOS_SLOT_RANGES_D16 rounds), kfpos_hip (host side + C ABI; it and kfpos_hip_replay turn a Plan of kfpos_launch_plan.h into a kernel and launch it, and hold no LDS size or kernel form of their own), kfpos_hip_state (the state side of the C ABI: whole-bank accessors, per-tag lifecycle, pose for a row list), kfpos_hip_slots (the streaming slots of the C ABI, kfpos_slot_*), kfpos_hip_replay (the replay entry points of the C ABI: whole schedules in few launches), kfpos_comm (RCCL gather).
  */
 #ifndef KFPOS_KERNELS_H
@@ -191,19 +191,27 @@ static_assert(sizeof(PevEachArgs) <= 4096, "kernel arguments are limited to 4 KB
 typedef void (*planar_events_each_kernel_t)(const PevEachArgs);
 
 /* Ranging rounds of a bank with anchor cells (kfpos_set_anchor_cells; kfpos_k_cells6s.hip / kfpos_k_cells6f.hip,
- * kfpos_k_cells9.hip): a block of its own around an unchanged KArgs once more. Rows [64 b, 64 b + 64) are workgroup b of
- * the launch and range against cell cell_of_block[b], whose table starts at cell_xyz + cell_of_block[b] * cell_stride:
- * k.A rows of xyz, zeros up to max_anchors rows (cell_stride = 3 * max_anchors doubles: a kernel with a compile-time
- * anchor count reads that many rows whatever k.A is, and finds the zeros kfpos_set_anchors pads with). k.anchors is not
- * read. The host has checked every entry of cell_of_block against the number of cells. */
-struct CellArgs {
-    KArgs k;
+ * kfpos_k_cells9.hip): KArgs, unchanged, and behind it where the tables are. A step kernel takes its argument block as a
+ * template parameter (KArgs by default) and names the by-value parameter itself wherever it reads a field: CellArgs
+ * derives from KArgs, so the one text reads a.T, a.flags, ... of either block, and `if constexpr (cells_block<ARGS>)`
+ * guards the lines that differ (kfpos_k_toa6.inc, kfpos_k_imu9.inc). Rows [64 b, 64 b + 64) are workgroup b of the launch
+ * and range against cell cell_of_block[b], whose table starts at cell_xyz + cell_of_block[b] * cell_stride: A rows of
+ * xyz, zeros up to max_anchors rows (cell_stride = 3 * max_anchors doubles: a kernel with a compile-time anchor count
+ * reads that many rows whatever A is, and finds the zeros kfpos_set_anchors pads with). `anchors` is not read. The host
+ * has checked every entry of cell_of_block against the number of cells: the kernels index with it as it is. */
+struct CellArgs : KArgs {
     const double *cell_xyz;       /* DEVICE, [n_cells][max_anchors][3] */
     const int32_t *cell_of_block; /* DEVICE, [(T + 63) / 64] */
     int32_t cell_stride;          /* doubles from one cell's table to the next */
 };
 static_assert(sizeof(CellArgs) <= 4096, "kernel arguments are limited to 4 KB");
 static_assert(KFPOS_CELL_TAGS == kfpos_plan::LANES, "a cell is assigned per workgroup: one wavefront, one tag per lane");
+template <class ARGS>
+constexpr bool cells_block = std::is_same<ARGS, CellArgs>::value;
+/* One workgroup is one wavefront is one block of KFPOS_CELL_TAGS rows, so a cell's table is wave-uniform as the
+ * kernel-argument table is: map and table are read through pointers in the constant address space (scalar loads) */
+typedef const __attribute__((address_space(4))) double *cell_table_t;
+typedef const __attribute__((address_space(4))) int32_t *cell_map_t;
 typedef void (*cells_kernel_t)(const CellArgs);
 
 /* ---- selectors: each is defined in the translation unit that instantiates the kernels it hands out ----
@@ -447,6 +455,8 @@ namespace {
 
 using namespace kfpos;
 using kfpos_k::KArgs;
+using kfpos_k::CellArgs;
+using kfpos_k::cells_block;
 using kfpos_k::PoseArgs;
 using kfpos_k::PoseRowsArgs;
 using kfpos_k::step_kernel_t;
@@ -543,6 +553,35 @@ __device__ inline P make_params_of(const KArgs &a) {
     return pr;
 }
 __device__ inline Params make_params(const KArgs &a) { return make_params_of<Params>(a); }
+/* the anchor table of this workgroup's cell: what Params::anchors points at in a kernel built around CellArgs */
+__device__ inline const double *cell_anchors(const CellArgs &c) {
+    const int cell = ((kfpos_k::cell_map_t)c.cell_of_block)[blockIdx.x];
+    return (const double *)((kfpos_k::cell_table_t)c.cell_xyz + (size_t)cell * c.cell_stride);
+}
+
+/* The 6-state selector table, once for every kernel family that has these forms (k_step_toa6 around either argument
+ * block: kfpos_k_toa6.inc; k_trace_toa6_each: kfpos_k_toa6each.inc): FAM::kernel<SYMM, REAL, MREAL, AS, HEUR>() is the
+ * family's instantiation. heur: 0 = the bank has no outlier heuristic (BASELINE configs 2 and 4), 1 = top-N only
+ * (config 5), 2 = leave-one-out (with or without top-N). 0 and 1 get instantiations with no leave-one-out loop compiled
+ * in: 13 % faster at 8 anchors. Combinations that run the AS = 0 form because their own would touch scratch memory
+ * inside the epoch loop (make check): DESIGN.md section 6 lists them. */
+template <class FAM, bool SYMM, typename REAL, typename MREAL>
+auto toa6_table(int as, int heur) -> decltype(FAM::template kernel<SYMM, REAL, MREAL, 0, 0>()) {
+    if constexpr (SYMM) {
+        if (as == 8) return heur ? FAM::template kernel<true, REAL, MREAL, 8, 2>() : FAM::template kernel<true, REAL, MREAL, 8, 0>();
+    } else {
+        /* non-symmetric layout (ML initialisation): its SVD path needs the registers a resident epoch would take
+         * (148-180 bytes/lane of scratch otherwise), so the 8-anchor epoch goes to LDS, loops still compile-time */
+        if (as == 8) {
+            if (!heur) return FAM::template kernel<false, REAL, MREAL, -8, 0>();
+            /* (leave-one-out with the 48-bit covariance: the host never asks -- kfpos_create -- and the instantiation
+             * is not built: it would access scratch memory inside its epoch loop) */
+            if constexpr (!std::is_same<REAL, p48>::value) return FAM::template kernel<false, REAL, MREAL, -8, 2>();
+        }
+    }
+    if (as == -16) return heur == 1 ? FAM::template kernel<SYMM, REAL, MREAL, -16, 1>() : FAM::template kernel<SYMM, REAL, MREAL, -16, 2>();
+    return heur ? FAM::template kernel<SYMM, REAL, MREAL, 0, 2>() : FAM::template kernel<SYMM, REAL, MREAL, 0, 0>();
+}
 
 /* Raw epoch of one tag as it sits in HBM: fetched one epoch ahead in multi-epoch launches, so its
  * latency hides behind the previous epoch's arithmetic. */
@@ -604,7 +643,7 @@ __device__ inline StaticScratch<N> stage_epoch_lds_n(const KArgs &a, double *lds
     }
     return sc;
 }
-/* ---- 9-state kernels (kfpos_k_imu9.hip, kfpos_k_imu9ev.hip): the accelerometer sample and its covariance ---- */
+/* ---- 9-state kernels (kfpos_k_imu9.inc, kfpos_k_imu9ev.hip): the accelerometer sample and its covariance ---- */
 /* The acceleration sample is fetched one epoch ahead like the ranges. Its covariance is loaded and whitened ONCE per
  * launch: a multi-epoch launch always has one covariance array for all its epochs (stride_cov = 0: a sensor with a
  * fixed covariance); a trace with a covariance per epoch is replayed one epoch per launch (kfpos_run_trace_dev). */

@@ -15,8 +15,12 @@ import subprocess
 import tempfile
 
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-# k_step_imu9<double,float,8,true> (the bench kernel) and k_step_imu9<p48,float,8,true>, mangled
-KERNELS = (r"k_step_imu9IdfLi8ELb1E", r"k_step_imu9I\w*p48\w*fLi8ELb1E")
+# k_step_imu9<double,float,8,true,KArgs> (the bench kernel) and k_step_imu9<p48,float,8,true,KArgs>, mangled. The
+# argument block is part of the pattern: the same template around CellArgs (anchor cells) keeps the plain epoch order,
+# has no pairs' loop to find, and is not held to the headline kernels' rules. \w* in front of it: KArgs is mangled as a
+# template argument in the library and as the parameter's type in names written before the block was a parameter.
+ARGS = r"\w*5KArgsE"
+KERNELS = (r"k_step_imu9IdfLi8ELb1E" + ARGS, r"k_step_imu9I\w*p48\w*fLi8ELb1E" + ARGS)
 VMEM = ("global_", "flat_", "buffer_", "scratch_", "tbuffer_")
 LINE = re.compile(r"^\s+(\S+)\s*(.*?)\s*//\s*([0-9A-Fa-f]+):\s*[0-9A-Fa-f ]*(?:<\S+?(?:\+0x([0-9a-fA-F]+))?>)?\s*$")
 FP64 = re.compile(r"^v_(mul|fmac|fma|add|rsq|rcp|sqrt|min|max|ldexp|div_\w+|trig_preop|frexp_mant|fract|floor|ceil|rndne|trunc)_f64")
