@@ -2,7 +2,7 @@
  * kfpos_hip.hip -- host side of libkfpos_hip.so: the handle, the step launch (a Plan of kfpos_launch_plan.h as a kernel,
  * its grid and its LDS bytes: launch selection itself lives there), two of the three ways in
  * (synchronous host-buffer API, device-buffer API) and the C ABI of include/kfpos.h. The kernels live in
- * kfpos_k_*.hip (kfpos_kernels.h says which is where); the state side of the ABI (whole-bank accessors, per-tag lifecycle,
+ * kfpos_k_*.hip (kfpos_kargs.h says which is where); the state side of the ABI (whole-bank accessors, per-tag lifecycle,
  * pose for a row list) in kfpos_hip_state.hip; the streaming slots in kfpos_hip_slots.hip; the replay entry points
  * (kfpos_run_*_dev: whole schedules in few launches) in kfpos_hip_replay.hip; the RCCL pose gather in kfpos_comm.hip.
  */
@@ -16,7 +16,9 @@
 #include <type_traits>
 #include <vector>
 
-#include "kfpos_kernels.h"
+#include "kfpos_host.h"
+#include "kfpos_core.h" /* the per-tag arithmetic's own constants: iekf9_next_meet, ST_* */
+using namespace kfpos;
 
 std::string &kfpos_error_text() {
     thread_local std::string text;

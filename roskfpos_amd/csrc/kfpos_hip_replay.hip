@@ -5,12 +5,12 @@
  * checks plus what is its own; what they share is written once, above them: the validation of `kinds`, the two ranging
  * paths ahead of a replay kernel's first event, a family's replay plan (kfpos_launch_plan.h: form, grid, LDS bytes) as
  * its kernel, and the one loop that launches. How a schedule is cut into launches and how `kinds` travels: kfpos_replay_plan.h. No kernel lives
- * here: like kfpos_hip.hip this unit obtains them through the selectors of kfpos_kernels.h.
+ * here: like kfpos_hip.hip this unit obtains them through the selectors of kfpos_kargs.h.
  */
 #include <cstring>
 #include <string>
 
-#include "kfpos_kernels.h"
+#include "kfpos_host.h"
 
 namespace {
 

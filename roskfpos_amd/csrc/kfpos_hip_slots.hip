@@ -4,14 +4,14 @@
  * the one before that overlap (a whole-bank round may carry its ranges as int16 codes, KFPOS_SLOT_RANGES_D16: d16_*, below,
  * and kfpos_k_d16.hip). Whole-bank rounds and row-list rounds share the acquire, the round's part of the argument
  * block and the third stage; what a round may feed is decided by round_check, the row-list machinery (rows_check,
- * rows_reserve, rows_step) lives in kfpos_hip.hip, the lifecycle code it is built on in kfpos_hip_state.hip (kfpos_kernels.h
+ * rows_reserve, rows_step) lives in kfpos_hip.hip, the lifecycle code it is built on in kfpos_hip_state.hip (kfpos_host.h
  * declares both).
  */
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
-#include "kfpos_kernels.h"
+#include "kfpos_host.h"
 
 int drain_slots(kfpos_handle *h) {
     for (auto &sl : h->slot)

@@ -4,7 +4,7 @@
  * (kfpos_get_tags / kfpos_set_tags / kfpos_reset_tags; kernels: kfpos_k_tags.hip) and the pose for a row list
  * (kfpos_get_pose_rows / kfpos_get_predicted_rows; kernel: k_get_pose_rows, kfpos_k_misc.hip). How a tag's record is laid
  * out in the bank is not written down here: kfpos_state_record.h holds the table, the whole-bank accessors walk it on the
- * CPU, the per-tag calls hand it to their kernels. Staging goes over the routes of kfpos_hip.hip (Route, kfpos_kernels.h).
+ * CPU, the per-tag calls hand it to their kernels. Staging goes over the routes of kfpos_hip.hip (Route, kfpos_host.h).
  */
 #include <algorithm>
 #include <cmath>
@@ -13,7 +13,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "kfpos_kernels.h"
+#include "kfpos_host.h"
 
 using namespace kfpos_k;
 

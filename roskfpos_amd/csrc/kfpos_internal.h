@@ -1,8 +1,6 @@
 /*
- * kfpos_internal.h -- what the translation units of libkfpos_hip.so share and the ABI does not show: the handle.
- * (kfpos_k_*.hip: the kernels; kfpos_hip.hip: host side and filter entry points; kfpos_hip_state.hip: whole-bank
- * accessors, per-tag lifecycle, pose for a row list; kfpos_hip_slots.hip: the streaming
- * slots, kfpos_slot_*; kfpos_hip_replay.hip: the replay entry points, kfpos_run_*_dev; kfpos_comm.hip: the RCCL pose gather.)
+ * kfpos_internal.h -- what the host translation units of libkfpos_hip.so (kfpos_hip*.hip through kfpos_host.h, and
+ * kfpos_comm.hip) share and the ABI does not show: the handle. No kernel unit sees it. The list of units: kfpos_kargs.h.
  */
 #ifndef KFPOS_INTERNAL_H
 #define KFPOS_INTERNAL_H
@@ -15,8 +13,7 @@
 #include "../../include/kfpos.h"
 #include "kfpos_host_layout.h"
 
-#define KFPOS_TRACE_CHUNK 128 /* epochs per multi-epoch launch (their dt values travel in the kernel arguments) */
-#define KFPOS_N_SLOTS 3       /* streaming host API: one slot being filled, one on the bus, one computing / returning */
+#define KFPOS_N_SLOTS 3      /* streaming host API: one slot being filled, one on the bus, one computing / returning */
 
 /* thread-local text behind kfpos_last_error() */
 __attribute__((visibility("hidden"))) std::string &kfpos_error_text();

@@ -14,7 +14,7 @@
  * Indices are validated on the host before the launch (kfpos_hip_slots.hip: d16_check); no item touches an element
  * outside [0, n) whatever the list holds.
  */
-#include "kfpos_kernels.h"
+#include "kfpos_kargs.h"
 
 namespace {
 

@@ -303,8 +303,7 @@ __global__ __launch_bounds__(WAVE) void k_step_imu9(const ARGS a) {
         stcov<REAL>(a.P, k, 45, T, t32, tg.P.a[k]);
         fin &= isfinite(tg.P.a[k]);
     }
-    const bool waiting = !a.use_init_pos && isnan(tg.pos[0]);
-    if (!fin && !waiting) s |= ST_NONFINITE;
+    if (nonfinite_state(fin, a.use_init_pos, tg.pos[0])) s |= ST_NONFINITE;
     a.flags[t32] = fl | FL_STARTED;
     if (a.status) a.status[t32] = s;
 }

@@ -199,8 +199,7 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9_each(const kfpos_k::EvEach
                 for (int k = 0; k < 3; ++k) fin &= isfinite(tg.pos[k]) & isfinite(tg.vel[k]);
 #pragma unroll
                 for (int k = 0; k < 45; ++k) fin &= isfinite(tg.P.a[k]);
-                const bool waiting = !a.use_init_pos && isnan(tg.pos[0]);
-                w = (!fin && !waiting) ? (s | ST_NONFINITE) : s;
+                w = nonfinite_state(fin, a.use_init_pos, tg.pos[0]) ? (s | ST_NONFINITE) : s;
             }
             if (ev.status_events) (ev.status_events + (size_t)opaque_uniform(e) * T)[t32] = w;
             if (last_status) a.status[t32] = w;

@@ -142,7 +142,7 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9(const kfpos_k::EvArgs ev) 
             for (int k = 0; k < 3; ++k) fin &= isfinite(tg.pos[k]) & isfinite(tg.vel[k]);
 #pragma unroll
             for (int k = 0; k < 45; ++k) fin &= isfinite(tg.P.a[k]);
-            const bool waiting = !a.use_init_pos && isnan(tg.pos[0]);
+            const bool waiting = !a.use_init_pos && isnan(tg.pos[0]); /* (open text: nonfinite_state() here changes the kernel's code) */
             (ev.status_events + (size_t)opaque_uniform(e) * T)[t32] = (!fin && !waiting) ? (s | ST_NONFINITE) : s;
         }
         if constexpr (cov_is_rounded<REAL>()) { /* what single launches would have kept in HBM */
@@ -175,8 +175,7 @@ __global__ __launch_bounds__(WAVE) void k_events_imu9(const kfpos_k::EvArgs ev) 
         stcov<REAL>(a.P, k, 45, T, t32, tg.P.a[k]);
         fin &= isfinite(tg.P.a[k]);
     }
-    const bool waiting = !a.use_init_pos && isnan(tg.pos[0]);
-    if (!fin && !waiting) s |= ST_NONFINITE;
+    if (nonfinite_state(fin, a.use_init_pos, tg.pos[0])) s |= ST_NONFINITE;
     a.flags[t32] = fl | FL_STARTED;
     if (ev.status_events) (ev.status_events + (size_t)(n - 1) * T)[t32] = s;
     if (a.status) a.status[t32] = s;

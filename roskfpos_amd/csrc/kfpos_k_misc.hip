@@ -206,8 +206,7 @@ __global__ __launch_bounds__(WAVE) void k_step_planar(const KArgs a) {
         stcov<REAL>(a.P, k, 36, T, t32, tg.P.a[k]);
         fin &= isfinite(tg.P.a[k]);
     }
-    const bool waiting = !a.use_init_pos && isnan(tg.xy[0]);
-    if (!fin && !waiting) s |= ST_NONFINITE;
+    if (nonfinite_state(fin, a.use_init_pos, tg.xy[0])) s |= ST_NONFINITE;
     fl |= FL_STARTED;
     if constexpr (SENS) fl |= lt.has << PLANAR_HAS_SHIFT;
     a.flags[t] = fl;

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(WAVE) void k_events_planar(const kfpos_k::PevArgs e
                        isfinite(tg.vel[1]) & isfinite(tg.ang) & isfinite(tg.om);
 #pragma unroll
             for (int k = 0; k < 36; ++k) fin &= isfinite(tg.P.a[k]);
-            const bool waiting = !a.use_init_pos && isnan(tg.xy[0]);
+            const bool waiting = !a.use_init_pos && isnan(tg.xy[0]); /* (open text: nonfinite_state() here changes the kernel's code) */
             if (!drop && !fin && !waiting) s |= ST_NONFINITE;
             if (ev.status_events) (ev.status_events + (size_t)opaque_uniform(e) * T)[tl] = s;
         }

@@ -14,7 +14,7 @@
  * (kfpos_hip_state.hip: bank_transfer); elements are decoded and encoded through ldrow / strow / ldcov / stcov.
  * Row indices are validated on the host before any launch: no kernel sees a row outside [0, T).
  */
-#include "kfpos_kernels.h"
+#include "kfpos_stored.h"
 
 namespace {
 

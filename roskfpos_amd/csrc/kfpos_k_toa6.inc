@@ -92,8 +92,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 2))) vo
         stcov<REAL>(a.P, k, Cov<6, SYMM>::SZ, T, ts, tg.P.a[k]);
         fin &= isfinite(tg.P.a[k]);
     }
-    const bool waiting = !a.use_init_pos && isnan(tg.pos[0]); /* still waiting for its ML initialisation */
-    if (!fin && !waiting) s |= ST_NONFINITE;
+    if (nonfinite_state(fin, a.use_init_pos, tg.pos[0])) s |= ST_NONFINITE;
     a.flags[t] = fl0 | FL_STARTED;
     if (a.status) a.status[t] = s;
 }

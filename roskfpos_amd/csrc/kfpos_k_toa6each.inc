@@ -87,7 +87,7 @@ __global__ __launch_bounds__(WAVE) void k_trace_toa6_each(const kfpos_k::TraceEa
                 for (int k = 0; k < 3; ++k) fin &= isfinite(tg.pos[k]);
 #pragma unroll
                 for (int k = 0; k < SZ; ++k) fin &= isfinite(tg.P.a[k]);
-                const bool waiting = !a.use_init_pos && isnan(tg.pos[0]); /* still waiting for its ML initialisation */
+                const bool waiting = !a.use_init_pos && isnan(tg.pos[0]); /* still waiting for its ML initialisation (open text: nonfinite_state() here changes the kernel's code) */
                 if (run && !fin && !waiting) s |= ST_NONFINITE;
             }
             if (ev.status_events) (ev.status_events + (size_t)opaque_uniform(e) * T)[tl] = s;

@@ -1,7 +1,7 @@
 /*
  * kfpos_launch_plan.h -- launch selection: which instantiation a handle runs for a launch, over how many workgroups, with
  * how many bytes of dynamic LDS. One function from (what the handle is, what is launched) to a Plan; the host units map a
- * Plan to a function pointer through the selectors of kfpos_kernels.h and launch it, and compute neither a form nor a
+ * Plan to a function pointer through the selectors of kfpos_kargs.h and launch it, and compute neither a form nor a
  * byte count themselves. Pure arithmetic: no HIP header, g++ compiles it alone (tests/launch/launch_driver.cpp walks
  * every configuration against a table read from the kernels). The plan takes no tag count: a row-list step of n tags
  * runs the whole bank's kernel by signature.
@@ -50,7 +50,7 @@ struct Inputs {
 enum Launch : int { STEP_RANGING, STEP_IMU_ONLY, STEP_SENSOR, TRACE6_EACH, EVENTS9, EVENTS_PLANAR };
 
 struct Plan {
-    int as, heur;                     /* the selectors' arguments (kfpos_kernels.h) ... */
+    int as, heur;                     /* the selectors' arguments (kfpos_kargs.h) ... */
     bool sensors, ranging, two_waves; /* ... planar_kernel, imu9_kernel, toa6_sym_kernel */
     int tags_per_group;
     size_t epoch_doubles, park_doubles;

@@ -15,7 +15,7 @@
 #define KFPOS_HD
 #endif
 
-#define KFPOS_PLAN_MAX_EVENTS 128 /* events per launch at the most: KFPOS_TRACE_CHUNK (kfpos_kernels.h asserts it) */
+#define KFPOS_PLAN_MAX_EVENTS 128 /* events per launch at the most: KFPOS_TRACE_CHUNK (kfpos_kargs.h asserts it) */
 #define KFPOS_PLAN_MAX_KINDS 5    /* the planar filter's: ranging, PX4Flow, IMU, magnetometer, compass */
 
 /* ---- 9-state schedules (EvArgs, EvEachArgs): one bit per event, 0 = KFPOS_EVENT_IMU, 1 = KFPOS_EVENT_TOA ---- */

@@ -4,6 +4,7 @@ to share a SIMD two at a time still fit twice. Neither can be seen by a parity t
 wavefront computes the same bits 25-40 % slower -- so the rules themselves are tested: they hold for the library as
 built, and they do fire."""
 import os
+import re
 import subprocess
 import sys
 
@@ -17,8 +18,15 @@ import check_scratch  # noqa: E402
 from disasm_fragment import FMA, NAME, NAME_P48, Fragment  # noqa: E402
 
 
+def _units():
+    """the translation units of the library, as the Makefile lists them"""
+    line = next(l for l in open(os.path.join(CSRC, "Makefile")) if l.startswith("UNITS"))
+    return line.split(":=")[1].split()
+
+
 def _built():
-    if not (os.path.exists(os.path.join(CSRC, "libkfpos_hip.so")) and os.path.exists(os.path.join(CSRC, "build.log"))):
+    have = ["libkfpos_hip.so", "build.log"] + [u + ".d" for u in _units()]
+    if not all(os.path.exists(os.path.join(CSRC, f)) for f in have):
         import __graft_entry__
         __graft_entry__.build()
 
@@ -139,3 +147,59 @@ def test_check_kernels_names_the_one_broken_rule_and_still_judges_the_others(tmp
     assert lines[:5] == verdicts[:5] and lines[-1] == verdicts[6], bad.stdout
     assert lines[5] == "the 9-state epoch loop carries too much across its back-edge in registers:", bad.stdout
     assert len(lines) == 8 and lines[6].startswith(NAME_P48) and "60 register copies (maximum 32)" in lines[6], bad.stdout
+
+
+def _headers_seen(unit):
+    """the project files unit.hip includes, as the compiler lists them (its own headers carry absolute paths)"""
+    res = subprocess.run(["hipcc", "-MM", "--offload-arch=gfx950", "-std=c++17", unit + ".hip"], cwd=CSRC,
+                         capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    words = res.stdout.replace("\\\n", " ").split()
+    seen = {w for w in words if not w.startswith(("/", "#")) and not w.endswith((":", ".hip"))
+            and (w.endswith((".h", ".inc")))}
+    assert seen, res.stdout
+    return seen
+
+
+def test_a_kernel_unit_sees_no_host_header_and_a_host_unit_no_device_header():
+    """what the split of kfpos_kernels.h promises: the handle and the host glue are out of every kernel unit's sight, the
+    two kernel units that run no filter see none of the per-tag arithmetic, and the host units see no device helper"""
+    units = _units()
+    kernels = [u for u in units if u.startswith("kfpos_k_")]
+    hosts = [u for u in units if u.startswith("kfpos_hip")]
+    assert len(kernels) == 16 and len(hosts) == 4, units
+    for u in kernels + hosts:
+        seen = _headers_seen(u)
+        for h in seen:
+            assert os.path.exists(os.path.join(CSRC, h)), (u, h)
+        names = {os.path.basename(h) for h in seen}
+        if u in kernels:
+            assert not names & {"kfpos_internal.h", "kfpos_host.h"}, (u, sorted(names))
+            assert "kfpos_kargs.h" in names, (u, sorted(names))
+        if u in ("kfpos_k_d16", "kfpos_k_tags"):
+            assert not [h for h in names if h.startswith("kfpos_core")], (u, sorted(names))
+        if u in hosts:
+            assert "kfpos_kernels.h" not in names and {"kfpos_host.h", "kfpos_internal.h"} <= names, (u, sorted(names))
+
+
+def _would_rebuild(*touched):
+    """the units `make` would compile again if these headers were newer than everything (a dry run: nothing is built)"""
+    cmd = ["make", "-n", "-C", CSRC]
+    for h in touched:
+        cmd += ["-W", h]
+    res = subprocess.run(cmd + ["libkfpos_hip.so"], capture_output=True, text=True)
+    assert res.returncode == 0, res.stdout + res.stderr
+    return set(re.findall(r"-c -o (\w+)\.o ", res.stdout))
+
+
+def test_a_touched_header_rebuilds_its_side_only():
+    """the Makefile takes each unit's headers from the compiler (%.d): a host-side edit reaches no kernel unit, an edit to
+    the device helpers no host unit"""
+    _built()
+    assert _would_rebuild() == set(), "the library as built is up to date"
+    host = _would_rebuild("kfpos_internal.h", "kfpos_host.h")
+    assert host == {"kfpos_hip", "kfpos_hip_state", "kfpos_hip_slots", "kfpos_hip_replay", "kfpos_comm"}, sorted(host)
+    device = _would_rebuild("kfpos_kernels.h")
+    assert device and all(u.startswith("kfpos_k_") for u in device), sorted(device)
+    assert {"kfpos_k_imu9", "kfpos_k_toa6s", "kfpos_k_misc", "kfpos_k_coop"} <= device, sorted(device)
+    assert not device & {"kfpos_k_d16", "kfpos_k_tags"}, sorted(device)
