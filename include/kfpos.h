@@ -146,7 +146,11 @@ typedef struct kfpos_planar_config {
 
 typedef struct kfpos_handle kfpos_handle;
 
-/* ---- lifetime: PosGenerator::setAlgorithm (Posgenerator.cpp:510-538) ---- */
+/* ---- lifetime: PosGenerator::setAlgorithm (Posgenerator.cpp:510-538) ----
+ * kfpos_create answers, in this order: KFPOS_ERR_ARG for a null argument, for a configuration it refuses and for a bad
+ * KFPOS_PAIR9_MEET (kfpos_last_error says which), KFPOS_ERR_NO_DEVICE, KFPOS_ERR_HIP where an allocation failed. Every
+ * KFPOS_* environment variable that bears on a handle is read here, once -- KFPOS_SLOT_SPLIT_BYTES included, which
+ * setting between kfpos_create and the first slot call therefore does not change (README.md lists them). */
 int kfpos_create(const kfpos_config *cfg, kfpos_handle **out);
 int kfpos_destroy(kfpos_handle *h);
 /* PositionEstimationAlgorithm::init(). Returns KFPOS_OK (the reference's `true`). */

@@ -170,11 +170,19 @@ struct kfpos_comm {
     int world = 1, rank = 0, device = 0;
     long long total = 0, base = 0, t_local = 0, t_pad = 0; /* set by kfpos_comm_set_total */
     int rem = 0;
-    hipStream_t side = nullptr;
-    hipEvent_t ready[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
+    Stream side;
+    Event ready[2], done[2];
     bool used[2] = {false, false};
-    double *send[2] = {nullptr, nullptr}, *staged[2] = {nullptr, nullptr};
+    DevPtr<double> send[2], staged[2];
     size_t cap_rows = 0; /* rows the buffers are sized for */
+    void drop_buffers() { /* the one place that frees the two sets: the caller has made sure nothing still reads them */
+        for (int b = 0; b < 2; ++b) {
+            send[b].reset();
+            staged[b].reset();
+            used[b] = false;
+        }
+        cap_rows = 0;
+    }
     unsigned long long calls = 0;
     int last = -1; /* buffer set of the last gather */
     int algo = KFPOS_GATHER_COLLECTIVE; /* how the blocks travel: kfpos_comm_set_algorithm */
@@ -186,10 +194,10 @@ int comm_finish_init(kfpos_comm *c) {
     KfposDevScope dev(c->device);
     const char *algo = getenv("KFPOS_GATHER_ALGO");
     if (algo && std::strcmp(algo, "direct") == 0) c->algo = KFPOS_GATHER_DIRECT;
-    HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(c->side.out(), hipStreamNonBlocking));
     for (int b = 0; b < 2; ++b) {
-        HIPCHK(hipEventCreateWithFlags(&c->ready[b], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->done[b], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(c->ready[b].out(), hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(c->done[b].out(), hipEventDisableTiming));
     }
     return KFPOS_OK;
 }
@@ -198,17 +206,11 @@ int comm_reserve(kfpos_comm *c, int rows) {
     if ((size_t)rows <= c->cap_rows) return KFPOS_OK;
     /* growing: nothing may still be reading the old buffers */
     HIPCHK(hipStreamSynchronize(c->side));
-    for (int b = 0; b < 2; ++b) {
-        if (c->send[b]) (void)hipFree(c->send[b]);
-        if (c->staged[b]) (void)hipFree(c->staged[b]);
-        c->send[b] = c->staged[b] = nullptr;
-        c->used[b] = false;
-    }
-    c->cap_rows = 0;
+    c->drop_buffers();
     const size_t one = (size_t)rows * c->t_pad * sizeof(double);
     for (int b = 0; b < 2; ++b) {
-        HIPCHK(hipMalloc((void **)&c->send[b], one));
-        HIPCHK(hipMalloc((void **)&c->staged[b], one * c->world));
+        HIPCHK(hipMalloc((void **)c->send[b].out(), one));
+        HIPCHK(hipMalloc((void **)c->staged[b].out(), one * c->world));
     }
     c->cap_rows = rows;
     return KFPOS_OK;
@@ -408,14 +410,7 @@ int kfpos_comm_destroy(kfpos_comm *c) {
     KfposDevScope dev(c->device);
     if (c->side) (void)hipStreamSynchronize(c->side);
     if (c->nccl) (void)rccl().CommDestroy(c->nccl);
-    for (int b = 0; b < 2; ++b) {
-        if (c->send[b]) (void)hipFree(c->send[b]);
-        if (c->staged[b]) (void)hipFree(c->staged[b]);
-        if (c->ready[b]) (void)hipEventDestroy(c->ready[b]);
-        if (c->done[b]) (void)hipEventDestroy(c->done[b]);
-    }
-    if (c->side) (void)hipStreamDestroy(c->side);
-    delete c;
+    delete c; /* buffers, events, the side stream: each member gives back what it owns (kfpos_internal.h) */
     return KFPOS_OK;
 }
 
@@ -444,13 +439,7 @@ int kfpos_comm_set_total(kfpos_comm *c, int64_t total_tags, int64_t *lo, int64_t
     c->rem = (int)(total_tags % c->world);
     c->t_local = u - l;
     c->t_pad = c->base + (c->rem ? 1 : 0);
-    for (int b = 0; b < 2; ++b) { /* buffers are sized by t_pad: start over */
-        if (c->send[b]) (void)hipFree(c->send[b]);
-        if (c->staged[b]) (void)hipFree(c->staged[b]);
-        c->send[b] = c->staged[b] = nullptr;
-        c->used[b] = false;
-    }
-    c->cap_rows = 0;
+    c->drop_buffers(); /* buffers are sized by t_pad: start over */
     if (lo) *lo = l;
     if (hi) *hi = u;
     return KFPOS_OK;

@@ -14,6 +14,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "kfpos_host.h"
@@ -36,10 +37,10 @@ void fill_args(const kfpos_handle *h, KArgs &a) {
     a.ignore_worst = h->cfg.ignore_worst;
     a.top_n = h->cfg.top_n;
     a.ml_variant = h->cfg.model == KFPOS_MODEL_ML ? h->cfg.ml_variant : 0;
-    a.pair9 = h->pair9 ? 1 : 0;
-    a.pair9_first = (short)h->pair9_first;
-    a.pair9_dense_until = (short)h->pair9_dense_until;
-    a.imu9_diag = h->imu9_diag ? 1 : 0;
+    a.pair9 = h->policy.pair9 ? 1 : 0;
+    a.pair9_first = (short)h->policy.pair9_first;
+    a.pair9_dense_until = (short)h->policy.pair9_dense_until;
+    a.imu9_diag = h->policy.imu9_diag ? 1 : 0;
     a.use_init_pos = h->cfg.use_init_pos;
     a.use_fixed_height = h->planar.use_fixed_height;
     a.imu_fixed_cov_acc = h->planar.imu_use_fixed_cov_acc;
@@ -83,7 +84,7 @@ step_kernel_t step_kernel(const kfpos_handle *h, const kfpos_plan::Plan &p) {
     if (h->cfg.model == KFPOS_MODEL_PLANAR) return kfpos_k::planar_kernel(st, p.sensors, p.as);
     if (h->cfg.model == KFPOS_MODEL_ML) return kfpos_k::ml_kernel(st, p.as);
     if (h->cfg.model == KFPOS_MODEL_TOA_IMU) return kfpos_k::imu9_kernel(st, p.as, p.ranging);
-    if (h->coop) return kfpos_k::toa6_coop_kernel(st);
+    if (h->policy.coop) return kfpos_k::toa6_coop_kernel(st);
     return h->full ? kfpos_k::toa6_full_kernel(st, p.as, p.heur) : kfpos_k::toa6_sym_kernel(st, p.as, p.heur, p.two_waves);
 }
 
@@ -147,10 +148,9 @@ int stage_region(kfpos_handle *h, size_t bytes, void **out) {
         /* grow: everything queued so far still reads the old buffer, so drain first */
         HIPCHK(hipDeviceSynchronize());
         const size_t cap = (h->stage_used + bytes) * 2;
-        unsigned char *nb = nullptr;
-        HIPCHK(hipMalloc((void **)&nb, cap));
-        if (h->d_stage) (void)hipFree(h->d_stage);
-        h->d_stage = nb;
+        DevPtr<unsigned char> nb;
+        HIPCHK(hipMalloc((void **)nb.out(), cap));
+        h->d_stage = std::move(nb);
         h->stage_cap = cap;
         h->stage_used = 0; /* regions handed out before the growth have been consumed (synchronised above) */
     }
@@ -190,141 +190,16 @@ Route route_of(kfpos_handle *h) {
 
 namespace {
 
-size_t small_bank_limit() { /* elements of the range matrix (n_tags x max_anchors) up to which a bank is "small" */
-    const char *e = getenv("KFPOS_SMALL_BANK_ELEMS");
-    return e ? (size_t)atol(e) : 4096;
-}
+static_assert(kfpos_policy::TRACE_CHUNK_MAX == KFPOS_TRACE_CHUNK, "Policy::trace_chunk: what the argument blocks hold");
 
-/* The meeting points of the 9-state pairs' tail (iekf9_next_meet): KFPOS_PAIR9_MEET=first,dense_until, unset or empty =
- * the default (8,10: after 8, 9 and 10 solves, then every 4; 8,8 = the schedule before this one: 8, then every 4; the
- * counters of profiles/imu9_pairs_meet_pmc.json chose it). false: not two integers with 1 <= first <= dense_until <= 20 (the cap of the gain iteration). */
-constexpr int PAIR9_MEET_FIRST = 8, PAIR9_MEET_DENSE_UNTIL = 10, PAIR9_MEET_MAX = 20;
-bool pair9_meet(int *first, int *dense_until) {
-    *first = PAIR9_MEET_FIRST;
-    *dense_until = PAIR9_MEET_DENSE_UNTIL;
-    const char *e = getenv("KFPOS_PAIR9_MEET");
-    if (!e || !e[0]) return true;
-    char rest = 0;
-    if (std::sscanf(e, "%d,%d%c", first, dense_until, &rest) != 2) return false;
-    return 1 <= *first && *first <= *dense_until && *dense_until <= PAIR9_MEET_MAX;
-}
-} // namespace
-
-extern "C" {
-
-const char *kfpos_last_error(void) { return g_err.c_str(); }
-const char *kfpos_strerror(int code) {
-    switch (code) {
-    case KFPOS_OK: return "ok";
-    case KFPOS_ERR_ARG: return "invalid argument";
-    case KFPOS_ERR_HIP: return "HIP runtime error";
-    case KFPOS_ERR_NO_DEVICE: return "no usable GPU";
-    case KFPOS_ERR_MODEL: return "call not defined for this model";
-    case KFPOS_ERR_STATE: return "call out of sequence";
-    case KFPOS_ERR_COMM: return "RCCL error";
-    default: return "unknown error";
-    }
-}
-int kfpos_version(void) { return KFPOS_VERSION; }
-int kfpos_pair9_meet_points(int32_t first, int32_t dense_until, int32_t *out) {
-    if (!out || first < 1 || first > dense_until || dense_until > PAIR9_MEET_MAX) return -1;
-    int n = 0;
-    int stop = first;
-    for (;;) { /* as iekf9_info walks it with max_steps = 20 */
-        out[n++] = stop;
-        if (stop >= PAIR9_MEET_MAX) return n;
-        stop = iekf9_next_meet(stop, dense_until, PAIR9_MEET_MAX);
-    }
-}
-
-int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
-    if (!cfg || !out) return KFPOS_ERR_ARG;
-    *out = nullptr;
-    g_err.clear();
-    auto bad = [](const char *why) {
-        g_err = why;
-        return KFPOS_ERR_ARG;
-    };
-    if (cfg->model != KFPOS_MODEL_TOA && cfg->model != KFPOS_MODEL_TOA_IMU && cfg->model != KFPOS_MODEL_ML &&
-        cfg->model != KFPOS_MODEL_PLANAR)
-        return bad("kfpos_config.model is not one of KFPOS_MODEL_*");
-    if (cfg->storage != KFPOS_STORE_F64 && cfg->storage != KFPOS_STORE_F32 && cfg->storage != KFPOS_STORE_MIXED &&
-        cfg->storage != KFPOS_STORE_P48)
-        return bad("kfpos_config.storage is not one of KFPOS_STORE_*");
-    if (cfg->n_tags < 1) return bad("kfpos_config.n_tags must be >= 1");
-    if (cfg->max_anchors < 1 || cfg->max_anchors > KFPOS_MAX_ANCHORS)
-        return bad("kfpos_config.max_anchors must be 1..64 (MAX_NUM_ANCS, Posgenerator.h:74)");
-    if (cfg->top_n < 0) return bad("kfpos_config.top_n must be >= 0");
-    if (cfg->ml_variant != KFPOS_ML_NORMAL && cfg->ml_variant != KFPOS_ML_IGNORE_N && cfg->ml_variant != KFPOS_ML_BEST)
-        return bad("kfpos_config.ml_variant is not one of KFPOS_ML_*");
-    if (cfg->ml_variant != KFPOS_ML_NORMAL && cfg->model != KFPOS_MODEL_ML)
-        return bad("kfpos_config.ml_variant belongs to KFPOS_MODEL_ML (MLLocation's variants, MLLocation.h:5-7)");
-    if ((cfg->model == KFPOS_MODEL_TOA_IMU && (cfg->top_n || cfg->ignore_worst)) ||
-        (cfg->model == KFPOS_MODEL_ML && cfg->ignore_worst) ||
-        (cfg->model == KFPOS_MODEL_PLANAR && (cfg->top_n || cfg->ignore_worst)))
-        return bad("ignore_worst exists for the 6-state filter only, top_n for the 6-state filter and the ML estimator");
-    int meet_first, meet_dense_until;
-    if (!pair9_meet(&meet_first, &meet_dense_until))
-        return bad("KFPOS_PAIR9_MEET must be first,dense_until with 1 <= first <= dense_until <= 20");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) {
-        g_err = "no HIP device";
-        return KFPOS_ERR_NO_DEVICE;
-    }
-    DevScope dev_(cfg->device); /* the caller's current device is left as it was */
-    kfpos_handle *h = new (std::nothrow) kfpos_handle();
-    if (!h) return KFPOS_ERR_ARG;
-    h->cfg = *cfg;
-    h->n = cfg->model == KFPOS_MODEL_TOA_IMU ? 9 : (cfg->model == KFPOS_MODEL_ML ? 3 : (cfg->model == KFPOS_MODEL_PLANAR ? 8 : 6));
-    h->full = (cfg->model == KFPOS_MODEL_TOA && !cfg->use_init_pos) ? 1 : 0;
-    h->psz = h->full ? h->n * h->n : h->n * (h->n + 1) / 2;
-    h->rsz = cfg->storage == KFPOS_STORE_F32 ? 4 : (cfg->storage == KFPOS_STORE_P48 ? 6 : 8);
-    h->msz = cfg->storage == KFPOS_STORE_F64 ? 8 : 4;
-    h->A = 0;
-    h->have_anchors = false;
-    h->stepped = false;
-    {
-        const char *g = getenv("KFPOS_GENERIC_KERNEL");
-        h->force_generic = g && g[0] == '1';
-        /* one combination has no anchor-count-specialised kernel: ML start (36-entry covariance + its SVD scratchpad) with
-         * leave-one-out and the 48-bit covariance -- the LDS-resident 8-anchor instantiation would touch scratch memory
-         * inside its epoch loop (make check), the run-time-loop kernel does not */
-        if (h->full && cfg->ignore_worst && cfg->storage == KFPOS_STORE_P48) h->force_generic = true;
-        {
-            hipDeviceProp_t prop;
-            const char *ow = getenv("KFPOS_ONE_WAVE_BUILD");
-            h->two_waves = false;
-            if (!(ow && ow[0] == '1') && hipGetDeviceProperties(&prop, cfg->device) == hipSuccess)
-                h->two_waves = ((size_t)cfg->n_tags + WAVE - 1) / WAVE > (size_t)prop.multiProcessorCount * 4;
-        }
-        /* the pairs' tail of the 9-state gain iteration (8 anchors): on where it was measured to win -- the two kernels
-         * whose pair trips read registers only (4-byte measurements with an 8- or 6-byte covariance); the other two
-         * storage modes keep it opt-in. KFPOS_PAIR9=0 / =1 overrides either way */
-        const char *np = getenv("KFPOS_PAIR9");
-        h->pair9 = np && np[0] ? np[0] == '1'
-                               : (cfg->storage == KFPOS_STORE_MIXED || cfg->storage == KFPOS_STORE_P48);
-        /* where the lanes of a wavefront meet to look for the hand-over: KFPOS_PAIR9_MEET (validated above) */
-        h->pair9_first = meet_first;
-        h->pair9_dense_until = meet_dense_until;
-        const char *nd = getenv("KFPOS_IMU9_DIAG");
-        h->imu9_diag = !(nd && nd[0] == '0');
-        const char *nc = getenv("KFPOS_NO_COOP");
-        /* up to 8 192 tags (1024 groups-of-8 wavefronts = one per SIMD) 8 lanes per tag pay off: 4.4-5.0 us per epoch
-         * against 7.5 us; at 16 384 the one-tag-per-lane grid wins again (7.7 vs 8.3 us, measured) */
-        h->coop = !(nc && nc[0] == '1') && !h->force_generic && cfg->model == KFPOS_MODEL_TOA && cfg->use_init_pos &&
-                  !cfg->ignore_worst && !cfg->top_n && cfg->max_anchors <= COOP_LANES && cfg->n_tags <= 8192;
-        const char *c = getenv("KFPOS_TRACE_CHUNK_STEPS");
-        int n = c ? atoi(c) : KFPOS_TRACE_CHUNK;
-        h->trace_chunk = n < 1 ? 1 : (n > KFPOS_TRACE_CHUNK ? KFPOS_TRACE_CHUNK : n);
-    }
-    std::memset(h->anchors, 0, sizeof(h->anchors));
-    const size_t T = cfg->n_tags, A = cfg->max_anchors, r = h->rsz, m = h->msz;
+/* kfpos_create, third part: everything the bank owns from its first call on (the rest comes with its first use), zeroed */
+int bank_allocate(kfpos_handle *h) {
+    const size_t T = h->cfg.n_tags, A = h->cfg.max_anchors, r = h->rsz, m = h->msz;
 #define ALLOC(ptr, bytes)                                                     \
     do {                                                                      \
-        hipError_t e_ = hipMalloc((void **)&(ptr), (bytes));                  \
+        hipError_t e_ = hipMalloc((void **)(ptr).out(), (bytes));             \
         if (e_ != hipSuccess) {                                               \
             g_err = std::string("hipMalloc: ") + hipGetErrorString(e_);       \
-            kfpos_destroy(h);                                                 \
             return KFPOS_ERR_HIP;                                             \
         }                                                                     \
         (void)hipMemset((ptr), 0, (bytes));                                   \
@@ -351,25 +226,26 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
     ALLOC(h->d_out, 15 * T * sizeof(double));
     ALLOC(h->d_status, T * sizeof(uint32_t));
 #undef ALLOC
-    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
+    if (hipEventCreate(h->ev0.out()) != hipSuccess || hipEventCreate(h->ev1.out()) != hipSuccess) {
         g_err = "hipEventCreate failed";
-        kfpos_destroy(h);
         return KFPOS_ERR_HIP;
     }
-    if (T * A <= small_bank_limit()) { /* small bank: one mapped block instead of staging copies (kfpos_handle::sm_*) */
+    if (T * A <= h->policy.small_bank_elems) { /* small bank: one mapped block instead of staging copies (kfpos_handle::sm_*) */
         h->sm = kfpos_layout::mapped_layout(handle_sizes(h));
-        const size_t off = h->sm.bytes;
-        void *hp = nullptr, *dp = nullptr;
-        if (hipHostMalloc(&hp, off, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
+        void *dp = nullptr;
+        if (hipHostMalloc((void **)h->sm_h.out(), h->sm.bytes, hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer(&dp, h->sm_h, 0) != hipSuccess) {
             g_err = "hipHostMalloc(mapped block of a small bank) failed";
-            if (hp) (void)hipHostFree(hp);
-            kfpos_destroy(h);
             return KFPOS_ERR_HIP;
         }
-        std::memset(hp, 0, off);
-        h->sm_h = (unsigned char *)hp;
+        std::memset(h->sm_h, 0, h->sm.bytes);
         h->sm_d = (unsigned char *)dp;
     }
+    return KFPOS_OK;
+}
+
+/* ... and fourth: the kernels' LDS allowance and the bank's initial position */
+int bank_seed(kfpos_handle *h) {
     /* every step launch this handle can ever make -- ranging, IMU-only, sensor call, ranging after a sensor sample --:
      * a kernel whose plan takes more than 64 KB of LDS is allowed them here, once */
     const kfpos_plan::Launch may[4] = {kfpos_plan::STEP_RANGING, kfpos_plan::STEP_IMU_ONLY, kfpos_plan::STEP_SENSOR, kfpos_plan::STEP_RANGING};
@@ -381,26 +257,98 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
         hipError_t e_ = hipFuncSetAttribute((const void *)step_kernel(h, p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.bytes());
         if (e_ != hipSuccess) {
             g_err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(e_);
-            kfpos_destroy(h);
             return KFPOS_ERR_HIP;
         }
     }
     /* initial position: fixed start (P0 = 0) or NaN until the ML initialisation */
+    const size_t T = h->cfg.n_tags;
     std::vector<double> p0(3 * T);
     for (size_t t = 0; t < T; ++t)
         for (int k = 0; k < 3; ++k) {
-            p0[(size_t)k * T + t] = cfg->use_init_pos ? cfg->init_pos[k] : NAN;
+            p0[(size_t)k * T + t] = h->cfg.use_init_pos ? h->cfg.init_pos[k] : NAN;
             if (h->n == 8 && k == 2) p0[(size_t)k * T + t] = 0.0; /* mUWBtagZ: kfpos_set_planar, not initialPosition.z */
         }
     if (h->n == 3 && hipMemcpy(h->d_vel, p0.data(), p0.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
         g_err = "hipMemcpy(ml seed) failed";
-        kfpos_destroy(h);
         return KFPOS_ERR_HIP;
     }
     if (hipMemcpy(h->d_pos, p0.data(), p0.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
         g_err = "hipMemcpy(init pos) failed";
-        kfpos_destroy(h);
         return KFPOS_ERR_HIP;
+    }
+    return KFPOS_OK;
+}
+} // namespace
+
+extern "C" {
+
+const char *kfpos_last_error(void) { return g_err.c_str(); }
+const char *kfpos_strerror(int code) {
+    switch (code) {
+    case KFPOS_OK: return "ok";
+    case KFPOS_ERR_ARG: return "invalid argument";
+    case KFPOS_ERR_HIP: return "HIP runtime error";
+    case KFPOS_ERR_NO_DEVICE: return "no usable GPU";
+    case KFPOS_ERR_MODEL: return "call not defined for this model";
+    case KFPOS_ERR_STATE: return "call out of sequence";
+    case KFPOS_ERR_COMM: return "RCCL error";
+    default: return "unknown error";
+    }
+}
+int kfpos_version(void) { return KFPOS_VERSION; }
+int kfpos_pair9_meet_points(int32_t first, int32_t dense_until, int32_t *out) {
+    using kfpos_policy::PAIR9_MEET_MAX;
+    if (!out || !kfpos_policy::pair9_meet_ok(first, dense_until)) return -1;
+    int n = 0;
+    int stop = first;
+    for (;;) { /* as iekf9_info walks it with max_steps = 20 */
+        out[n++] = stop;
+        if (stop >= PAIR9_MEET_MAX) return n;
+        stop = iekf9_next_meet(stop, dense_until, PAIR9_MEET_MAX);
+    }
+}
+
+/* validate, decide (both kfpos_policy.h), allocate, seed. Answers in this order: a null argument, a configuration refusal,
+ * a KFPOS_PAIR9_MEET refusal, KFPOS_ERR_NO_DEVICE, allocation */
+int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
+    if (!cfg || !out) return KFPOS_ERR_ARG;
+    *out = nullptr;
+    g_err.clear();
+    auto bad = [](const char *why) {
+        g_err = why;
+        return KFPOS_ERR_ARG;
+    };
+    if (const char *why = kfpos_policy::config_refusal(*cfg)) return bad(why);
+    int ndev = 0;
+    const bool have_dev = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && cfg->device >= 0 && cfg->device < ndev;
+    hipDeviceProp_t prop;
+    const size_t wave_slots = have_dev && hipGetDeviceProperties(&prop, cfg->device) == hipSuccess ? (size_t)prop.multiProcessorCount * 4 : 0;
+    kfpos_policy::Policy policy; /* every KFPOS_* variable of the handle is read here, once */
+    if (!kfpos_policy::policy(*cfg, wave_slots, [](const char *name) -> const char * { return getenv(name); }, &policy))
+        return bad(kfpos_policy::PAIR9_MEET_REFUSAL);
+    if (!have_dev) {
+        g_err = "no HIP device";
+        return KFPOS_ERR_NO_DEVICE;
+    }
+    DevScope dev_(cfg->device); /* the caller's current device is left as it was */
+    kfpos_handle *h = new (std::nothrow) kfpos_handle();
+    if (!h) return KFPOS_ERR_ARG;
+    h->cfg = *cfg;
+    h->policy = policy;
+    h->n = cfg->model == KFPOS_MODEL_TOA_IMU ? 9 : (cfg->model == KFPOS_MODEL_ML ? 3 : (cfg->model == KFPOS_MODEL_PLANAR ? 8 : 6));
+    h->full = kfpos_policy::full_layout(*cfg) ? 1 : 0;
+    h->psz = h->full ? h->n * h->n : h->n * (h->n + 1) / 2;
+    h->rsz = cfg->storage == KFPOS_STORE_F32 ? 4 : (cfg->storage == KFPOS_STORE_P48 ? 6 : 8);
+    h->msz = cfg->storage == KFPOS_STORE_F64 ? 8 : 4;
+    h->A = 0;
+    h->have_anchors = false;
+    h->stepped = false;
+    std::memset(h->anchors, 0, sizeof(h->anchors));
+    int rc = bank_allocate(h);
+    if (rc == KFPOS_OK) rc = bank_seed(h);
+    if (rc) { /* what it owns so far goes with it */
+        kfpos_destroy(h);
+        return rc;
     }
     *out = h;
     return KFPOS_OK;
@@ -408,35 +356,9 @@ int kfpos_create(const kfpos_config *cfg, kfpos_handle **out) {
 
 int kfpos_destroy(kfpos_handle *h) {
     if (!h) return KFPOS_ERR_ARG;
-    void *ptrs[] = {h->d_pos, h->d_vel, h->d_P, h->d_imu_acc, h->d_imu_cov, h->d_flags, h->d_ranges,
-                    h->d_err, h->d_accel, h->d_cov, h->d_dt, h->d_out, h->d_status, h->d_latch, h->d_sensor,
-                    h->d_stage, h->d_work, h->d_cell_xyz, h->d_cell_of_block};
     DevScope dev_(h->cfg.device);
     (void)hipDeviceSynchronize(); /* nothing of this handle may still be in flight (streaming slots) */
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (h->sm_h) (void)hipHostFree(h->sm_h);
-    for (auto &sl : h->slot) {
-        if (sl.host) (void)hipHostFree(sl.host);
-        if (sl.rows) (void)hipHostFree(sl.rows);
-        if (sl.pose_host) (void)hipHostFree(sl.pose_host);
-        if (sl.pose_dev) (void)hipFree(sl.pose_dev);
-        if (sl.d16_host) (void)hipHostFree(sl.d16_host);
-        if (sl.d16_dev) (void)hipFree(sl.d16_dev);
-        if (sl.dev) (void)hipFree(sl.dev);
-        if (sl.copied) (void)hipEventDestroy(sl.copied);
-        if (sl.copied2) (void)hipEventDestroy(sl.copied2);
-        if (sl.computed) (void)hipEventDestroy(sl.computed);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    if (h->d16_base) (void)hipFree(h->d16_base);
-    if (h->s_copy) (void)hipStreamDestroy(h->s_copy);
-    if (h->s_copy2) (void)hipStreamDestroy(h->s_copy2);
-    if (h->s_comp) (void)hipStreamDestroy(h->s_comp);
-    if (h->s_back) (void)hipStreamDestroy(h->s_back);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    delete h;
+    delete h; /* every member that owns something gives it back (kfpos_internal.h) */
     return KFPOS_OK;
 }
 
@@ -473,7 +395,7 @@ int kfpos_set_anchor_cells(kfpos_handle *h, int32_t n_cells, int32_t n_anchors, 
                     " is outside [0, " + std::to_string(n_cells) + ")";
             return KFPOS_ERR_ARG;
         }
-    if (h->coop && h->stepped) {
+    if (h->policy.coop && h->stepped) {
         g_err = "kfpos_set_anchor_cells: this handle runs the 8-lanes-per-tag kernel, which sums in another order than the "
                 "cells kernels, and has already stepped (call it before the first step, or create the handle under KFPOS_NO_COOP=1)";
         return KFPOS_ERR_STATE;
@@ -488,20 +410,16 @@ int kfpos_set_anchor_cells(kfpos_handle *h, int32_t n_cells, int32_t n_anchors, 
     if (p.bytes() > 64 * 1024)
         HIPCHK(hipFuncSetAttribute((const void *)cells_kernel(h, p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.bytes()));
     const size_t stride = 3 * (size_t)h->cfg.max_anchors;
-    double *tab = h->d_cell_xyz;
-    int32_t *map = h->d_cell_of_block;
-    if ((size_t)n_cells > h->cell_cap) HIPCHK(hipMalloc((void **)&tab, (size_t)n_cells * stride * sizeof(double)));
-    if (!map && hipMalloc((void **)&map, n_blocks * sizeof(int32_t)) != hipSuccess) {
-        if (tab != h->d_cell_xyz) (void)hipFree(tab);
+    DevPtr<double> tab; /* both or neither: a table that grew replaces the old one once the map has its room too */
+    if ((size_t)n_cells > h->cell_cap) HIPCHK(hipMalloc((void **)tab.out(), (size_t)n_cells * stride * sizeof(double)));
+    if (!h->d_cell_of_block && hipMalloc((void **)h->d_cell_of_block.out(), n_blocks * sizeof(int32_t)) != hipSuccess) {
         g_err = "hipMalloc(cell_of_block) failed";
         return KFPOS_ERR_HIP;
     }
-    if (tab != h->d_cell_xyz) {
-        if (h->d_cell_xyz) (void)hipFree(h->d_cell_xyz);
-        h->d_cell_xyz = tab;
+    if (tab) {
+        h->d_cell_xyz = std::move(tab);
         h->cell_cap = (size_t)n_cells;
     }
-    h->d_cell_of_block = map;
     /* the table as the kernels read it: n_anchors rows per cell, zeros up to max_anchors */
     std::vector<double> padded((size_t)n_cells * stride, 0.0);
     for (size_t c = 0; c < (size_t)n_cells; ++c)
@@ -512,7 +430,7 @@ int kfpos_set_anchor_cells(kfpos_handle *h, int32_t n_cells, int32_t n_anchors, 
     h->A = n_anchors;
     h->have_anchors = true;
     h->n_cells = n_cells;
-    h->coop = false; /* (not stepped, or never was: see above) */
+    h->policy.coop = false; /* the one change of the policy after kfpos_create (not stepped, or never was: see above) */
     return KFPOS_OK;
 }
 int kfpos_anchor_cells(const kfpos_handle *h) { return h ? h->n_cells : 0; }
@@ -817,10 +735,8 @@ extern "C++" int rows_reserve(kfpos_handle *h, size_t n) {
     size_t cap = n > 2 * h->work_cap ? n : 2 * h->work_cap;
     if (cap > (size_t)h->cfg.n_tags) cap = h->cfg.n_tags;
     HIPCHK(hipDeviceSynchronize());
-    if (h->d_work) (void)hipFree(h->d_work);
-    h->d_work = nullptr;
     h->work_cap = 0;
-    HIPCHK(hipMalloc((void **)&h->d_work, kfpos_layout::rows_layout(handle_sizes(h), KFPOS_N_SLOTS, cap, cap).total));
+    HIPCHK(hipMalloc((void **)h->d_work.out(), kfpos_layout::rows_layout(handle_sizes(h), KFPOS_N_SLOTS, cap, cap).total));
     h->work_cap = cap;
     return KFPOS_OK;
 }

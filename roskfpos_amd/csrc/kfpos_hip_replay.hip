@@ -82,7 +82,7 @@ int ranging_lead(kfpos_handle *h, int lead, int n_events, const double *dt_event
     a.mode = MODE_TOA;
     a.stride_ranges = stride_ranges;
     a.stride_err = stride_err;
-    const int chunk = status_events ? 1 : h->trace_chunk;
+    const int chunk = status_events ? 1 : h->policy.trace_chunk;
     for (int s0 = 0; s0 < lead; s0 += chunk) {
         const int n = lead - s0 < chunk ? lead - s0 : chunk;
         a.n_steps = n;
@@ -135,7 +135,7 @@ template <class K, class Args, class Own>
 int replay_launches(kfpos_handle *h, K kern, const Plan &p, Args &ev, const uint8_t *kinds, int n_kinds, int first,
                     int n_events, double *trajectory, uint32_t *status_events, uint32_t *status, hipStream_t s, Own own) {
     const size_t T = h->cfg.n_tags;
-    for (kfpos_replay_cut c(kinds, n_events, first, h->trace_chunk, n_kinds); c.next();) {
+    for (kfpos_replay_cut c(kinds, n_events, first, h->policy.trace_chunk, n_kinds); c.next();) {
         ev.k.n_steps = c.n;
         ev.k.traj = trajectory ? trajectory + (size_t)c.e0 * 3 * T : nullptr;
         ev.status_events = status_events ? status_events + (size_t)c.e0 * T : nullptr;
@@ -209,7 +209,7 @@ int kfpos_run_trace_dev(kfpos_handle *h, int32_t n_steps, const int32_t *range_m
     a.stride_cov = stride_cov;
     const size_t r = h->msz;
     /* the kernels whiten the accelerometer covariance once per launch: a covariance per epoch means one epoch per launch */
-    const int chunk = (accel && stride_cov != 0) ? 1 : h->trace_chunk;
+    const int chunk = (accel && stride_cov != 0) ? 1 : h->policy.trace_chunk;
     /* Up to `chunk` epochs per launch: the kernel keeps every tag's state in registers across them, so
      * state traffic and launch boundaries are paid once per chunk instead of once per epoch. (A loop of its own, not
      * ranging_lead: the sample, its covariance and the latch, a status every launch writes.) */
@@ -321,7 +321,7 @@ int kfpos_run_trace_each_dev(kfpos_handle *h, int32_t n_steps, const double *dt_
     /* The 8-lanes-per-tag kernel sums in another order and has a contraction mode of its own (kfpos_k_coop.hip): a
      * one-tag-per-lane replay would not match what this handle's single calls compute. Such a handle runs its slots
      * as those single calls, one launch each: the same bits, not fused. */
-    if (h->coop)
+    if (h->policy.coop)
         return ranging_lead_each(h, n_steps, n_steps, dt_steps_dev, range_mm, stride_ranges, err_est, stride_err, trajectory,
                                  status_steps, status, s);
     /* k_trace_toa6_each; a bank with more wavefronts than SIMDs runs it too (the two-wavefront build of the single

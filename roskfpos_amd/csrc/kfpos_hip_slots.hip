@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 
 #include "kfpos_host.h"
 
@@ -26,25 +27,21 @@ namespace {
 
 int slots_init(kfpos_handle *h) {
     if (h->s_copy) return KFPOS_OK;
-    {
-        const char *e = getenv("KFPOS_SLOT_SPLIT_BYTES");
-        h->split_bytes = e ? (size_t)atol(e) : 0; /* off: measured slower inside the pipeline (profiles/r02i_*) */
-    }
     h->so = kfpos_layout::slot_layout(handle_sizes(h));
     const size_t bytes = h->so.bytes;
-    HIPCHK(hipStreamCreateWithFlags(&h->s_copy, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&h->s_copy2, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&h->s_comp, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&h->s_back, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(h->s_copy.out(), hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(h->s_copy2.out(), hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(h->s_comp.out(), hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(h->s_back.out(), hipStreamNonBlocking));
     for (auto &sl : h->slot) {
-        HIPCHK(hipHostMalloc((void **)&sl.host, bytes, hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&sl.dev, bytes));
+        HIPCHK(hipHostMalloc((void **)sl.host.out(), bytes, hipHostMallocDefault));
+        HIPCHK(hipMalloc((void **)sl.dev.out(), bytes));
         std::memset(sl.host, 0, bytes);
         HIPCHK(hipMemset(sl.dev, 0, bytes));
-        HIPCHK(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&sl.copied2, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&sl.computed, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(sl.copied.out(), hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(sl.copied2.out(), hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(sl.computed.out(), hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(sl.done.out(), hipEventDisableTiming));
     }
     HIPCHK(hipDeviceSynchronize()); /* whatever the other entry points queued on the default stream comes first */
     return KFPOS_OK;
@@ -58,7 +55,7 @@ int slot_acquire(kfpos_handle *h, int32_t slot, bool listed, kfpos_epoch_slot *o
     const int rc = slots_init(h);
     if (rc) return rc;
     auto &sl = h->slot[slot];
-    if (listed && !sl.rows) HIPCHK(hipHostMalloc((void **)&sl.rows, sizeof(int32_t) * h->cfg.n_tags, hipHostMallocDefault));
+    if (listed && !sl.rows) HIPCHK(hipHostMalloc((void **)sl.rows.out(), sizeof(int32_t) * h->cfg.n_tags, hipHostMallocDefault));
     if (sl.busy) {
         HIPCHK(hipEventSynchronize(sl.done));
         sl.busy = false;
@@ -109,23 +106,22 @@ int d16_init(kfpos_handle *h) {
     h->d16 = kfpos_layout::delta_layout(handle_sizes(h));
     for (auto &sl : h->slot) {
         if (!sl.d16_host) {
-            HIPCHK(hipHostMalloc((void **)&sl.d16_host, h->d16.bytes, hipHostMallocDefault));
+            HIPCHK(hipHostMalloc((void **)sl.d16_host.out(), h->d16.bytes, hipHostMallocDefault));
             std::memset(sl.d16_host, 0, h->d16.bytes);
         }
         if (!sl.d16_dev) {
-            HIPCHK(hipMalloc((void **)&sl.d16_dev, h->d16.bytes));
+            HIPCHK(hipMalloc((void **)sl.d16_dev.out(), h->d16.bytes));
             HIPCHK(hipMemset(sl.d16_dev, 0, h->d16.bytes));
         }
     }
     h->d16_mirror.assign(n, 0);
-    int32_t *base = nullptr;
-    HIPCHK(hipMalloc((void **)&base, n * sizeof(int32_t)));
+    DevPtr<int32_t> base;
+    HIPCHK(hipMalloc((void **)base.out(), n * sizeof(int32_t)));
     if (hipMemset(base, 0, n * sizeof(int32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(base);
         g_err = "kfpos_slot_delta: clearing the device base failed";
         return KFPOS_ERR_HIP;
     }
-    h->d16_base = base;
+    h->d16_base = std::move(base);
     return KFPOS_OK;
 }
 
@@ -237,7 +233,7 @@ int submit_whole(kfpos_handle *h, int32_t slot, int32_t flags, double dt_shared)
      * (KFPOS_SLOT_SPLIT_BYTES=n turns that on for copies of n bytes and more; default off). */
     bool second = false;
     auto h2d = [&](size_t off, size_t bytes) -> hipError_t {
-        if (h->split_bytes == 0 || bytes < h->split_bytes) return hipMemcpyAsync(sl.dev + off, sl.host + off, bytes, hipMemcpyHostToDevice, h->s_copy);
+        if (h->policy.slot_split_bytes == 0 || bytes < h->policy.slot_split_bytes) return hipMemcpyAsync(sl.dev + off, sl.host + off, bytes, hipMemcpyHostToDevice, h->s_copy);
         const size_t half = (bytes / 2 + 255) & ~(size_t)255;
         hipError_t e = hipMemcpyAsync(sl.dev + off, sl.host + off, half, hipMemcpyHostToDevice, h->s_copy);
         if (e != hipSuccess) return e;
@@ -418,8 +414,8 @@ int kfpos_slot_submit_rows(kfpos_handle *h, int32_t slot, int32_t flags, int32_t
     if (r.answer) return round_refusal(r.answer);
     const size_t cap = h->cfg.n_tags;
     if (pose_cov && !sl.pose_host) { /* first use of the flag in this slot */
-        HIPCHK(hipHostMalloc((void **)&sl.pose_host, cap * 12 * sizeof(double), hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&sl.pose_dev, cap * 12 * sizeof(double)));
+        HIPCHK(hipHostMalloc((void **)sl.pose_host.out(), cap * 12 * sizeof(double), hipHostMallocDefault));
+        HIPCHK(hipMalloc((void **)sl.pose_dev.out(), cap * 12 * sizeof(double)));
     }
     if ((rc = rows_reserve(h, (size_t)n))) return rc;
     const kfpos_layout::Rows L = rows_layout(h, (size_t)n);

@@ -50,10 +50,8 @@ inline kfpos_layout::Sizes handle_sizes(const kfpos_handle *h) {
 inline kfpos_layout::Rows rows_layout(const kfpos_handle *h, size_t n) { /* the work block as it is, n tags listed */
     return kfpos_layout::rows_layout(handle_sizes(h), KFPOS_N_SLOTS, h->work_cap, n);
 }
-/* what launch selection depends on (kfpos_launch_plan.h): the handle's configuration and kfpos_create's policy flags */
-inline kfpos_plan::Inputs plan_inputs(const kfpos_handle *h) {
-    return {h->cfg.model, h->cfg.storage, h->cfg.max_anchors, h->full != 0, h->cfg.ignore_worst != 0, h->cfg.top_n != 0,
-            h->force_generic, h->coop, h->two_waves, h->planar_sensors};
+inline kfpos_plan::Inputs plan_inputs(const kfpos_handle *h) { /* kfpos_policy.h, of the handle as it is now */
+    return kfpos_policy::plan_inputs(h->cfg, h->policy, h->full != 0, h->planar_sensors);
 }
 KFPOS_HIDDEN void fill_args(const kfpos_handle *h, kfpos_k::KArgs &a);           /* the handle's part of every argument block */
 KFPOS_HIDDEN int launch_step(kfpos_handle *h, const kfpos_k::KArgs &a, hipStream_t s); /* the step kernel of the handle, a.T tags */

@@ -12,6 +12,8 @@
 
 #include "../../include/kfpos.h"
 #include "kfpos_host_layout.h"
+#include "kfpos_owned.h"
+#include "kfpos_policy.h"
 
 #define KFPOS_N_SLOTS 3      /* streaming host API: one slot being filled, one on the bus, one computing / returning */
 
@@ -33,6 +35,13 @@ struct KfposDevScope {
     KfposDevScope &operator=(const KfposDevScope &) = delete;
 };
 
+/* What the handle and the communicator own gives itself back when they are deleted: nothing else frees anything. A raw
+ * pointer, event or stream beside these points into a block or names somebody else's, and says so. */
+template <class T> using DevPtr = kfpos_owned::Owned<T *, hipFree>;
+template <class T> using PinnedPtr = kfpos_owned::Owned<T *, hipHostFree>;
+using Event = kfpos_owned::Owned<hipEvent_t, hipEventDestroy>;
+using Stream = kfpos_owned::Owned<hipStream_t, hipStreamDestroy>;
+
 struct kfpos_handle {
     kfpos_config cfg;
     int n;        /* state dimension */
@@ -42,13 +51,7 @@ struct kfpos_handle {
     int msz;      /* sizeof(kfpos_real): bytes per measurement element */
     int A;        /* anchors set */
     bool have_anchors, stepped;
-    int trace_chunk;    /* epochs per launch in kfpos_run_trace_dev (KFPOS_TRACE_CHUNK_STEPS, 1..128) */
-    bool force_generic; /* KFPOS_GENERIC_KERNEL=1: always the LDS-staged kernel (A/B measurements, tests) */
-    bool two_waves;     /* n_tags / 64 exceeds the device's SIMD count (KFPOS_ONE_WAVE_BUILD=1: never) */
-    bool pair9;         /* 9-state bank: iekf9_pairs for the tail of the gain iteration; bit-identical either way. Default: on in KFPOS_STORE_MIXED and KFPOS_STORE_P48, whose pair trips read registers only (2.8 % fewer cycles per epoch), off in the other two; KFPOS_PAIR9=0 / =1 overrides (profiles/HISTORY.md, "The pairs' tail") */
-    int pair9_first, pair9_dense_until; /* ... and where the lanes of a wavefront meet to look for the hand-over (iekf9_next_meet): KFPOS_PAIR9_MEET=first,dense_until, 1 <= first <= dense_until <= 20, default 8,10; 8,8 = after 8 solves, then every 4 (profiles/HISTORY.md, "Where the lanes meet") */
-    bool imu9_diag;     /* 9-state bank: wavefronts with diagonal accelerometer covariances take the diagonal form of the gain iteration (bit-identical); KFPOS_IMU9_DIAG=0 disables */
-    bool coop;          /* small plain 6-state bank: one tag per 8 lanes (k_step_toa6_coop); KFPOS_NO_COOP=1 disables */
+    kfpos_policy::Policy policy; /* kfpos_create's choices (kfpos_policy.h), fixed from then on but for policy.coop */
     double anchors[KFPOS_MAX_ANCHORS * 3];
     /* anchor cells (kfpos_set_anchor_cells): n_cells > 0 = every block of KFPOS_CELL_TAGS rows ranges against the table
      * of its cell, and ranging rounds run the cells kernels (kfpos_k_cells*.hip). d_cell_xyz: [n_cells][max_anchors][3],
@@ -56,67 +59,69 @@ struct kfpos_handle {
      * Both stay allocated when kfpos_set_anchors returns the handle to one table (n_cells = 0). */
     int n_cells = 0;
     size_t cell_cap = 0;
-    double *d_cell_xyz = nullptr;
-    int32_t *d_cell_of_block = nullptr;
+    DevPtr<double> d_cell_xyz;
+    DevPtr<int32_t> d_cell_of_block;
     /* device state */
-    double *d_pos = nullptr;
-    double *d_vel = nullptr;
-    void *d_P = nullptr, *d_imu_acc = nullptr, *d_imu_cov = nullptr;
-    uint32_t *d_flags = nullptr;
+    DevPtr<double> d_pos, d_vel;
+    DevPtr<void> d_P, d_imu_acc, d_imu_cov;
+    DevPtr<uint32_t> d_flags;
     /* staging for the host-buffer API */
-    int32_t *d_ranges = nullptr;
-    void *d_err = nullptr, *d_accel = nullptr, *d_cov = nullptr;
-    double *d_dt = nullptr, *d_out = nullptr; /* d_out: [15][T] doubles for pose results */
-    uint32_t *d_status = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevPtr<int32_t> d_ranges;
+    DevPtr<void> d_err, d_accel, d_cov;
+    DevPtr<double> d_dt, d_out; /* d_out: [15][T] doubles for pose results */
+    DevPtr<uint32_t> d_status;
+    Event ev0, ev1;
     /* planar filter */
     kfpos_planar_config planar = {};
     bool planar_sensors = false; /* a PX4Flow / IMU / magnetometer / compass sample has been fed: latches are live */
-    double *d_latch = nullptr;   /* [15][T] */
-    double *d_sensor = nullptr;  /* [24][T] staging of one sensor sample */
+    DevPtr<double> d_latch;      /* [15][T] */
+    DevPtr<double> d_sensor;     /* [24][T] staging of one sensor sample */
     /* row-major staging area of the host-buffer API: one region per array of a call (bump-allocated) */
-    unsigned char *d_stage = nullptr;
+    DevPtr<unsigned char> d_stage;
     size_t stage_cap = 0, stage_used = 0;
     /* small banks (the single-tag adaptor objects, test banks): ONE host-pinned, device-mapped block holds every
      * input and output of a host-API call in component-major form; the kernels read and write it in place over the
      * bus, so a call is "turn the layout on the CPU, launch, synchronise" -- no hipMemcpy, no layout kernels */
-    unsigned char *sm_h = nullptr, *sm_d = nullptr;
+    PinnedPtr<unsigned char> sm_h;
+    unsigned char *sm_d = nullptr; /* sm_h as the device sees it: not owning */
     kfpos_layout::Mapped sm = {}; /* sm.bytes, the whole block: nothing in it outlives a call, so the per-tag accessors stage through all of it */
     /* streaming host API: KFPOS_N_SLOTS slots of pinned host + device buffers, three streams (kfpos_slot_*) */
     struct Slot {
-        unsigned char *host = nullptr; /* pinned block: ranges | err | accel | cov | dt | status | pos */
-        unsigned char *dev = nullptr;  /* device block, same layout */
-        hipEvent_t copied = nullptr, copied2 = nullptr, computed = nullptr, done = nullptr;
+        PinnedPtr<unsigned char> host; /* pinned block: ranges | err | accel | cov | dt | status | pos */
+        DevPtr<unsigned char> dev;     /* device block, same layout */
+        Event copied, copied2, computed, done;
         /* `computed` of the last submission (of ANY slot) whose kernel read this slot's device errorEstimations /
-         * sensor covariance: an upload into those regions waits for it, whichever slot holds the current ones by then */
+         * sensor covariance: an upload into those regions waits for it, whichever slot holds the current ones by then
+         * (some slot's `computed`: not owning) */
         hipEvent_t err_reader = nullptr, cov_reader = nullptr;
         bool busy = false;
-        int32_t *rows = nullptr; /* pinned [n_tags]: the row list of a row-list round (kfpos_slot_acquire_rows) */
+        PinnedPtr<int32_t> rows; /* pinned [n_tags]: the row list of a row-list round (kfpos_slot_acquire_rows) */
         /* KFPOS_SLOT_POSE_COV, allocated by the first round that carries it: cov3x3 [n][9] at 0 and vel [n][3] at
          * 9 * n_tags doubles, pinned and on the device; pose_round: the slot's last row-list round filled them */
-        double *pose_host = nullptr, *pose_dev = nullptr;
+        PinnedPtr<double> pose_host;
+        DevPtr<double> pose_dev;
         bool pose_round = false;
         /* KFPOS_SLOT_RANGES_D16, allocated by the handle's first kfpos_slot_delta: code | esc (kfpos_layout::Delta),
          * pinned and on the device; n_esc: what kfpos_delta_slot::n_esc points at */
-        unsigned char *d16_host = nullptr, *d16_dev = nullptr;
+        PinnedPtr<unsigned char> d16_host;
+        DevPtr<unsigned char> d16_dev;
         int32_t n_esc = 0;
     } slot[KFPOS_N_SLOTS];
     /* the base of the D16 rounds: host mirror and device copy [max_anchors][n_tags]; d16_open: the slot kfpos_slot_delta
      * opened, or -1; d16_restart: the next kfpos_slot_delta zeroes both sides first */
     std::vector<int32_t> d16_mirror;
-    int32_t *d16_base = nullptr;
+    DevPtr<int32_t> d16_base;
     kfpos_layout::Delta d16 = {};
     int d16_open = -1;
     bool d16_restart = false;
     kfpos_layout::Slot so = {};
-    hipStream_t s_copy = nullptr, s_copy2 = nullptr, s_comp = nullptr, s_back = nullptr;
-    size_t split_bytes = 0;                            /* H2D copies from this size on travel as two halves on two streams */
+    Stream s_copy, s_copy2, s_comp, s_back;
     int err_slot = -1, cov_slot = -1;                  /* which slot's device block holds the current err / cov */
     /* row-list steps (kfpos_step_*_rows, kfpos_slot_submit_rows): one device block, allocated on first use, grown to the
      * largest n seen (never beyond n_tags): KFPOS_N_SLOTS input areas -- what a round uploads (rows, row-major inputs,
      * dt) and returns (status, pos); fixed places, since the copy stream runs ahead of the compute stream -- followed by
      * the work bank: the listed tags' state and the turned inputs at stride n, used on one stream in submission order */
-    unsigned char *d_work = nullptr;
+    DevPtr<unsigned char> d_work;
     size_t work_cap = 0;                               /* listed tags it holds */
     std::vector<uint32_t> row_stamp;                   /* [n_tags] host: the call that last listed a row (duplicate check in O(n)) */
     uint32_t stamp = 0;

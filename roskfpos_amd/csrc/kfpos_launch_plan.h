@@ -37,8 +37,8 @@ constexpr size_t PARK9_DOUBLES = 78 * LANES + 24;
 /* k_step_toa6_w2: covariance entries per lane parked during the ML solve -- what 160 KB / 8 leave next to the epoch */
 constexpr int toa6_w2_park(size_t msz) { return msz == 4 ? 19 : 15; }
 
-/* what the decision depends on. How kfpos_create derives the last four (environment, device, the 8 192-tag limit of
- * coop, p48 + full + leave-one-out = force_generic) is its own business */
+/* what the decision depends on. kfpos_policy.h derives them from a configuration (environment, device, the 8 192-tag
+ * limit of coop, p48 + full + leave-one-out = force_generic) and says which combinations exist: producible() */
 struct Inputs {
     int model, storage, max_anchors;
     bool full, ignore_worst, top_n;

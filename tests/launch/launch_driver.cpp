@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "kfpos_launch_plan.h"
+#include "kfpos_policy.h"
 
 using namespace kfpos_plan;
 
@@ -89,12 +90,7 @@ int main() {
                            (bits & 8) != 0, (bits & 16) != 0, (bits & 32) != 0, (bits & 64) != 0};
         const Launch what = (Launch)w;
         const bool toa = model == KFPOS_MODEL_TOA, imu9 = model == KFPOS_MODEL_TOA_IMU, planar = model == KFPOS_MODEL_PLANAR;
-        /* what kfpos_create refuses or never produces */
-        if (in.full && !toa) continue;                                     /* the non-symmetric layout: 6-state, ML start */
-        if ((in.ignore_worst && !toa) || (in.top_n && !toa && model != KFPOS_MODEL_ML)) continue;
-        if (in.coop && (!toa || in.force_generic || in.full || in.ignore_worst || in.top_n || A > 8)) continue;
-        if (in.full && in.ignore_worst && storage == KFPOS_STORE_P48 && !in.force_generic) continue;
-        if (in.planar_sensors && !planar) continue;
+        if (!kfpos_policy::producible(in)) continue; /* what kfpos_create refuses or never produces */
         /* launches no entry point makes */
         if ((what == STEP_IMU_ONLY || what == EVENTS9) && !imu9) continue;
         if ((what == STEP_SENSOR || what == EVENTS_PLANAR) && !planar) continue;

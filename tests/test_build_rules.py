@@ -174,12 +174,13 @@ def test_a_kernel_unit_sees_no_host_header_and_a_host_unit_no_device_header():
             assert os.path.exists(os.path.join(CSRC, h)), (u, h)
         names = {os.path.basename(h) for h in seen}
         if u in kernels:
-            assert not names & {"kfpos_internal.h", "kfpos_host.h"}, (u, sorted(names))
+            assert not names & {"kfpos_internal.h", "kfpos_host.h", "kfpos_policy.h", "kfpos_owned.h"}, (u, sorted(names))
             assert "kfpos_kargs.h" in names, (u, sorted(names))
         if u in ("kfpos_k_d16", "kfpos_k_tags"):
             assert not [h for h in names if h.startswith("kfpos_core")], (u, sorted(names))
         if u in hosts:
-            assert "kfpos_kernels.h" not in names and {"kfpos_host.h", "kfpos_internal.h"} <= names, (u, sorted(names))
+            assert "kfpos_kernels.h" not in names, (u, sorted(names))
+            assert {"kfpos_host.h", "kfpos_internal.h", "kfpos_policy.h", "kfpos_owned.h"} <= names, (u, sorted(names))
 
 
 def _would_rebuild(*touched):
@@ -198,6 +199,7 @@ def test_a_touched_header_rebuilds_its_side_only():
     _built()
     assert _would_rebuild() == set(), "the library as built is up to date"
     host = _would_rebuild("kfpos_internal.h", "kfpos_host.h")
+    assert host == _would_rebuild("kfpos_policy.h") == _would_rebuild("kfpos_owned.h")
     assert host == {"kfpos_hip", "kfpos_hip_state", "kfpos_hip_slots", "kfpos_hip_replay", "kfpos_comm"}, sorted(host)
     device = _would_rebuild("kfpos_kernels.h")
     assert device and all(u.startswith("kfpos_k_") for u in device), sorted(device)
